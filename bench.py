@@ -10,9 +10,12 @@ Workload at N=1: BASELINE.json configs[1] — ONE ~30k-point synthetic smplsynth
 them with no data-path collective ("scaling": "weak"): per-GPU work is fixed as N grows.
 
 Rank 0 prints ONE JSON line; `value` = GN iterations of all frames on all ranks / max-over-ranks wall time of the
-timed region, inputs already resident in HBM.  `roofline` is for the kernel class with the largest share of device
-time; `cpu_baseline` times the CPU oracle (a scalar fp64 restatement of the reference algorithm, not Ceres) on
-this host's cores on the same frame.
+timed region, inputs already resident in HBM; `ms_per_step` = that time / K.  A plain run sets up, runs W warm-up
+steps, times exactly K steps and prints the line.  `--full` adds everything else: the timed region repeated (median of
+15), the instrumented passes behind `roofline` (the kernel class with the largest share of device time), the secondary
+configurations, the stages beside the path, the batch-split checks, and `cpu_baseline`, which times the CPU oracle (a
+scalar fp64 restatement of the reference algorithm, not Ceres) on this host's cores on the same frame.
+`--dump-outputs DIR` writes the fitted states and statistics of the last timed step (rank 0's frames) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -124,10 +127,12 @@ def _max_over_ranks(x, torch, dist, world, backend):
     return float(te.item())
 
 
-def measure(api, synth, Options, torch, dist, smpl, gm, args, F, steps, warmup, rank, world, local_rank, dense, shard=None, regions=REGIONS, lm_policy=None):
+def measure(api, synth, Options, torch, dist, smpl, gm, args, F, steps, warmup, rank, world, local_rank, dense, shard=None, regions=REGIONS, lm_policy=None,
+            full=True):
     """Times `steps` optimize() calls over this rank's F resident frames, `regions` times; returns the per-config dict.
     Global frame g = rank + world * i is frame i of this rank (avt_shard partition); with a shard handle every step also
-    enqueues the result all-gather (RCCL, device buffers) behind optimize()."""
+    enqueues the result all-gather (RCCL, device buffers) behind optimize().  full=False: `warmup` steps, the timed
+    regions and the download of the results, nothing else (no instrumented passes, roofline, host-to-host leg or checks)."""
     V, J, K, P = gm.numPoints(), gm.numJoints(), gm.numShapeKeys(), gm.arrays.P
     pm = synth.identity_part_map()
     B = F * world
@@ -146,7 +151,6 @@ def measure(api, synth, Options, torch, dist, smpl, gm, args, F, steps, warmup, 
     p0 = np.array([s[1] for s in starts])
     q0 = api.rot_to_quat(np.array([s[2] for s in starts]).reshape(-1, 3, 3)).reshape(F, J, 4)
     w0 = np.array([s[0] for s in starts])
-    d0, l0 = ctx.frame_download(0)
     ctx.state_upload(p0, q0, w0)          # the tracking start states (109 doubles per frame): resident like the frames
     groups, nfg, G = ctx.launch_shape()
 
@@ -164,31 +168,33 @@ def measure(api, synth, Options, torch, dist, smpl, gm, args, F, steps, warmup, 
         if world > 1:
             dist.barrier()
 
-    # which kernel class dominates this configuration (one instrumented, untimed step: same frame groups and launch shapes
-    # as the replayed graph, run back to back on one stream with HIP events around every launch)
-    for _ in range(max(1, warmup)):
+    if full:
+        d0, l0 = ctx.frame_download(0)
+        # which kernel class dominates this configuration (one instrumented, untimed step: same frame groups and launch shapes
+        # as the replayed graph, run back to back on one stream with HIP events around every launch)
+        for _ in range(max(1, warmup)):
+            step()
+        ctx.sync()
+        ctx.profile_begin()
         step()
-    ctx.sync()
-    ctx.profile_begin()
-    step()
-    ctx.sync()
-    prof = ctx.profile_end()
-    dominant = max(prof, key=lambda k: prof[k][0])
-    # the roofline object describes the kernel on the CRITICAL path.  One frame group: the class with the most device time
-    # (one frame: k_solve).  Two frame groups on two streams: the single-workgroup-per-frame solves of one group hide behind the
-    # evaluation of the other, so the evaluation is the class that bounds the step whatever the summed device times say.
-    moments_run = args.data_term == "moments" or (args.data_term == "auto" and nfg >= ctx.tuning().mom_min_frames)
-    if groups >= 2 and not moments_run:
-        dominant = "eval"      # (moment form: every class of the GN loop is a short launch of the same chain - the one with the most device time stands)
-    for _ in range(warmup):
-        step()
-    # HIP events only around the dominant kernel class, on the stream it is launched on, over K steps
-    full_sync()
-    ctx.profile_begin(classes=[dominant])
-    for _ in range(steps):
-        step()
-    ctx.sync()
-    prof_timed = ctx.profile_end()
+        ctx.sync()
+        prof = ctx.profile_end()
+        dominant = max(prof, key=lambda k: prof[k][0])
+        # the roofline object describes the kernel on the CRITICAL path.  One frame group: the class with the most device time
+        # (one frame: k_solve).  Two frame groups on two streams: the single-workgroup-per-frame solves of one group hide behind the
+        # evaluation of the other, so the evaluation is the class that bounds the step whatever the summed device times say.
+        moments_run = args.data_term == "moments" or (args.data_term == "auto" and nfg >= ctx.tuning().mom_min_frames)
+        if groups >= 2 and not moments_run:
+            dominant = "eval"      # (moment form: every class of the GN loop is a short launch of the same chain - the one with the most device time stands)
+        for _ in range(warmup):
+            step()
+        # HIP events only around the dominant kernel class, on the stream it is launched on, over K steps
+        full_sync()
+        ctx.profile_begin(classes=[dominant])
+        for _ in range(steps):
+            step()
+        ctx.sync()
+        prof_timed = ctx.profile_end()
     # the timed regions proper: no event records; EXACTLY `steps` steps each, barrier + synchronize on both sides,
     # max over ranks; the reported value is the median region
     for _ in range(warmup):
@@ -213,10 +219,23 @@ def measure(api, synth, Options, torch, dist, smpl, gm, args, F, steps, warmup, 
     gn_per_step = F * opt.icp_iters * opt.max_iters_per_icp
     res = {"value": world * gn_per_step * steps / med, "elapsed": med, "elapsed_min": times_sorted[0], "elapsed_max": times_sorted[-1],
            "regions": regions, "steps": steps, "F": F}
-    tot = sum(v[0] for v in prof.values())
-    res["kernels"] = {k: {"ms": round(v[0], 5), "launches": v[1], "share": round(v[0] / tot, 4)} for k, v in prof.items() if v[1]}
+    # what a caller of the timed path receives after the last timed step: this rank's fitted states and their statistics
+    res["outputs"] = {"p": p, "q": q, "w": w, **{k: np.array([getattr(s, k) for s in st], np.float64) for k, _ in st[0]._fields_}}
     Nmean = float(np.mean(npts))
     M = float(np.mean([s.matched_model_points for s in st]))
+    res["tuning"] = {"values": ctx.tuning().as_dict(), "non_default": sorted(ctx.tuning().non_default()), "data_term": args.data_term,
+                     "data_term_run": "moments" if (args.data_term == "moments" or (args.data_term == "auto" and nfg >= ctx.tuning().mom_min_frames)) else "rows"}
+    res["points_per_frame"] = int(Nmean)
+    res["matched_model_points"] = int(M)
+    res["final_cost_frame0"] = st[0].final_cost
+    res["accepted_steps_frame0"] = st[0].accepted_steps
+    res["accepted_fraction"] = float(sum(s.accepted_steps for s in st)) / max(1, sum(s.gn_iterations for s in st))
+    res["opt"] = opt
+    if not full:
+        del ctx
+        return res
+    tot = sum(v[0] for v in prof.values())
+    res["kernels"] = {k: {"ms": round(v[0], 5), "launches": v[1], "share": round(v[0] / tot, 4)} for k, v in prof.items() if v[1]}
     bytes_iter = algorithmic_bytes_per_gn_iter(Nmean, V, K, P)
     bytes_launch = nfg * bytes_iter                                         # one launch covers one frame group
     avg_ms = prof_timed[dominant][0] / max(1, prof_timed[dominant][1])      # live, HIP events, this run
@@ -331,15 +350,7 @@ def measure(api, synth, Options, torch, dist, smpl, gm, args, F, steps, warmup, 
                                "equals_resident_run": bool(np.array_equal(ph, p[0].ravel()) and np.array_equal(qh, q[0].ravel()) and np.array_equal(wh, w[0].ravel())),
                                "note": "avt_optimize(ctx, data, labels, N, opt, p, q, w, stats) on pageable host memory: upload, fit, download and the synchronisation "
                                        "that ends the call inside the region; `value` (the contract's) has the frames resident in HBM"}
-    res["tuning"] = {"values": ctx.tuning().as_dict(), "non_default": sorted(ctx.tuning().non_default()), "data_term": args.data_term,
-                     "data_term_run": "moments" if (args.data_term == "moments" or (args.data_term == "auto" and nfg >= ctx.tuning().mom_min_frames)) else "rows"}
-    res["points_per_frame"] = int(Nmean)
-    res["matched_model_points"] = int(M)
-    res["final_cost_frame0"] = st[0].final_cost
-    res["accepted_steps_frame0"] = st[0].accepted_steps
-    res["accepted_fraction"] = float(sum(s.accepted_steps for s in st)) / max(1, sum(s.gn_iterations for s in st))
     res["frames0"] = {"data": d0, "labels": l0}
-    res["opt"] = opt
     res["start0"] = (p0[0], q0[0], w0[0])
     if shard is not None:      # every rank holds every frame's result; this rank's own rows must equal its local states
         pg, qg, wg, stg = shard.gather_download(ctx, B)
@@ -788,9 +799,10 @@ def compact_line(out):
         sec["dense_64"] = _triple(out["dense_batch_config"].get("64_frames"))
     if sec:
         line["configs"] = sec
-    bs = out.get("batch_split") or {}
-    line["batch_split"] = {"enabled": bs.get("enabled"), "world": bs.get("world"), "backend": str(bs.get("backend", ""))[:24],
-                           "ok": bool((bs.get("run") or {}).get("gathered_equals_local_on_every_rank", (bs.get("run") or {}).get("gathered_equals_local", False)))}
+    if "batch_split" in out:
+        bs = out["batch_split"]
+        line["batch_split"] = {"enabled": bs.get("enabled"), "world": bs.get("world"), "backend": str(bs.get("backend", ""))[:24],
+                               "ok": bool((bs.get("run") or {}).get("gathered_equals_local_on_every_rank", (bs.get("run") or {}).get("gathered_equals_local", False)))}
     line["step_rule"] = {k: v for k, v in (out.get("step_rule") or {}).items() if k != "note"}
     if out.get("fixed_factor_schedule"):
         g = out["fixed_factor_schedule"]
@@ -814,6 +826,25 @@ def compact_line(out):
             if len(s) < COMPACT_LIMIT:
                 break
     return s
+
+
+DUMP_LIMIT = 64 << 20          # bytes of --dump-outputs in all
+
+
+def dump_outputs(path, outputs, limit=DUMP_LIMIT):
+    """Writes every array of `outputs` (first axis = frame) as path/<name>.npy in float64.  When they would exceed `limit` bytes,
+    a fixed seeded sample of frames is written instead, and its frame indices as path/frame.npy."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: np.asarray(v, np.float64) for k, v in outputs.items()}
+    F = len(arrs["p"])
+    per_frame = sum(a.nbytes for a in arrs.values()) // F
+    room = limit - 128 * (len(arrs) + 1)          # (an .npy header is 128 bytes)
+    if per_frame * F > room:
+        keep = np.sort(np.random.default_rng(0).choice(F, size=room // (per_frame + 8), replace=False))
+        arrs = {k: a[keep] for k, a in arrs.items()}
+        arrs["frame"] = keep.astype(np.float64)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def spawn_plan(gpus, env, visible_devices, share_gpu0=False):
@@ -840,7 +871,12 @@ def main():
     ap.add_argument("--frames", type=int, default=1, help="independent frames per GPU (configs[2] uses 64)")
     ap.add_argument("--dense", action="store_true", help="120k-point stress frames (configs[4])")
     ap.add_argument("--icp-iters", type=int, default=1)
-    ap.add_argument("--regions", type=int, default=REGIONS, help="how many times the K-step timed region is repeated (median reported)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: instrumented passes (roofline, kernel shares, host-to-host leg), the secondary "
+                         "configurations, the stages beside the path, the CPU baselines and the batch-split checks (the --no-* options select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the fitted states and statistics of the last timed step as DIR/<name>.npy (float64)")
+    ap.add_argument("--regions", type=int, default=None,
+                    help=f"how many times the K-step timed region is repeated (median reported); default 1, {REGIONS} with --full")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-throughput-config", action="store_true", help="skip the secondary 64-frames-per-GPU measurement")
     ap.add_argument("--saturation-frames", type=int, default=512, help="frames per GPU of the saturation measurement (0 = skip)")
@@ -855,6 +891,8 @@ def main():
     ap.add_argument("--scale-only", action="store_true", help="headline + 64 frames/GPU only (the default for --gpus N > 1: what a scaling record needs)")
     ap.add_argument("--detail-file", default=os.path.join(ROOT, "bench_detail.json"), help="where the full result object goes (the stdout line is the compact one)")
     args = ap.parse_args()
+    if args.regions is None:
+        args.regions = REGIONS if args.full else 1      # a plain run times exactly --steps steps
 
     share0 = bool(os.environ.get("AVT_BENCH_SHARE_GPU0"))
     if args.gpus > 1 and not os.environ.get("WORLD_SIZE"):
@@ -940,9 +978,12 @@ def main():
         gm = api.AvatarModel(smpl)
     P = gm.arrays.P
     F = args.frames
-    r = measure(api, synth, Options, torch, dist, smpl, gm, args, F, args.steps, args.warmup, rank, world, local_rank, args.dense, shard, args.regions)
+    r = measure(api, synth, Options, torch, dist, smpl, gm, args, F, args.steps, args.warmup, rank, world, local_rank, args.dense, shard, args.regions,
+                full=args.full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r["outputs"])
     r2 = r3 = None
-    if F == 1 and not args.dense and not args.no_throughput_config:
+    if args.full and F == 1 and not args.dense and not args.no_throughput_config:
         r2 = measure(api, synth, Options, torch, dist, smpl, gm, args, 64, max(10, args.steps // 2), 3, rank, world, local_rank, False, shard, args.regions)
         if args.saturation_frames > 0 and not args.scale_only:
             r3 = measure(api, synth, Options, torch, dist, smpl, gm, args, args.saturation_frames, 5, 2, rank, world, local_rank, False, shard,
@@ -955,16 +996,17 @@ def main():
         for n, fr in ((2, 256), (4, 128)):
             rs[n] = measure(api, synth, Options, torch, dist, smpl, gm, args, fr, 5, 2, rank, world, local_rank, False, shard, max(3, args.regions // 3))
     rg = None
-    if F == 1 and not args.dense and not args.scale_only:      # the fixed-factor damping schedule (avt_options.lm_policy = 0: the default of rounds 1-5) on the headline frame
+    if args.full and F == 1 and not args.dense and not args.scale_only:      # the fixed-factor damping schedule (avt_options.lm_policy = 0: the default of rounds 1-5) on the headline frame
         rg = measure(api, synth, Options, torch, dist, smpl, gm, args, 1, max(10, args.steps // 2), 3, rank, world, local_rank, False, None, max(3, args.regions // 3), lm_policy=0)
     rd = rd16 = rd64 = None
-    if F == 1 and not args.dense and not args.no_dense_config and not args.scale_only:      # configs[4]: the dense stress frame, alone and in batches
+    if args.full and F == 1 and not args.dense and not args.no_dense_config and not args.scale_only:      # configs[4]: the dense stress frame, alone and in batches
         rd = measure(api, synth, Options, torch, dist, smpl, gm, args, 1, max(10, args.steps // 2), 3, rank, world, local_rank, True, shard, max(3, args.regions // 3))
         rd16 = measure(api, synth, Options, torch, dist, smpl, gm, args, 16, 5, 2, rank, world, local_rank, True, shard, 3)
         rd64 = measure(api, synth, Options, torch, dist, smpl, gm, args, 64, 5, 2, rank, world, local_rank, True, shard, 3)
     chk = None
     if shard is not None:
         assert shard_info.get("world") == args.gpus, "batch_split.world != n_gpus"
+    if shard is not None and args.full:
         try:
             shard.set_self_exchange(True)     # the root's own block also travels through ncclSend/ncclRecv
             chk = shard_check(api, synth, Options, shard, dist, smpl, gm, rank, world, local_rank)
@@ -1001,10 +1043,11 @@ def main():
                                       if shard is not None else f"frames sharded over {world} GPU(s), no data-path collective"},
             "timing": {"regions": r["regions"], "steps_per_region": args.steps, "statistic": "median region, max over ranks per region",
                        "ms_per_step_min_max": [round(r["elapsed_min"] / args.steps * 1e3, 4), round(r["elapsed_max"] / args.steps * 1e3, 4)]},
-            "roofline": r["roofline"], **({"roofline_nn": r["roofline_nn"]} if "roofline_nn" in r else {}), "eval_kernel": r["eval_kernel"], "kernels": r["kernels"],
+            **{k: r[k] for k in ("roofline", "roofline_nn", "eval_kernel", "kernels") if k in r},      # (the instrumented passes: --full)
             "final_cost_frame0": r["final_cost_frame0"], "accepted_steps_frame0": r["accepted_steps_frame0"], "tuning": r["tuning"],
-            "batch_split": {**shard_info, **({"run": r["shard"]} if "shard" in r else {}), **({"check": chk} if chk is not None else {})},
         }
+        if args.full:
+            out["batch_split"] = {**shard_info, **({"run": r["shard"]} if "shard" in r else {}), **({"check": chk} if chk is not None else {})}
         out["step_rule"] = {"lm_policy": int(opt.lm_policy), "lm_up": opt.lm_up, "lm_down": round(opt.lm_down, 6), "function_tolerance": opt.function_tolerance,
                             "note": "the library's default damping schedule (gain ratio since round 6); the stopping rule (default 1e-4, the reference's) is off here: the metric counts iterations"}
         if rs:
@@ -1029,7 +1072,7 @@ def main():
             out["dense_config"] = cfg(rd, "BASELINE configs[4]: ONE dense frame (2560x1440 render, ~150k points), same optimize()")
             out["dense_batch_config"] = {"16_frames": cfg(rd16, "16 dense frames per GPU (one frame group)"),
                                          "64_frames": cfg(rd64, "64 dense frames per GPU (two frame groups of 32): the dense workload as an HBM stress")}
-        if F == 1 and not args.dense and not args.no_seed_spread and not args.scale_only:
+        if args.full and F == 1 and not args.dense and not args.no_seed_spread and not args.scale_only:
             sg = seed_spread(api, synth, Options, smpl, gm, args, local_rank)                   # the default step rule (gain ratio)
             sf = seed_spread(api, synth, Options, smpl, gm, args, local_rank, lm_policy=0)      # the fixed factors
             sg["ends_lower_than_fixed_factors_on"] = int(sum(a < b for a, b in zip(sg["final_cost_by_seed"], sf["final_cost_by_seed"])))
@@ -1049,13 +1092,13 @@ def main():
         out["icp_iterations_per_s"] = round(F * world * opt.icp_iters * args.steps / r["elapsed"], 2)
         if args.scale_only:
             args.no_render_stage = args.no_label_stage = True
-        if F == 1 and not args.dense and not args.no_render_stage:
+        if args.full and F == 1 and not args.dense and not args.no_render_stage:
             out["render_stage"] = render_stage(api, synth, smpl, gm, not args.no_cpu_baseline, local_rank)
-        if F == 1 and not args.dense and not args.no_label_stage:
+        if args.full and F == 1 and not args.dense and not args.no_label_stage:
             out["label_stage"] = label_stage(synth, smpl, not args.no_cpu_baseline)
-        if F == 1 and not args.dense and not args.no_render_stage:
+        if args.full and F == 1 and not args.dense and not args.no_render_stage:
             out["tracker_stage"] = tracker_stage(api, synth, smpl, gm)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             cb = cpu_baselines(synth, smpl, r, opt, args.cpu_seconds, 64)
             out["cpu_baseline"] = cb
             out["speedup_vs_cpu_port"] = round(r["value"] / cb["value"], 1)

@@ -22,8 +22,6 @@ def build(force=False):
     src = os.path.join(_HERE, "avatar_oracle.cpp")
     if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < os.path.getmtime(src):
         subprocess.check_call(["make", "-C", _HERE, "liboracle.so"], stdout=subprocess.DEVNULL)
-    if os.path.exists("/root/reference/include/nanoflann.hpp") and (force or not os.path.exists(_REF_SO)):
-        subprocess.check_call(["make", "-C", _HERE, "ref"], stdout=subprocess.DEVNULL)
 
 
 _lib = None

@@ -45,6 +45,42 @@ def test_compact_line_survives_oversized_fields():
     assert json.loads(line)["roofline"]["frac"] > 0
 
 
+def test_compact_line_of_a_plain_run():
+    """A run without --full has no instrumented passes, secondary configurations, stages or batch-split checks: the line still
+    carries every contract key, and no verdict on a check that did not run."""
+    out = canned()
+    for k in ("roofline", "roofline_nn", "eval_kernel", "kernels", "batch_split", "cpu_baseline", "throughput_config", "saturation_config",
+              "dense_config", "dense_batch_config", "host_to_host", "value_host_to_host", "fixed_factor_schedule", "strong_scaling_prediction",
+              "tracker_stage", "render_stage", "label_stage", "single_frame_spread", "useful_iterations_12_seeds"):
+        out.pop(k, None)
+    d = json.loads(bench.compact_line(out))
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data"):
+        assert d[k] == out[k], k
+    assert d["roofline"] is None and "batch_split" not in d and "configs" not in d and "cpu_baseline" not in d
+
+
+def test_dump_outputs_float64_and_bounded(tmp_path):
+    """--dump-outputs: every array as <name>.npy in float64; above the size limit a fixed seeded sample of frames (the same one on
+    every run) with its frame indices, and the files stay within the limit."""
+    import numpy as np
+    F = 50
+    rng = np.random.default_rng(1)
+    outs = {"p": rng.standard_normal((F, 3)), "q": rng.standard_normal((F, 24, 4)), "gn_iterations": np.arange(F, dtype=np.int32)}
+    bench.dump_outputs(str(tmp_path / "all"), outs)
+    assert sorted(os.listdir(tmp_path / "all")) == ["gn_iterations.npy", "p.npy", "q.npy"]
+    for k, v in outs.items():
+        a = np.load(tmp_path / "all" / (k + ".npy"))
+        assert a.dtype == np.float64 and np.array_equal(a, v), k
+    limit = 20 * 100 * 8
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), outs, limit=limit)
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= limit
+    fr = np.load(tmp_path / "a" / "frame.npy")
+    assert 0 < len(fr) < F and np.array_equal(fr, np.load(tmp_path / "b" / "frame.npy"))
+    for k, v in outs.items():
+        assert np.array_equal(np.load(tmp_path / "a" / (k + ".npy")), v[fr.astype(int)]), k
+
+
 def test_spawn_decision():
     assert bench.spawn_plan(1, {}, 8) is None                          # one GPU: run in place
     assert bench.spawn_plan(4, {"WORLD_SIZE": "4"}, 8) is None         # already a rank of somebody's launch

@@ -1,10 +1,14 @@
-"""Row f2 pinned by the reference's own reader: the same model.npz goes through cnpy::npz_load (cnpy.cpp:246-300, compiled from
-/root/reference where it lies into oracle/_ref/libcnpy_ref.so) and through include/ark/Npz.h; shapes and every element agree.
-The reference turns a member's raw bytes into a matrix in util::loadFloatMatrix / loadUintMatrix (Util.cpp:249-300: word size 4 or
-8, column-major map when fortran_order, row-major otherwise); that rule is applied to cnpy's bytes here, member by member, with
-the interpretation AvatarModel.cpp:25-127 chooses (float for v_template / shapedirs / J_regressor / weights, unsigned for f /
-kintree_table).  Fixtures are generated, not committed."""
+"""Row f2 pinned by the reference's own reader: the same model.npz goes through cnpy::npz_load (cnpy.cpp:246-300) and through
+include/ark/Npz.h; shapes and every element agree.  What cnpy returns for each fixture - every member's word size, fortran_order
+flag, shape and the SHA-256 of its data bytes - is committed in tests/golden/npz_cnpy_golden.json (tests/golden/make_npz_golden.py,
+run where oracle/Makefile has built the reference's reader into oracle/_ref/libcnpy_ref.so; where that library exists the test
+also runs it live).  The reference turns a member's raw bytes into a matrix in util::loadFloatMatrix / loadUintMatrix
+(Util.cpp:249-300: word size 4 or 8, column-major map when fortran_order, row-major otherwise); that rule is applied to cnpy's
+bytes here, member by member, with the interpretation AvatarModel.cpp:25-127 chooses (float for v_template / shapedirs /
+J_regressor / weights, unsigned for f / kintree_table).  Fixtures are generated, not committed."""
 import ctypes as C
+import hashlib
+import json
 import os
 import subprocess
 
@@ -14,17 +18,14 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 REF_SO = os.path.join(ROOT, "oracle", "_ref", "libcnpy_ref.so")
+GOLDEN = os.path.join(HERE, "golden", "npz_cnpy_golden.json")
+VARIANTS = ("stored", "deflated", "fortran_f32", "wide_ints_foreign")
 
 FLOAT_KEYS = ("v_template", "shapedirs", "J_regressor", "weights", "posedirs")
 UINT_KEYS = ("f", "kintree_table")
 
 
 def _ref_lib():
-    if not os.path.exists(REF_SO):
-        if os.path.exists("/root/reference/cnpy.cpp"):
-            subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "ref"], stdout=subprocess.DEVNULL)
-        else:
-            pytest.skip("the reference's cnpy reader was not built (no reference tree here)")
     lib = C.CDLL(REF_SO)
     lib.cnpyref_open.restype = C.c_void_p; lib.cnpyref_open.argtypes = [C.c_char_p]
     lib.cnpyref_name.restype = C.c_char_p; lib.cnpyref_name.argtypes = [C.c_void_p, C.c_int]
@@ -69,6 +70,39 @@ def _load_ref(lib, path):
     return out
 
 
+def _golden_ref(path, variant, arrs):
+    """What _load_ref returns for the fixture of `variant` at `path`, from the committed record of the reference's reader: word size,
+    order flag and shape as cnpy reported them, and the member's bytes, which must hash to what cnpy returned."""
+    out = {}
+    for name, (ws, fo, shape, sha) in json.load(open(GOLDEN))[variant].items():
+        raw = np.frombuffer(np.asarray(arrs[name]).tobytes(order="F" if fo else "C"), np.uint8)
+        assert hashlib.sha256(raw.tobytes()).hexdigest() == sha, name
+        out[name] = (ws, fo, tuple(shape), raw)
+    if os.path.exists(REF_SO):          # the reference's reader is built here: it must still read what the record says
+        live = _load_ref(_ref_lib(), path)
+        assert set(live) == set(out)
+        for name, (ws, fo, shape, raw) in live.items():
+            assert (ws, fo, shape) == out[name][:3] and np.array_equal(raw, out[name][3]), name
+    return out
+
+
+def write_fixture(smpl, variant, path):
+    """Writes the model.npz of `variant` to `path`; returns its members."""
+    rng = np.random.default_rng(3)
+    arrs = _model_arrays(smpl, rng)
+    if variant == "fortran_f32":        # Fortran-order members and float32 members (SMPL exports carry both)
+        arrs["weights"] = np.asfortranarray(arrs["weights"])
+        arrs["J_regressor"] = np.asfortranarray(arrs["J_regressor"].astype(np.float32))
+        arrs["v_template"] = arrs["v_template"].astype(np.float32)
+        arrs["f"] = np.asfortranarray(arrs["f"])
+    if variant == "wide_ints_foreign":  # 64-bit index arrays plus members that are not numeric arrays at all
+        arrs["f"] = arrs["f"].astype(np.uint64)
+        arrs["kintree_table"] = arrs["kintree_table"].astype(np.int64)
+        arrs["bs_style"] = np.array("lbs"); arrs["is_female"] = np.array(True); arrs["names"] = np.array(["a", "bcd"])
+    (np.savez_compressed if variant == "deflated" else np.savez)(path, **arrs)
+    return arrs
+
+
 def _load_ark(lib, path):
     h = lib.arknpz_open(path.encode())
     err = lib.arknpz_error(h).decode()
@@ -103,23 +137,11 @@ def _model_arrays(smpl, rng):
                 f=np.asarray(smpl["f"], np.uint32), kintree_table=kt, posedirs=rng.standard_normal((V, 3, 9)))
 
 
-@pytest.mark.parametrize("variant", ["stored", "deflated", "fortran_f32", "wide_ints_foreign"])
+@pytest.mark.parametrize("variant", VARIANTS)
 def test_ark_npz_reads_what_the_references_cnpy_reads(smpl, tmp_path, ark_lib, variant):
-    ref = _ref_lib()
-    rng = np.random.default_rng(3)
-    arrs = _model_arrays(smpl, rng)
-    if variant == "fortran_f32":        # Fortran-order members and float32 members (SMPL exports carry both)
-        arrs["weights"] = np.asfortranarray(arrs["weights"])
-        arrs["J_regressor"] = np.asfortranarray(arrs["J_regressor"].astype(np.float32))
-        arrs["v_template"] = arrs["v_template"].astype(np.float32)
-        arrs["f"] = np.asfortranarray(arrs["f"])
-    if variant == "wide_ints_foreign":  # 64-bit index arrays plus members that are not numeric arrays at all
-        arrs["f"] = arrs["f"].astype(np.uint64)
-        arrs["kintree_table"] = arrs["kintree_table"].astype(np.int64)
-        arrs["bs_style"] = np.array("lbs"); arrs["is_female"] = np.array(True); arrs["names"] = np.array(["a", "bcd"])
     path = str(tmp_path / "model.npz")
-    (np.savez_compressed if variant == "deflated" else np.savez)(path, **arrs)
-    r = _load_ref(ref, path)
+    arrs = write_fixture(smpl, variant, path)
+    r = _golden_ref(path, variant, arrs)
     a = _load_ark(ark_lib, path)
     assert set(r) == set(arrs)                            # the reference's reader keeps every member
     for key in FLOAT_KEYS + UINT_KEYS:

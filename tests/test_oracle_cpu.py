@@ -49,16 +49,18 @@ def test_oracle_nn_matches_nanoflann_golden(omodel):
 
 
 def test_oracle_nn_live_against_reference_build(smpl, omodel):
+    """Frame 11 against the reference's nanoflann: its index array is committed (tests/golden/nn_golden_frame11.npz, made by
+    make_nn_golden_frame11.py); where oracle/_ref is built the reference's search also runs live."""
     from oracle import oracle as orc
-    if not orc.have_reference_nn():
-        pytest.skip("oracle/_ref not built (reference tree absent)")
-    fr = synth.make_frame(smpl, 11)
-    w0, p0, R0 = fr["start"]
-    cloud, _, _ = omodel.update(w0, p0, R0)
-    vis = omodel.visibility(cloud)
-    pm = synth.identity_part_map()
-    ref, _ = orc.reference_nn(pm[omodel.main_joint()].astype(np.int32), cloud, vis, fr["data"], fr["labels"], 24)
-    assert np.array_equal(ref, omodel.nn(pm, 24, cloud, vis, fr["data"], fr["labels"]))
+    sys.path.insert(0, os.path.join(HERE, "golden"))
+    import make_nn_golden_frame11 as mk
+    import make_nn_golden_full as mkf
+    pm, npart, cloud, vis, data, labels = mkf.case_inputs(smpl, omodel, mk.CASE)
+    got = omodel.nn(pm, npart, cloud, vis, data, labels)
+    assert np.array_equal(np.load(mk.PATH)["idx"], got)
+    if orc.have_reference_nn():
+        ref, _ = orc.reference_nn(pm[omodel.main_joint()].astype(np.int32), cloud, vis, data, labels, npart)
+        assert np.array_equal(ref, got)
 
 
 def test_oracle_nn_full_size_against_nanoflann_goldens(smpl, omodel):

@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out
 mkdir -p $O
-COMMON="--no-cpu-baseline --no-throughput-config --no-label-stage --no-render-stage --no-shard --no-dense-config --no-seed-spread --saturation-frames 0 --regions 3"
+COMMON="--full --no-cpu-baseline --no-throughput-config --no-label-stage --no-render-stage --no-shard --no-dense-config --no-seed-spread --saturation-frames 0 --regions 3"
 # configurations: "<frames>[d]" (d = dense 150k-point frames)
 for CFG in ${FRAMES:-1 64 512 1d 16d 64d}; do
   F=${CFG%d}; DENSE=""; TAG=""; [ "$CFG" != "$F" ] && DENSE="--dense" && TAG="_dense"
