@@ -382,6 +382,23 @@ class Context:
     def optimize_resident(self, opt: Options):
         _check(self._lib.avt_optimize_resident(self.h, C.byref(opt)))
 
+    def optimize_resident_budgets(self, opt: Options, budgets):
+        """avt_optimize_resident with a per-frame ICP budget (one int per resident frame, 0 .. opt.icp_iters; 0 = not fitted)."""
+        b = np.ascontiguousarray(np.asarray(budgets, np.int32).reshape(-1))
+        if len(b) != self._F:
+            raise AvtError(f"optimize_resident_budgets: {len(b)} budgets for {self._F} resident frames")
+        _check(self._lib.avt_optimize_resident_budgets(self.h, C.byref(opt), iptr(b)))
+
+    def state_upload_frames(self, frames, p, q, w):
+        """Overwrite the resident state of the listed frames (working and start copies); the other frames keep theirs."""
+        fr = np.ascontiguousarray(np.asarray(frames, np.int32).reshape(-1))
+        n, J, K = len(fr), self.model.numJoints(), self.model.numShapeKeys()
+        p, q, w = (np.asarray(a, np.float64) for a in (p, q, w))
+        if p.size != 3 * n or q.size != 4 * J * n or w.size != K * n:
+            raise AvtError(f"state_upload_frames: want p ({n},3), q ({n},{J},4), w ({n},{K}); got sizes {p.size}, {q.size}, {w.size}")
+        p = np.ascontiguousarray(p.reshape(n, 3)); q = np.ascontiguousarray(q.reshape(n, 4 * J)); w = np.ascontiguousarray(w.reshape(n, K))
+        _check(self._lib.avt_state_upload_frames(self.h, C.c_int(n), iptr(fr), dptr(p), dptr(q), dptr(w)))
+
     def state_reset(self):
         """Asynchronous device-side reinstall of the last uploaded start state (no host transfer, no synchronisation)."""
         _check(self._lib.avt_state_reset(self.h))

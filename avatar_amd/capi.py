@@ -230,6 +230,8 @@ def load_library():
         "avt_frames_download": [vp, C.c_int, c_double_p, c_int_p],
         "avt_state_upload": [vp, C.c_int, c_double_p, c_double_p, c_double_p],
         "avt_optimize_resident": [vp, C.POINTER(Options)],
+        "avt_optimize_resident_budgets": [vp, C.POINTER(Options), c_int_p],
+        "avt_state_upload_frames": [vp, C.c_int, c_int_p, c_double_p, c_double_p, c_double_p],
         "avt_state_reset": [vp],
         "avt_state_download": [vp, c_double_p, c_double_p, c_double_p, C.POINTER(Stats)],
         "avt_get_correspondences": [vp, C.c_int, c_int_p],
@@ -288,6 +290,7 @@ EXPORTED_SYMBOLS = [
     "avt_model_dims", "avt_model_main_joint", "avt_model_joint_regression", "avt_model_tile_layout", "avt_ctx_create", "avt_ctx_destroy",
     "avt_sync", "avt_lbs_update", "avt_visibility", "avt_nn", "avt_optimize", "avt_optimize_posed", "avt_optimize_batch",
     "avt_frames_upload", "avt_synth_render_frames", "avt_synth_render_frames_mode", "avt_synth_render_images", "avt_frames_download", "avt_state_upload", "avt_optimize_resident", "avt_state_reset", "avt_state_download",
+    "avt_optimize_resident_budgets", "avt_state_upload_frames",
     "avt_get_correspondences", "avt_get_cloud", "avt_get_posed", "avt_get_normal_equations", "avt_ctx_get_tuning", "avt_ctx_set_tuning", "avt_set_data_term", "avt_get_data_term", "avt_debug_trace", "avt_debug_mfma_count", "avt_launch_shape", "avt_profile_begin", "avt_profile_select", "avt_profile_end",
     # include/avt_shard.h
     "avt_shard_owner", "avt_shard_local_count", "avt_shard_local_index", "avt_shard_global_frame", "avt_model_pack_size", "avt_model_pack",

@@ -173,8 +173,9 @@ int check_launch(const char* what) {
     return 0;
 }
 
-// the launch sequence of one optimize() over the resident frames
-void enqueue_optimize(avt_ctx* c, const avt_options* o, int f0, int nf, hipStream_t stream) {
+// the launch sequence of one optimize() over the resident frames.  budget (avt_optimize_resident_budgets; nullptr for every other call):
+// the per-frame ICP budgets in device memory - the frames whose budget ends early are held where it ends and put back at the end
+void enqueue_optimize(avt_ctx* c, const avt_options* o, int f0, int nf, hipStream_t stream, const int* budget = nullptr) {
     c->fb.f0 = f0;
     c->fb.max_iters = o->max_iters_per_icp;
     c->cur_stream = stream;
@@ -191,11 +192,14 @@ void enqueue_optimize(avt_ctx* c, const avt_options* o, int f0, int nf, hipStrea
     // workgroup's 90 KB of LDS for EVERY workgroup of the skinning, one per CU, and at 32 frames per launch that costs more than the INIT launch
     // saves: 0.980 -> 0.990 ms.  The row form's batches need k_solve INIT's deal of the evaluation ranges.)
     const bool fuse_init = (c->fb.G >= 64 || (c->fb.use_moments && nf <= 16)) && avt_lbs_can_init(c->dm.d);
+    const bool hold = budget && o->icp_iters > 0;
+    if (hold) launch_budget_hold(c, nf, budget, c->budget_hold, 0, false, 1);      // budget 0: the state the call found ...
     if (!fuse_bucket) { ProfScope ps(c, AVT_K_BUCKET); launch_bucket(c, nf, true); }
     // frame batches: k_compact gathers its candidates from the cloud, so k_lbs does not write the part-sorted copy of it
     const bool few = avt_nn_few(c, nf);
     c->nn_from_cloud = !few;
     { ProfScope ps(c, AVT_K_LBS); launch_lbs(c, nf, nullptr, nullptr, nullptr, nullptr, 1, vis_init, fuse_bucket, fuse_init && o->icp_iters > 0, false, few); }   // ava.update() precondition (:1356)
+    if (hold) launch_budget_hold(c, nf, budget, c->budget_hold, 0, false, 2);      // ... and its skinning
     for (int icp = 0; icp < o->icp_iters; ++icp) {
         { ProfScope ps(c, AVT_K_VISIBILITY); launch_visibility(c, nf, o->enable_occlusion, fuse_bucket && icp == 0); }
         { ProfScope ps(c, AVT_K_NN); launch_nn(c, nf); }
@@ -216,6 +220,7 @@ void enqueue_optimize(avt_ctx* c, const avt_options* o, int f0, int nf, hipStrea
             { ProfScope ps(c, AVT_K_LBS); const bool more = icp + 1 < o->icp_iters;
               launch_lbs(c, nf, nullptr, nullptr, nullptr, nullptr, 2, more ? vis_init : -1, false, fuse_init && more, false, few && more, !more); }      // (the last launch of the call also writes the result records)
             c->ran_icp_iters++;
+            if (hold) launch_budget_hold(c, nf, budget, c->budget_hold, c->ran_icp_iters, c->ran_icp_iters == o->icp_iters);
             continue;
         }
         { ProfScope ps(c, AVT_K_AGGREGATE); launch_finalize(c, nf); launch_records(c, nf); }
@@ -237,6 +242,8 @@ void enqueue_optimize(avt_ctx* c, const avt_options* o, int f0, int nf, hipStrea
         { ProfScope ps(c, AVT_K_LBS); const bool more = icp + 1 < o->icp_iters;      // the last launch of the call skins only: no bookkeeping reset, no part-sorted copy
           launch_lbs(c, nf, nullptr, nullptr, nullptr, nullptr, 2, more ? vis_init : -1, false, fuse_init && more, o->max_iters_per_icp > 0, few && more, !more); }   // :1494-1497 (2: from the skeleton tables of the current point)
         c->ran_icp_iters++;
+        // budget b: held behind the closing launch of ICP iteration b - 1; behind the call's closing launch, the held frames are put back
+        if (hold) launch_budget_hold(c, nf, budget, c->budget_hold, c->ran_icp_iters, c->ran_icp_iters == o->icp_iters);
     }
     c->lbs_cleared = false;
     c->nn_from_cloud = false;
@@ -275,7 +282,8 @@ void note_products(avt_ctx* c, const avt_options* o) {
     c->results_fresh = o->icp_iters > 0;      // the closing k_lbs launch of the call wrote fb.results (no ICP iteration: no closing launch)
 }
 
-int run_optimize(avt_ctx* c, const avt_options* o) {
+// what run_optimize checks before anything changes on the device
+int check_optimize(const avt_ctx* c, const avt_options* o) {
     const int nf = c->nframes;
     if (nf <= 0 || !c->frames_valid) { avt_set_error("avt_optimize: no frames resident (upload frames first; the stand-alone entry points avt_nn / avt_visibility / avt_lbs_update invalidate them)"); return 1; }
     if (!c->state_valid) { avt_set_error("avt_optimize: no start state resident for these frames (avt_state_upload)"); return 1; }
@@ -283,6 +291,13 @@ int run_optimize(avt_ctx* c, const avt_options* o) {
     if (o->lm_policy != 0 && o->lm_policy != 1) { avt_set_error("avt_optimize: lm_policy must be 0 (fixed factors) or 1 (gain ratio)"); return 1; }
     if (!(o->lm_up > 1.0) || !(o->lm_down > 0.0 && o->lm_down < 1.0)) { avt_set_error("avt_optimize: lm_up must be > 1 and lm_down in (0, 1)"); return 1; }
     if (!(o->function_tolerance >= 0.0 && o->function_tolerance < 1.0)) { avt_set_error("avt_optimize: function_tolerance must be in [0, 1) (0 = no early exit)"); return 1; }
+    return 0;
+}
+
+// budget: see enqueue_optimize (nullptr: a plain call, whose launch sequence and graphs do not know about budgets)
+int run_optimize(avt_ctx* c, const avt_options* o, const int* budget = nullptr) {
+    const int nf = c->nframes;
+    if (check_optimize(c, o)) return 1;
     if (sync_params(c, o)) return 1;
     c->ran_max_iters = o->max_iters_per_icp;
     // Large batches run as several frame groups: the latency-bound single-workgroup-per-frame kernels of one group
@@ -298,7 +313,7 @@ int run_optimize(avt_ctx* c, const avt_options* o) {
     if (!c->tun.use_graph || c->profiling) {
         for (int gi = 0; gi < ngroups; ++gi) {
             const int f0 = gi * nfg, n = std::min(nfg, nf - f0);
-            if (n > 0) enqueue_optimize(c, o, f0, n, c->stream);
+            if (n > 0) enqueue_optimize(c, o, f0, n, c->stream, budget);
         }
         c->ran_icp_iters = o->icp_iters;
         note_products(c, o);
@@ -311,7 +326,8 @@ int run_optimize(avt_ctx* c, const avt_options* o) {
     // only enqueue, so the lock is held for microseconds.
     std::lock_guard<std::mutex> graph_lock(g_graph_mutex);
     char key[160];
-    snprintf(key, sizeof key, "%d|%d|%d|%d|%d|%d|%d|%d", nf, ngroups, c->fb.G, c->launch_maxN, o->icp_iters, o->max_iters_per_icp, o->enable_occlusion, c->fb.use_moments);
+    snprintf(key, sizeof key, "%d|%d|%d|%d|%d|%d|%d|%d%s", nf, ngroups, c->fb.G, c->launch_maxN, o->icp_iters, o->max_iters_per_icp, o->enable_occlusion, c->fb.use_moments,
+             budget ? "|budgets" : "");      // (the budgets themselves live in device memory: a changing pattern replays the same graph)
     avt_ctx::GraphEntry* hit = nullptr;
     for (auto& e : c->graphs) if (e.key == key) { hit = &e; break; }
     if (!hit) {
@@ -325,14 +341,14 @@ int run_optimize(avt_ctx* c, const avt_options* o) {
             for (int gi = 1; gi < ngroups; ++gi) cap(hipStreamWaitEvent(c->side[gi - 1], c->ev_fork, 0));
             for (int gi = 0; gi < ngroups; ++gi) {
                 const int f0 = gi * nfg, n = std::min(nfg, nf - f0);
-                if (n > 0) enqueue_optimize(c, o, f0, n, gi == 0 ? c->stream : c->side[gi - 1]);
+                if (n > 0) enqueue_optimize(c, o, f0, n, gi == 0 ? c->stream : c->side[gi - 1], budget);
             }
             for (int gi = 1; gi < ngroups; ++gi) {
                 cap(hipEventRecord(c->ev_join[gi - 1], c->side[gi - 1]));
                 cap(hipStreamWaitEvent(c->stream, c->ev_join[gi - 1], 0));
             }
         } else {
-            enqueue_optimize(c, o, 0, nf, c->stream);
+            enqueue_optimize(c, o, 0, nf, c->stream, budget);
         }
         cap(hipGetLastError());
         // the capture is ALWAYS ended, so that a failure does not leave the stream stuck in capture mode
@@ -1018,6 +1034,68 @@ int avt_optimize_resident(avt_ctx* c, const avt_options* opt) {
     if (rc) c->results_fresh = false;      //  a call that failed left no result records
     return rc;
     AVT_API_GUARD_END("avt_optimize_resident")
+}
+
+int avt_optimize_resident_budgets(avt_ctx* c, const avt_options* opt, const int* icp_budget) {
+    AVT_API_GUARD_BEGIN
+    if (!c || !opt || !icp_budget) { avt_set_error("avt_optimize_resident_budgets: null argument"); return 1; }
+    HIP_OK(hipSetDevice(c->device));
+    if (check_optimize(c, opt)) return 1;
+    const int nf = c->nframes;
+    for (int f = 0; f < nf; ++f)
+        if (icp_budget[f] < 0 || icp_budget[f] > opt->icp_iters) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "avt_optimize_resident_budgets: frame %d has budget %d, outside [0, icp_iters = %d]", f, icp_budget[f], opt->icp_iters);
+            avt_set_error(msg);
+            return 1;
+        }
+    if (!c->budget_hold && dev_alloc(c, &c->budget_hold, (size_t)c->fb.max_frames * avt_budget_hold_doubles(c->dm.d))) return 1;
+    if (!c->budget) {
+        if (dev_alloc(c, &c->budget, (size_t)c->fb.max_frames)) return 1;
+        c->budget_host.clear();
+    }
+    if (c->budget_host.size() < (size_t)nf || !std::equal(icp_budget, icp_budget + nf, c->budget_host.begin())) {
+        for (int f0 = 0; f0 < nf; f0 += AVT_BUDGET_CHUNK) {
+            AvtBudgetChunk a;
+            a.f0 = f0;
+            a.n = std::min(AVT_BUDGET_CHUNK, nf - f0);
+            std::copy(icp_budget + f0, icp_budget + f0 + a.n, a.b);
+            launch_budget_set(c, c->budget, a);
+        }
+        if (check_launch("k_budget_set")) { c->budget_host.clear(); return 1; }
+        c->budget_host.assign(icp_budget, icp_budget + nf);
+    }
+    const int rc = run_optimize(c, opt, c->budget);
+    c->results_fresh = false;      // the result records of the closing launch describe the frames before the held ones were put back
+    return rc;
+    AVT_API_GUARD_END("avt_optimize_resident_budgets")
+}
+
+int avt_state_upload_frames(avt_ctx* c, int count, const int* frames, const double* p, const double* q, const double* w) {
+    AVT_API_GUARD_BEGIN
+    if (!c || !frames || !p || !q || !w) { avt_set_error("avt_state_upload_frames: null argument"); return 1; }
+    if (!c->frames_valid || !c->state_valid || c->nframes <= 0) { avt_set_error("avt_state_upload_frames: no resident state to update (avt_state_upload first)"); return 1; }
+    const int nf = c->nframes;
+    if (count <= 0 || count > nf) { avt_set_error("avt_state_upload_frames: count out of range"); return 1; }
+    std::vector<char> seen(nf, 0);
+    for (int i = 0; i < count; ++i) {
+        if (frames[i] < 0 || frames[i] >= nf) { avt_set_error("avt_state_upload_frames: frame id out of range"); return 1; }
+        if (seen[frames[i]]++) { avt_set_error("avt_state_upload_frames: a frame id is repeated"); return 1; }
+    }
+    HIP_OK(hipSetDevice(c->device));
+    const AvtDims& d = c->dm.d;
+    for (int i = 0; i < count; ++i) {
+        AvtStateInstall a;
+        a.frame = frames[i];
+        a.N = c->frame_N[frames[i]];
+        std::copy(p + 3 * i, p + 3 * i + 3, a.x);
+        std::copy(q + (size_t)4 * d.J * i, q + (size_t)4 * d.J * (i + 1), a.x + 3);
+        std::copy(w + (size_t)d.K * i, w + (size_t)d.K * (i + 1), a.x + 3 + 4 * d.J);
+        launch_state_install(c, a);
+    }
+    c->results_fresh = false;
+    return check_launch("k_state_install");
+    AVT_API_GUARD_END("avt_state_upload_frames")
 }
 
 int avt_state_reset(avt_ctx* c) {

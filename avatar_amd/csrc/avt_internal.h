@@ -373,6 +373,10 @@ struct avt_ctx {
     unsigned long long* render_mkey; float* render_depth; float* render_fkey; int* render_frank; unsigned char* render_fedge;
     size_t render_cap_paint_pix; size_t render_cap_paint_face;
     int render_img_frames, render_img_w, render_img_h;   // what render_depth / render_label hold (avt_synth_render_images); 0 = nothing
+    // avt_optimize_resident_budgets, allocated on its first call: the budget word of every frame, one hold block per frame
+    // (avt_budget_hold_doubles), and what budget[] was last set to (a repeated pattern is not uploaded again)
+    int* budget; double* budget_hold;
+    std::vector<int> budget_host;
 };
 
 void avt_set_error(const std::string& s);
@@ -399,6 +403,15 @@ void launch_reduce(avt_ctx* c, int nframes);
 bool avt_solve_rides(const avt_ctx* c, int nframes);      // the reduction rides in k_solve's launch: no launch_reduce in front of launch_solve
 void launch_solve(avt_ctx* c, int nframes, int mode, int seq = 0 /* which solve of the ICP iteration (riding shape) */);
 void launch_pack_results(avt_ctx* c, int nframes, double* out, int stride);
+// per-frame ICP budgets (avt_optimize_resident_budgets) and per-frame state installs (avt_state_upload_frames)
+#define AVT_BUDGET_CHUNK 248
+struct AvtBudgetChunk { int f0, n; int b[AVT_BUDGET_CHUNK]; };        // a kernel argument (1 KB)
+#define AVT_MAX_XSIZE (3 + 4 * AVT_MAX_JOINTS + AVT_MAX_SHAPE)
+struct AvtStateInstall { int frame, N; double x[AVT_MAX_XSIZE]; };    // a kernel argument (2.2 KB)
+size_t avt_budget_hold_doubles(const AvtDims& d);                     // doubles of one frame's hold block
+void launch_budget_hold(avt_ctx* c, int nframes, const int* budget, double* hold, int at /* ICP iterations done */, bool restore, int part = 0);
+void launch_budget_set(avt_ctx* c, int* dst, const AvtBudgetChunk& a);
+void launch_state_install(avt_ctx* c, const AvtStateInstall& a);
 // avt_moments.hip
 void launch_moments(avt_ctx* c, int nframes);             // once per ICP iteration, behind k_finalize (carries the cost-constant workgroups)
 void launch_assemble(avt_ctx* c, int nframes);            // normal equations of the trial point from the moments (+ the pose-prior workgroups)

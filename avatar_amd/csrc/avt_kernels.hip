@@ -506,6 +506,87 @@ void launch_state_reset(avt_ctx* c, int nframes) {
     hipLaunchKernelGGL(k_state_reset, dim3((std::max(nx, nctl) + 255) / 256), dim3(256), 0, c->stream, c->fb, nx, nctl, nframes);
 }
 
+// =================================================================================================
+// Per-frame ICP budgets (avt_optimize_resident_budgets).  Every frame of the call runs all opt->icp_iters ICP iterations with the
+// same launches as a plain call; what a frame with budget b < icp_iters must be left with - its state as the closing launch of
+// ICP iteration b - 1 left it (budget 0: as the call found it) - is copied aside at that point and copied back once the call's
+// closing launch has run.  Both launches read the budget word of the frame from device memory, so that the captured sequence does
+// not depend on the budgets.  A hold block per frame: the control block, both state slots, and what avt_get_posed reads.
+// grid (ceil(hold / 2048), frames of the group), block 256.
+// =================================================================================================
+static_assert(sizeof(AvtFrameCtl) % sizeof(double) == 0, "the hold block copies the control block as doubles");
+
+size_t avt_budget_hold_doubles(const AvtDims& d) {
+    return sizeof(AvtFrameCtl) / sizeof(double) + 2 * (size_t)d.xsize + 3 * (size_t)d.V + 15 * (size_t)d.J;
+}
+
+__global__ __launch_bounds__(256) void k_budget_hold(FrameBuffers fb, const int* __restrict__ budget, double* __restrict__ hold, int at,
+                                                     int restore, int xsize, int V, int J, int stride, int lo, int hi) {
+    const int f = blockIdx.y + fb.f0;
+    const int b = budget[f];
+    if (restore ? !(b < at) : b != at) return;      // restore: every frame whose budget ends before the call's last ICP iteration
+    const int nctl = (int)(sizeof(AvtFrameCtl) / sizeof(double)), nx = 2 * xsize, nc = 3 * V, njp = 3 * J;
+    double* h = hold + (size_t)f * stride;
+    double* ctl = (double*)(fb.ctl + f);
+    double* x = fb.x + (size_t)f * nx;
+    double* cloud = fb.cloud + (size_t)f * nc;
+    double* jp = fb.jointpos + (size_t)f * njp;
+    double* jt = fb.jointtrans + (size_t)f * 12 * J;
+    for (int e = lo + blockIdx.x * 2048 + threadIdx.x; e < min(hi, lo + (int)(blockIdx.x + 1) * 2048); e += 256) {
+        int k = e;
+        double* live;
+        if (k < nctl) live = ctl + k;
+        else if ((k -= nctl) < nx) live = x + k;
+        else if ((k -= nx) < nc) live = cloud + k;
+        else if ((k -= nc) < njp) live = jp + k;
+        else live = jt + (k - njp);
+        if (restore) *live = h[e];
+        else h[e] = *live;
+    }
+}
+
+// part: 0 the whole hold block, 1 the control block and the state slots only, 2 the posed outputs only (budget 0 holds the state in
+// front of the call's first launch and the skinning of it that launch makes behind it, as a call with icp_iters = 0 leaves them)
+void launch_budget_hold(avt_ctx* c, int nframes, const int* budget, double* hold, int at, bool restore, int part) {
+    const AvtDims& d = c->dm.d;
+    const int stride = (int)avt_budget_hold_doubles(d), mid = (int)(sizeof(AvtFrameCtl) / sizeof(double)) + 2 * d.xsize;
+    const int lo = part == 2 ? mid : 0, hi = part == 1 ? mid : stride;
+    hipLaunchKernelGGL(k_budget_hold, dim3((hi - lo + 2047) / 2048, nframes), dim3(256), 0, c->cur_stream, c->fb, budget, hold, at,
+                       restore ? 1 : 0, d.xsize, d.V, d.J, stride, lo, hi);
+}
+
+// the budget words of frames [f0, f0 + n), n <= AVT_BUDGET_CHUNK, carried by the launch's arguments (nothing in host memory has to
+// outlive the call; stream-ordered in front of the optimize() that reads them)
+__global__ __launch_bounds__(256) void k_budget_set(int* __restrict__ dst, AvtBudgetChunk a) {
+    const int t = threadIdx.x;
+    if (t < a.n) dst[a.f0 + t] = a.b[t];
+}
+
+void launch_budget_set(avt_ctx* c, int* dst, const AvtBudgetChunk& a) {
+    hipLaunchKernelGGL(k_budget_set, dim3(1), dim3(256), 0, c->stream, dst, a);
+}
+
+// avt_state_upload_frames: one frame's start state into both the working and the start copy (as upload_state writes them:
+// the state in slot 0, slot 1 zero, a cleared control block with the frame's point count)
+__global__ __launch_bounds__(256) void k_state_install(FrameBuffers fb, AvtStateInstall a, int xsize) {
+    const int t = threadIdx.x, f = a.frame;
+    for (int e = t; e < 2 * xsize; e += 256) {
+        const double v = e < xsize ? a.x[e] : 0.0;
+        fb.x[(size_t)f * 2 * xsize + e] = v;
+        fb.x_start[(size_t)f * 2 * xsize + e] = v;
+    }
+    const int nctl = (int)(sizeof(AvtFrameCtl) / sizeof(int));
+    if (t < nctl) {
+        const int v = t == (int)(offsetof(AvtFrameCtl, N) / sizeof(int)) ? a.N : (t == (int)(offsetof(AvtFrameCtl, comp_cur) / sizeof(int)) ? -1 : 0);
+        ((int*)(fb.ctl + f))[t] = v;
+        ((int*)(fb.ctl_start + f))[t] = v;
+    }
+}
+
+void launch_state_install(avt_ctx* c, const AvtStateInstall& a) {
+    hipLaunchKernelGGL(k_state_install, dim3(1), dim3(256), 0, c->stream, c->fb, a, c->dm.d.xsize);
+}
+
 void launch_bucket(avt_ctx* c, int nframes, bool clear_after) {
     const int maxN = c->launch_maxN;
     const int nb = std::max(1, (maxN + BUCKET_TILE - 1) / BUCKET_TILE);

@@ -13,6 +13,49 @@ import numpy as np
 from . import api
 
 
+def subsample(xyz, part_mask, bbox, interval, num_parts):
+    """Every `interval`-th pixel of the bounding box (top, left, bottom, right; inclusive; None = the whole image) that carries a
+    body-part label (demo.cpp:216-250); y is negated (:245).  Returns (data_cloud (n,3) float64, labels (n,) int32)."""
+    H, W = part_mask.shape
+    top, left, bottom, right = bbox if bbox is not None else (0, 0, H - 1, W - 1)
+    rows = np.arange(top, bottom + 1, interval)
+    cols = np.arange(left, right + 1, interval)
+    sub_mask = part_mask[np.ix_(rows, cols)]
+    keep = sub_mask != 255
+    if (sub_mask[keep] >= num_parts).any():
+        raise ValueError("body part prediction out of range (demo.cpp:236-243)")
+    pts = xyz[np.ix_(rows, cols)][keep].astype(np.float64)
+    pts[:, 1] = -pts[:, 1]
+    return pts, sub_mask[keep].astype(np.int32)
+
+
+def frame_decision(tr, labels, num_parts):
+    """The per-frame policy of one stream (demo.cpp:225-265, live-demo.cpp:376-418) on the subsampled labels: returns
+    (fit, ICP iterations, reinitialise); fit False means tracking is lost (nothing is fitted, the next fitted frame reinitialises).
+    `tr` carries the stream's policy and state under FrameTracker's attribute names; reinit / firstTime are updated."""
+    part_missing = False                          # live-demo.cpp:376-380: the first fit wants every body part seen
+    if tr.firstTime and tr.initialPerPartCnz > 0:
+        part_cnz = np.bincount(labels, minlength=num_parts)
+        part_missing = part_cnz.min() < max(1, tr.initialPerPartCnz // (tr.interval * tr.interval))
+    if len(labels) == 0 or part_missing or len(labels) < tr.reinitCnz // (tr.interval * tr.interval):   # an empty frame is never fitted
+        tr.reinit = True
+        return False, 0, False
+    if not tr.reinit:
+        return True, tr.frameICPIters, False
+    icp_iters = tr.initialICPIters if tr.firstTime else tr.reinitICPIters     # live-demo.cpp:417-418
+    tr.reinit = False
+    tr.firstTime = False
+    return True, icp_iters, True
+
+
+def reinit_state(data, num_joints, num_shape_keys):
+    """The start state of a (re)initialisation (demo.cpp:252-265): the data centroid, zero shape, identity joints and the root
+    turned by AngleAxis(pi, y).  Returns (p (3,), r (J,3,3), w (K,))."""
+    r = np.tile(np.eye(3), (num_joints, 1, 1))
+    r[0] = np.array([[-1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, -1.0]])   # AngleAxis(pi, y)
+    return data.mean(0), r, np.zeros(num_shape_keys)
+
+
 class FrameTracker:
     def __init__(self, ava_opt: "api.AvatarOptimizer", interval=12, frame_icp_iters=3, reinit_icp_iters=6, reinit_cnz=1000,
                  num_threads=4, rtree=None, rtree_interval=2, dist_to_pre_weight=0.001, initial_per_part_cnz=0, initial_icp_iters=None):
@@ -35,40 +78,19 @@ class FrameTracker:
     def subsample(self, xyz, part_mask, bbox=None):
         """Every `interval`-th pixel of the bounding box that carries a body-part label (demo.cpp:216-250);
         y is negated (:245).  Returns (data_cloud (n,3) float64, labels (n,) int32)."""
-        H, W = part_mask.shape
-        top, left, bottom, right = bbox if bbox is not None else (0, 0, H - 1, W - 1)
-        rows = np.arange(top, bottom + 1, self.interval)
-        cols = np.arange(left, right + 1, self.interval)
-        sub_mask = part_mask[np.ix_(rows, cols)]
-        keep = sub_mask != 255
-        if (sub_mask[keep] >= self.opt.numParts).any():
-            raise ValueError("body part prediction out of range (demo.cpp:236-243)")
-        pts = xyz[np.ix_(rows, cols)][keep].astype(np.float64)
-        pts[:, 1] = -pts[:, 1]
-        return pts, sub_mask[keep].astype(np.int32)
+        return subsample(xyz, part_mask, bbox, self.interval, self.opt.numParts)
 
     def process(self, xyz, part_mask, bbox=None):
         """One tracked frame.  Returns True if the avatar was fitted, False if tracking was declared lost
         (too few body pixels: the next frame reinitialises, demo.cpp:225,283-285)."""
         data, labels = self.subsample(xyz, part_mask, bbox)
-        part_missing = False                          # live-demo.cpp:376-380: the first fit wants every body part seen
-        if self.firstTime and self.initialPerPartCnz > 0:
-            part_cnz = np.bincount(labels, minlength=self.opt.numParts)
-            part_missing = part_cnz.min() < max(1, self.initialPerPartCnz // (self.interval * self.interval))
-        if len(labels) == 0 or part_missing or len(labels) < self.reinitCnz // (self.interval * self.interval):   # an empty frame is never fitted
-            self.reinit = True
+        fit, icp_iters, reinit = frame_decision(self, labels, self.opt.numParts)
+        if not fit:
             return False
-        icp_iters = self.frameICPIters
         ava = self.ava
-        if self.reinit:                               # demo.cpp:252-265
-            ava.p = data.mean(0)
-            ava.w = np.zeros_like(ava.w)
-            ava.r = np.tile(np.eye(3), (ava.model.numJoints(), 1, 1))
-            ava.r[0] = np.array([[-1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, -1.0]])   # AngleAxis(pi, y)
-            self.reinit = False
+        if reinit:                                    # demo.cpp:252-265
+            ava.p, ava.r, ava.w = reinit_state(data, ava.model.numJoints(), len(ava.w))
             ava.update()
-            icp_iters = self.initialICPIters if self.firstTime else self.reinitICPIters     # live-demo.cpp:417-418
-            self.firstTime = False
         self.opt.optimize(data, labels, icp_iters, self.num_threads)
         return True
 
@@ -86,3 +108,107 @@ class FrameTracker:
     def process_depth(self, xyz, bbox):
         """One tracked frame from depth alone: label() then process()."""
         return self.process(xyz, self.label(xyz, bbox), bbox)
+
+
+class _Stream:
+    """Policy and state of one stream of a MultiFrameTracker, under FrameTracker's attribute names (frame_decision reads them)."""
+
+    def __init__(self, interval, frame_icp_iters, reinit_icp_iters, reinit_cnz, initial_per_part_cnz, initial_icp_iters):
+        self.interval = interval
+        self.frameICPIters = frame_icp_iters
+        self.reinitICPIters = reinit_icp_iters
+        self.reinitCnz = reinit_cnz
+        self.initialPerPartCnz = initial_per_part_cnz
+        self.initialICPIters = reinit_icp_iters if initial_icp_iters is None else initial_icp_iters
+        self.firstTime = True
+        self.reinit = True
+        self.framesFitted = 0
+
+
+class MultiFrameTracker:
+    """S independent FrameTracker streams fitted together: one batched fit per step over one resident frame per stream.
+
+    Every stream has exactly FrameTracker's policy and state (`streams[s]`: reinit, firstTime, interval, the three ICP budgets,
+    reinitCnz, initialPerPartCnz).  A step subsamples every stream's frame on the host, makes the S frames resident (the warm
+    states stay resident), installs the start state of the streams that reinitialise (avt_state_upload_frames; the first step
+    installs all S with avt_state_upload), fits every stream with its own ICP budget in ONE call (avt_optimize_resident_budgets;
+    a lost stream has budget 0 and keeps its state) and downloads all states once.  Posed clouds are fetched on request (posed()).
+
+    `ctx` is an api.Context with room for S frames of `max_points` points (create() makes one)."""
+
+    def __init__(self, ctx, num_streams, interval=12, frame_icp_iters=3, reinit_icp_iters=6, reinit_cnz=1000, initial_per_part_cnz=0,
+                 initial_icp_iters=None, beta_pose=0.1, beta_shape=1.0, max_iters_per_icp=10, enable_occlusion=True,
+                 function_tolerance=1e-4):
+        self.ctx = ctx
+        self.S = int(num_streams)
+        self.numParts = ctx.num_parts
+        self.J, self.K = ctx.model.numJoints(), ctx.model.numShapeKeys()
+        self.streams = [_Stream(interval, frame_icp_iters, reinit_icp_iters, reinit_cnz, initial_per_part_cnz, initial_icp_iters)
+                        for _ in range(self.S)]
+        self.betaPose, self.betaShape = beta_pose, beta_shape
+        self.maxItersPerICP, self.enableOcclusion, self.functionTolerance = max_iters_per_icp, enable_occlusion, function_tolerance
+        self.p = np.zeros((self.S, 3))
+        self.q = np.zeros((self.S, self.J, 4)); self.q[:, :, 3] = 1.0
+        self.w = np.zeros((self.S, self.K))
+        self.stats = [None] * self.S                  # avt_stats of every stream's last fit
+        self.state_resident = False
+        self.last_budgets = None                      # the budget vector of the last step (0 = not fitted)
+        self.last_reinit = []                         # the streams re-installed by the last step
+
+    @classmethod
+    def create(cls, model: "api.AvatarModel", num_streams, num_parts=None, part_map=None, max_points=200000, device=None, **kw):
+        J = model.numJoints()
+        pm = np.arange(J, dtype=np.int32) if part_map is None else np.asarray(part_map, np.int32)
+        ctx = api.Context(model, J if num_parts is None else num_parts, pm, max_points, num_streams, device)
+        return cls(ctx, num_streams, **kw)
+
+    def options(self, icp_iters):
+        o = api.Options.reference_defaults()
+        o.beta_pose, o.beta_shape = self.betaPose, self.betaShape
+        o.max_iters_per_icp, o.enable_occlusion, o.icp_iters = self.maxItersPerICP, int(self.enableOcclusion), icp_iters
+        o.function_tolerance = self.functionTolerance
+        return o
+
+    def process(self, frames):
+        """One step: `frames` holds one (xyz (H,W,3), part mask (H,W) uint8, bbox or None) per stream.  Returns the list of
+        per-stream fitted flags (False: tracking lost, the stream's next fitted frame reinitialises)."""
+        if len(frames) != self.S:
+            raise ValueError(f"MultiFrameTracker.process: {len(frames)} frames for {self.S} streams")
+        datas, labels, budgets, reinit, fitted = [], [], np.zeros(self.S, np.int32), [], []
+        for s, (xyz, mask, bbox) in enumerate(frames):
+            d, l = subsample(xyz, mask, bbox, self.streams[s].interval, self.numParts)
+            fit, icp_iters, re = frame_decision(self.streams[s], l, self.numParts)
+            fitted.append(fit)
+            if not fit:                               # nothing of a lost stream's frame is needed: it rides as an empty frame
+                d, l = d[:0], l[:0]
+            budgets[s] = icp_iters if fit else 0
+            if re:
+                reinit.append(s)
+                p, r, w = reinit_state(d, self.J, self.K)
+                self.p[s], self.q[s], self.w[s] = p, api.rot_to_quat(r), w
+            datas.append(d); labels.append(l)
+        self.last_budgets, self.last_reinit = budgets.copy(), list(reinit)
+        if not any(fitted):
+            return fitted
+        ctx = self.ctx
+        ctx.frames_upload(datas, labels)
+        if not self.state_resident:
+            ctx.state_upload(self.p, self.q, self.w)
+            self.state_resident = True
+        elif reinit:
+            ctx.state_upload_frames(reinit, self.p[reinit], self.q[reinit], self.w[reinit])
+        ctx.optimize_resident_budgets(self.options(int(budgets.max())), budgets)
+        p, q, w, st = ctx.state_download()
+        for s in range(self.S):
+            if fitted[s]:
+                self.p[s], self.q[s], self.w[s], self.stats[s] = p[s], q[s], w[s], st[s]
+                self.streams[s].framesFitted += 1
+        return fitted
+
+    def posed(self, stream):
+        """(cloud (V,3), jointPos (J,3), jointTrans (J,12)) of the stream's last fit (one download; avt_get_posed)."""
+        return self.ctx.posed(stream)
+
+    def rotations(self, stream):
+        """The stream's joint rotations (J,3,3), as FrameTracker's Avatar.r holds them."""
+        return api.quat_to_rot(self.q[stream])

@@ -1,0 +1,147 @@
+// ark/MultiFrameTracker.h — S independent tracking streams (each the protocol of ark::FrameTracker) fitted together: one batched
+// fit per step over one resident frame per stream, every stream with its own ICP budget (avt_optimize_resident_budgets).
+// Header-only, over the C ABI, with a device context of its own sized for S frames.
+//
+// A step: subsample every stream's frame on the host; avt_frames_upload of the S frames (the same count keeps the warm states
+// resident; a lost stream rides as an empty frame); avt_state_upload_frames for the streams that reinitialise (the first step
+// installs all S with avt_state_upload); avt_optimize_resident_budgets with icp_iters = the largest budget of the step; one
+// avt_state_download.  Per-stream p, r, w and stats are always there; posed clouds are fetched on request (posed()).
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <vector>
+
+#include "AvatarOptimizer.h"
+#include "TrackerPolicy.h"
+
+namespace ark {
+
+class MultiFrameTracker {
+   public:
+    using Rect = TrackRect;
+    /** policy and state of one stream: FrameTracker's members of the same names */
+    struct Stream {
+        int interval = 12, frameICPIters = 3, reinitICPIters = 6, initialICPIters = 6, reinitCnz = 1000, initialPerPartCnz = 0;
+        bool reinit = true, firstTime = true;
+        long framesFitted = 0;
+    };
+    /** one stream's input of a step: XYZ map (height x width x 3 float), part mask (uint8, 255 = background), box */
+    struct Frame { const float* xyz; const std::uint8_t* mask; int width, height; Rect box; };
+
+    MultiFrameTracker(const AvatarModel& model, int num_streams, int num_parts, const std::vector<int>& part_map, int max_points_per_frame,
+                      int device = 0)
+        : model(model), S(num_streams), numParts(num_parts), J(model.numJoints()), K(model.numShapeKeys()), streams((size_t)num_streams),
+          p(3 * (size_t)num_streams, 0.0), q(4 * (size_t)J * num_streams, 0.0), w((size_t)K * num_streams, 0.0),
+          stats((size_t)num_streams), clouds((size_t)num_streams), labels((size_t)num_streams), cnz((size_t)num_streams) {
+        for (int s = 0; s < S; ++s) for (int j = 0; j < J; ++j) q[((size_t)s * J + j) * 4 + 3] = 1.0;
+        ARK_AVT_CHECK(avt_ctx_create(device, model.handle, num_parts, part_map.data(), max_points_per_frame, num_streams, &ctx));
+    }
+    ~MultiFrameTracker() { if (ctx) avt_ctx_destroy(ctx); }
+    MultiFrameTracker(const MultiFrameTracker&) = delete;
+    MultiFrameTracker& operator=(const MultiFrameTracker&) = delete;
+
+    /** One step, one frame per stream.  fitted[s] = 1 if stream s was fitted, 0 if its tracking was declared lost. */
+    void process(const std::vector<Frame>& frames, std::vector<int>& fitted) {
+        if ((int)frames.size() != S) { std::fprintf(stderr, "MultiFrameTracker: %d frames for %d streams\n", (int)frames.size(), S); std::exit(1); }
+        fitted.assign((size_t)S, 0);
+        budgets.assign((size_t)S, 0);
+        reinitStreams.clear();
+        std::vector<Matrix3d> r((size_t)J);
+        std::vector<double> wz((size_t)K, 0.0);
+        for (int s = 0; s < S; ++s) {
+            Stream& st = streams[(size_t)s];
+            cnz[(size_t)s] = subsampleFrame(frames[(size_t)s].xyz, frames[(size_t)s].mask, frames[(size_t)s].width, frames[(size_t)s].box, st.interval,
+                                            numParts, clouds[(size_t)s], labels[(size_t)s]);
+            int icp = 0;
+            bool re = false;
+            if (!frameDecision(st, labels[(size_t)s], cnz[(size_t)s], numParts, icp, re)) {
+                cnz[(size_t)s] = 0;                    // nothing of a lost stream's frame is needed: it rides as an empty frame
+                continue;
+            }
+            fitted[(size_t)s] = 1;
+            budgets[(size_t)s] = icp;
+            if (re) {
+                reinitStreams.push_back(s);
+                reinitState(clouds[(size_t)s], cnz[(size_t)s], &p[3 * (size_t)s], wz, r);
+                std::copy(wz.begin(), wz.end(), w.begin() + (size_t)K * s);
+                for (int j = 0; j < J; ++j) {
+                    const Quaterniond qq = rotationToQuaternion(r[(size_t)j]);
+                    for (int c = 0; c < 4; ++c) q[((size_t)s * J + j) * 4 + c] = qq.c[c];
+                }
+            }
+        }
+        if (std::find(fitted.begin(), fitted.end(), 1) == fitted.end()) return;
+        // the frames back to back
+        std::vector<int> offs((size_t)S + 1, 0);
+        for (int s = 0; s < S; ++s) offs[(size_t)s + 1] = offs[(size_t)s] + (int)cnz[(size_t)s];
+        data.resize(3 * (size_t)offs[(size_t)S]);
+        lab.resize((size_t)offs[(size_t)S]);
+        for (int s = 0; s < S; ++s) {
+            std::copy(clouds[(size_t)s].data(), clouds[(size_t)s].data() + 3 * cnz[(size_t)s], data.begin() + 3 * (size_t)offs[(size_t)s]);
+            std::copy(labels[(size_t)s].begin(), labels[(size_t)s].begin() + (long)cnz[(size_t)s], lab.begin() + offs[(size_t)s]);
+        }
+        ARK_AVT_CHECK(avt_frames_upload(ctx, S, data.data(), lab.data(), offs.data()));
+        if (!stateResident) {
+            ARK_AVT_CHECK(avt_state_upload(ctx, S, p.data(), q.data(), w.data()));
+            stateResident = true;
+        } else if (!reinitStreams.empty()) {
+            const size_t n = reinitStreams.size();
+            std::vector<double> pp(3 * n), qq(4 * (size_t)J * n), ww((size_t)K * n);
+            for (size_t i = 0; i < n; ++i) {
+                const size_t s = (size_t)reinitStreams[i];
+                std::copy(&p[3 * s], &p[3 * s] + 3, &pp[3 * i]);
+                std::copy(&q[4 * (size_t)J * s], &q[4 * (size_t)J * s] + 4 * J, &qq[4 * (size_t)J * i]);
+                std::copy(&w[(size_t)K * s], &w[(size_t)K * s] + K, &ww[(size_t)K * i]);
+            }
+            ARK_AVT_CHECK(avt_state_upload_frames(ctx, (int)n, reinitStreams.data(), pp.data(), qq.data(), ww.data()));
+        }
+        avt_options o;
+        avt_options_default(&o);
+        o.beta_pose = betaPose; o.beta_shape = betaShape; o.max_iters_per_icp = maxItersPerICP;
+        o.enable_occlusion = enableOcclusion ? 1 : 0; o.function_tolerance = functionTolerance;
+        o.icp_iters = *std::max_element(budgets.begin(), budgets.end());
+        ARK_AVT_CHECK(avt_optimize_resident_budgets(ctx, &o, budgets.data()));
+        std::vector<avt_stats> st((size_t)S);
+        ARK_AVT_CHECK(avt_state_download(ctx, p.data(), q.data(), w.data(), st.data()));
+        for (int s = 0; s < S; ++s)
+            if (fitted[(size_t)s]) { stats[(size_t)s] = st[(size_t)s]; ++streams[(size_t)s].framesFitted; }
+    }
+
+    /** ava.cloud (3 x V), jointPos (3 x J), jointTrans (12 x J) of stream s's last fit; any pointer may be null (avt_get_posed) */
+    void posed(int s, double* cloud_3xV, double* joint_pos_3xJ = nullptr, double* joint_trans_12xJ = nullptr) {
+        ARK_AVT_CHECK(avt_get_posed(ctx, s, cloud_3xV, joint_pos_3xJ, joint_trans_12xJ));
+    }
+    const double* pos(int s) const { return &p[3 * (size_t)s]; }
+    const double* shape(int s) const { return &w[(size_t)K * s]; }
+    const double* quats(int s) const { return &q[4 * (size_t)J * s]; }           // J quaternions (x, y, z, w)
+    Matrix3d rotation(int s, int j) const {
+        Quaterniond qq;
+        for (int c = 0; c < 4; ++c) qq.c[c] = q[((size_t)s * J + j) * 4 + c];
+        return quaternionToRotation(qq);
+    }
+
+    const AvatarModel& model;
+    const int S, numParts, J, K;
+    std::vector<Stream> streams;
+    double betaPose = 0.1, betaShape = 1.0, functionTolerance = 1e-4;
+    int maxItersPerICP = 10;
+    bool enableOcclusion = true;
+    std::vector<int> budgets, reinitStreams;       // of the last step (0 = not fitted)
+
+   private:
+    std::vector<double> p, q, w;
+
+   public:
+    std::vector<avt_stats> stats;                  // avt_stats of every stream's last fit
+
+   private:
+    avt_ctx* ctx = nullptr;
+    bool stateResident = false;
+    std::vector<CloudType> clouds;
+    std::vector<VectorXi> labels;
+    std::vector<size_t> cnz;
+    std::vector<double> data;
+    std::vector<int> lab;
+};
+
+}  // namespace ark

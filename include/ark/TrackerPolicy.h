@@ -1,0 +1,93 @@
+// ark/TrackerPolicy.h — the per-frame protocol pieces of the reference's trackers (demo.cpp:215-290, live-demo.cpp:376-418) that
+// ark::FrameTracker and ark::MultiFrameTracker share: interval subsampling of a labelled XYZ map, the tracking-loss /
+// reinitialisation decision of one stream, and the start state of a reinitialisation.  Header-only, no OpenCV.
+#pragma once
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+#include "Avatar.h"
+
+namespace ark {
+
+struct TrackRect { int top = 0, left = 0, bottom = 0, right = 0; };   // inclusive, like bgsub.topLeft / botRight
+
+/** Every `interval`-th pixel of the box that carries a body-part label (demo.cpp:216-250); y negated (:245).  Returns the number
+ *  of points; a label >= numParts is fatal exactly like demo.cpp:236-243. */
+inline size_t subsampleFrame(const float* xyz, const std::uint8_t* part_mask, int width, const TrackRect& box, int interval, int numParts,
+                             CloudType& dataCloud, VectorXi& dataPartLabels) {
+    size_t cnz = 0;
+    for (int r = box.top; r <= box.bottom; r += interval) {
+        const std::uint8_t* partptr = part_mask + (size_t)r * width;
+        for (int c = box.left; c <= box.right; c += interval) cnz += partptr[c] != 255;
+    }
+    dataCloud.resize(3, cnz);
+    dataPartLabels.assign(cnz, 0);
+    size_t i = 0;
+    for (int r = box.top; r <= box.bottom; r += interval) {
+        const float* ptr = xyz + (size_t)r * width * 3;
+        const std::uint8_t* partptr = part_mask + (size_t)r * width;
+        for (int c = box.left; c <= box.right; c += interval) {
+            if (partptr[c] == 255) continue;
+            if (partptr[c] >= numParts) {
+                std::fprintf(stderr, "FATAL: body part prediction %d is invalid, since there are only %d body parts\n", (int)partptr[c], numParts);
+                std::exit(1);
+            }
+            dataCloud(0, i) = ptr[3 * c];
+            dataCloud(1, i) = -ptr[3 * c + 1];
+            dataCloud(2, i) = ptr[3 * c + 2];
+            dataPartLabels[i] = partptr[c];
+            ++i;
+        }
+    }
+    return cnz;
+}
+
+/** The decision of one stream on its subsampled frame.  `T` carries the stream's policy and state under FrameTracker's member names
+ *  (interval, frameICPIters, reinitICPIters, initialICPIters, reinitCnz, initialPerPartCnz, reinit, firstTime); reinit / firstTime
+ *  are updated.  Returns false when tracking is lost (nothing is fitted; the next fitted frame reinitialises: live-demo.cpp:335-340,
+ *  :379-383 - demo.cpp:225 only skips the frame, the documented deviation FrameTracker keeps); else sets the ICP iterations and
+ *  whether the stream reinitialises (demo.cpp:252-265, live-demo.cpp:417-418). */
+template <class T>
+bool frameDecision(T& tr, const VectorXi& labels, size_t cnz, int numParts, int& icpIters, bool& reinitNow) {
+    // An EMPTY frame is never fitted whatever reinitCnz says: the reinitialisation centroid divides by cnz.
+    bool part_missing = false;       // live-demo.cpp:376-380: the FIRST fit wants every body part seen (initialPerPartCnz pixels at interval 1)
+    if (tr.firstTime && tr.initialPerPartCnz > 0) {
+        std::vector<size_t> partCnz((size_t)numParts, 0);
+        for (size_t i = 0; i < cnz; ++i) ++partCnz[(size_t)labels[i]];
+        size_t mn = partCnz.empty() ? 0 : partCnz[0];
+        for (size_t v : partCnz) mn = v < mn ? v : mn;
+        const int need = tr.initialPerPartCnz / (tr.interval * tr.interval);
+        part_missing = mn < (size_t)(need > 1 ? need : 1);
+    }
+    reinitNow = false;
+    icpIters = 0;
+    if (cnz == 0 || part_missing || cnz < (size_t)(tr.reinitCnz / (tr.interval * tr.interval))) {
+        tr.reinit = true;
+        return false;
+    }
+    icpIters = tr.frameICPIters;
+    if (tr.reinit) {
+        icpIters = tr.firstTime ? tr.initialICPIters : tr.reinitICPIters;
+        tr.reinit = false;
+        tr.firstTime = false;
+        reinitNow = true;
+    }
+    return true;
+}
+
+/** Start state of a reinitialisation (demo.cpp:252-265): p = centroid of the data, w = 0, identity joints, root AngleAxis(pi, y). */
+inline void reinitState(const CloudType& dataCloud, size_t cnz, double p[3], std::vector<double>& w, std::vector<Matrix3d>& r) {
+    double cen[3] = {0, 0, 0};
+    for (size_t i = 0; i < cnz; ++i) for (int c = 0; c < 3; ++c) cen[c] += dataCloud(c, i);
+    for (int c = 0; c < 3; ++c) p[c] = cen[c] / (double)cnz;
+    w.assign(w.size(), 0.0);
+    for (size_t i = 1; i < r.size(); ++i) r[i].setIdentity();
+    // AngleAxis(pi, (0, 1, 0)).toRotationMatrix(): written out (cos(pi) and sin(pi) leave rounding residue)
+    Matrix3d r0;
+    r0(0, 0) = -1.0; r0(2, 2) = -1.0;
+    r[0] = r0;
+}
+
+}  // namespace ark

@@ -198,6 +198,18 @@ int avt_optimize_resident(avt_ctx* c, const avt_options* opt);
  * enqueues avt_state_reset + avt_optimize_resident without any host-to-device transfer or host synchronisation. */
 int avt_state_reset(avt_ctx* c);
 int avt_state_download(avt_ctx* c, double* p, double* q, double* w, avt_stats* stats);
+/* avt_optimize_resident with a per-frame ICP budget: frame f runs ICP iterations 0 .. icp_budget[f]-1 of the
+ * opt->icp_iters the call runs and is left exactly as that point left it; 0 = not fitted (state untouched).
+ * 0 <= icp_budget[f] <= opt->icp_iters for every resident frame, else the call fails before anything changes.  A frame with budget b
+ * ends with p, q, w, every avt_stats field and what avt_get_posed returns (the skinning of that state; for b = 0 of the start state) as
+ * a call with icp_iters = b leaves them on the same resident frames (bit for bit: same launch shape).  The budgets are uploaded on the context's stream and are not part of the launch shape: a
+ * changing budget pattern replays the same captured graph.  avt_get_correspondences / avt_get_normal_equations describe the last ICP
+ * iteration the call ran.  Every frame runs all opt->icp_iters iterations on the device (those past its budget are discarded). */
+int avt_optimize_resident_budgets(avt_ctx* c, const avt_options* opt, const int* icp_budget /* nframes */);
+/* overwrite the resident state (working and start copies) of `count` frames; the other frames keep theirs.  Needs a resident state of
+ * the resident frame count (avt_state_upload); rejects out-of-range or repeated frame ids.  p: 3 x count, q: 4J x count, w: K x count,
+ * in the order of `frames`.  Asynchronous on the context's stream (the host arrays may be reused when the call returns). */
+int avt_state_upload_frames(avt_ctx* c, int count, const int* frames, const double* p, const double* q, const double* w);
 
 /* ---- synthetic-frame generator on the GPU: AvatarRenderer::renderDepth / renderPartMask
  * (AvatarRenderer.cpp:72-101, :174-202) of `nframes` posed avatars + back-projection (Calibration.cpp:68-74, y negated as
