@@ -1,0 +1,539 @@
+// avt_bgsub.hip — background subtraction on gfx950 (include/avt_bgsub.h): BGSubtractor::run (BGSubtractor.cpp:10-163)
+// as a near-background test plus a union-find connected-component labelling whose roots are the smallest raster index
+// of every component, so the partition, the roots and hence the ids are the reference's whatever the scheduling.
+//
+// Launch sequence per run (every kernel batched over the images on a grid dimension):
+//   k_bgs_local    32x32 tile per 256-thread workgroup: the 3x3 near-background test against an LDS copy of the
+//                  background tile and its one-pixel halo (:30-76), then union-find over the tile's 4-neighbour edges
+//                  with LDS atomicMin (the tile's XYZ in LDS); writes the tile-local root (a global index) per pixel
+//                  (-1: not a candidate) and zeroes the size counter of every local root
+//   k_bgs_border   one lane per edge across a tile border: lock-free union in global memory, larger root under smaller
+//   k_bgs_flatten  every pixel to its root; component sizes counted with one atomic per (wave, root), not per pixel
+//   k_bgs_compact  kept roots (size >= min_pts, :114) into a per-image list
+//   k_bgs_ids      one workgroup per image sorts the list by index: the rank is the id (:95-123), the 254th kept root
+//                  caps the run (:124)
+//   k_bgs_mask     the mask byte, the foreground box by per-wave min / max and integer atomics (:128-151)
+//   k_bgs_depth    the demos' use of the mask (demo.cpp:183-192, live-demo.cpp:317-332): depth zeroed inside the box
+//                  where the mask is >= 254, pixels < 254 inside the box counted
+// Every retry loop is bounded; a bound that runs out sets the handle's sticky fault word (AVT_STATUS_DEVICE_FAULT).
+// Float arithmetic is the reference's, operation by operation: this file is built with -ffp-contract=off.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cstddef>
+#include <exception>
+#include <string>
+#include <vector>
+
+#include "avt_internal.h"
+#include "../../include/avt_bgsub.h"
+
+#define BGS_TILE 32
+#define BGS_HALO (BGS_TILE + 2)
+#define BGS_LIST_CAP 1024      // kept components per image: each has >= max(N/1000, 100) pixels, so at most 1009 of them
+#define BGS_FAULT_LOCAL 1u     // LDS union ran out of its bound
+#define BGS_FAULT_GLOBAL 2u    // global union / find ran out of its bound
+#define BGS_FAULT_LIST 4u      // more kept roots than BGS_LIST_CAP (cannot happen with the bound above)
+
+struct BgsInfo {               // per image, device resident
+    int box[4];                // tl.x tl.y br.x br.y: in the previous box, out this run's (kept when capped)
+    int acc[4];                // min col, min row, -max col, -max row of non-255 pixels (atomicMin)
+    int n_kept, capped, cap_root, fg_count, n_comps, pad[3];
+    int comps[AVT_BGSUB_MAX_COMPS][2];
+    int list[BGS_LIST_CAP];
+};
+
+struct avt_bgsub {
+    int device = 0, n_bg = 0, rows = 0, cols = 0;
+    hipStream_t stream = nullptr;
+    float* d_bg = nullptr;                 // n_bg x N x 3
+    float* d_img = nullptr;                // cap x N x 3
+    int* d_bgidx = nullptr;                // cap
+    int* d_label = nullptr;                // cap x N: parent / root index, -1 not a candidate
+    int* d_count = nullptr;                // cap x N: size at a root; after k_bgs_ids -1 - code at a kept root
+    unsigned char* d_mask = nullptr;       // cap x N
+    float* d_depth = nullptr;              // cap x N
+    BgsInfo* d_info = nullptr;             // cap
+    unsigned* d_fault = nullptr;           // sticky fault word of the handle
+    int cap = 0, n_images = 0;
+};
+
+namespace {
+
+#define BG_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { avt_set_error(std::string(#x) + ": " + hipGetErrorString(e_)); return 1; } } while (0)
+
+__device__ __forceinline__ float sqdist(float a0, float a1, float a2, float b0, float b1, float b2) {
+    const float d0 = a0 - b0, d1 = a1 - b1, d2 = a2 - b2;
+    return (d0 * d0 + d1 * d1) + d2 * d2;        // BGSubtractor.cpp:47 / :86, left to right, no contraction
+}
+
+__device__ __forceinline__ int ld_rel(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ int ld_wg(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+
+// parents always point to a smaller index, so a chain is strictly decreasing; the bounds only guard against a broken invariant
+__device__ int find_lds(const int* L, int x, bool& ok) {
+    for (int i = 0; i < BGS_TILE * BGS_TILE; ++i) {
+        const int y = ld_wg(&L[x]);
+        if (y == x) return x;
+        x = y;
+    }
+    ok = false;
+    return x;
+}
+
+__device__ void union_lds(int* L, int a, int b, bool& ok) {
+    for (int it = 0; it < 4 * BGS_TILE * BGS_TILE; ++it) {
+        a = find_lds(L, a, ok); b = find_lds(L, b, ok);
+        if (a == b) return;
+        if (a < b) { const int t = a; a = b; b = t; }
+        const int old = atomicMin(&L[a], b);     // link the larger root under the smaller
+        if (old == a) return;
+        a = old;                                 // a was linked meanwhile: join its new parent with b
+    }
+    ok = false;
+}
+
+__device__ int find_g(const int* L, int x, int npix, bool& ok) {
+    for (int i = 0; i < npix; ++i) {
+        const int y = ld_rel(&L[x]);
+        if (y == x) return x;
+        x = y;
+    }
+    ok = false;
+    return x;
+}
+
+__device__ void union_g(int* L, int a, int b, int npix, bool& ok) {
+    for (int it = 0; it < (1 << 20); ++it) {
+        a = find_g(L, a, npix, ok); b = find_g(L, b, npix, ok);
+        if (!ok || a == b) return;
+        if (a < b) { const int t = a; a = b; b = t; }
+        const int old = atomicMin(&L[a], b);
+        if (old == a) return;
+        a = old;
+    }
+    ok = false;
+}
+
+__global__ __launch_bounds__(256) void k_bgs_local(const float* __restrict__ bgs, const int* __restrict__ bgidx, const float* __restrict__ imgs,
+                                                   int* __restrict__ label, int* __restrict__ count, BgsInfo* __restrict__ info,
+                                                   unsigned* __restrict__ fault, int rows, int cols, float nn_thresh, float neighb_thresh) {
+    __shared__ float s_bg[BGS_HALO * BGS_HALO * 3];
+    __shared__ float s_px[BGS_TILE * BGS_TILE * 3];
+    __shared__ int s_L[BGS_TILE * BGS_TILE];
+    const int img = blockIdx.z, t = threadIdx.x;
+    const size_t npix = (size_t)rows * cols;
+    const float* bg = bgs + (size_t)bgidx[img] * npix * 3;
+    const float* px = imgs + (size_t)img * npix * 3;
+    const int r0 = blockIdx.y * BGS_TILE, c0 = blockIdx.x * BGS_TILE;
+    if (blockIdx.x == 0 && blockIdx.y == 0 && t == 0) {      // per-run state of the image (later kernels of this run use it)
+        BgsInfo& in = info[img];
+        in.acc[0] = INT_MAX; in.acc[1] = INT_MAX; in.acc[2] = INT_MAX; in.acc[3] = INT_MAX;
+        in.n_kept = 0; in.capped = 0; in.cap_root = INT_MAX; in.fg_count = 0; in.n_comps = 0;
+    }
+    // background tile + halo; outside the image z = 0, which the test skips as it skips a zero-depth neighbour: the
+    // window clipped at the border (:33-34)
+    for (int i = t; i < BGS_HALO * BGS_HALO; i += 256) {
+        const int r = r0 + i / BGS_HALO - 1, c = c0 + i % BGS_HALO - 1;
+        float x = 0.f, y = 0.f, z = 0.f;
+        if (r >= 0 && r < rows && c >= 0 && c < cols) {
+            const float* p = bg + ((size_t)r * cols + c) * 3;
+            x = p[0]; y = p[1]; z = p[2];
+        }
+        s_bg[3 * i] = x; s_bg[3 * i + 1] = y; s_bg[3 * i + 2] = z;
+    }
+    for (int i = t; i < BGS_TILE * BGS_TILE; i += 256) {
+        const int r = r0 + (i >> 5), c = c0 + (i & 31);
+        float x = 0.f, y = 0.f, z = 0.f;
+        if (r < rows && c < cols) {
+            const float* p = px + ((size_t)r * cols + c) * 3;
+            x = p[0]; y = p[1]; z = p[2];
+        }
+        s_px[3 * i] = x; s_px[3 * i + 1] = y; s_px[3 * i + 2] = z;
+    }
+    __syncthreads();
+    // near-background test (:56-71): -1 invalid (255), else the pixel's own index (a root of its own)
+    for (int i = t; i < BGS_TILE * BGS_TILE; i += 256) {
+        const int ly = i >> 5, lx = i & 31;
+        int lab = -1;
+        const float x = s_px[3 * i], y = s_px[3 * i + 1], z = s_px[3 * i + 2];
+        if (r0 + ly < rows && c0 + lx < cols && z != 0.f) {
+            lab = i;
+            for (int dy = 0; dy < 3 && lab >= 0; ++dy)
+                for (int dx = 0; dx < 3; ++dx) {
+                    const float* b = &s_bg[3 * ((ly + dy) * BGS_HALO + lx + dx)];
+                    if (b[2] == 0.f) continue;
+                    if (sqdist(b[0], b[1], b[2], x, y, z) < nn_thresh) { lab = -1; break; }
+                }
+        }
+        s_L[i] = lab;
+    }
+    __syncthreads();
+    // edges to the left and upper neighbour inside the tile: joined unless the squared distance is > neighb (:86)
+    bool ok = true;
+    for (int i = t; i < BGS_TILE * BGS_TILE; i += 256) {
+        if (s_L[i] < 0) continue;
+        const int ly = i >> 5, lx = i & 31;
+        const float x = s_px[3 * i], y = s_px[3 * i + 1], z = s_px[3 * i + 2];
+        if (lx > 0 && s_L[i - 1] >= 0 && !(sqdist(x, y, z, s_px[3 * (i - 1)], s_px[3 * (i - 1) + 1], s_px[3 * (i - 1) + 2]) > neighb_thresh))
+            union_lds(s_L, i, i - 1, ok);
+        if (ly > 0 && s_L[i - 32] >= 0 && !(sqdist(x, y, z, s_px[3 * (i - 32)], s_px[3 * (i - 32) + 1], s_px[3 * (i - 32) + 2]) > neighb_thresh))
+            union_lds(s_L, i, i - 32, ok);
+    }
+    __syncthreads();
+    // the local root (smallest tile index = smallest raster index inside the tile) as a global index
+    for (int i = t; i < BGS_TILE * BGS_TILE; i += 256) {
+        const int r = r0 + (i >> 5), c = c0 + (i & 31);
+        if (r >= rows || c >= cols) continue;
+        int g = -1;
+        if (s_L[i] >= 0) {
+            const int root = find_lds(s_L, i, ok);
+            g = (r0 + (root >> 5)) * cols + c0 + (root & 31);
+            if (root == i) count[(size_t)img * npix + g] = 0;     // only local roots can be global roots
+        }
+        label[(size_t)img * npix + (size_t)r * cols + c] = g;
+    }
+    if (!ok) atomicOr(fault, BGS_FAULT_LOCAL);
+}
+
+__global__ __launch_bounds__(256) void k_bgs_border(const float* __restrict__ imgs, int* __restrict__ label, unsigned* __restrict__ fault, int rows,
+                                                    int cols, float neighb_thresh, int nvb, int nhb) {
+    const int img = blockIdx.y;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long nv = (long long)nvb * rows;
+    if (e >= nv + (long long)nhb * cols) return;
+    int p, q;
+    if (e < nv) {                                 // across the vertical border k: (r, 32(k+1) - 1) - (r, 32(k+1))
+        const int k = (int)(e / rows), r = (int)(e % rows), c = BGS_TILE * (k + 1) - 1;
+        p = r * cols + c; q = p + 1;
+    } else {                                      // across the horizontal border k
+        const long long e2 = e - nv;
+        const int k = (int)(e2 / cols), c = (int)(e2 % cols), r = BGS_TILE * (k + 1) - 1;
+        p = r * cols + c; q = p + cols;
+    }
+    const int npix = rows * cols;
+    int* L = label + (size_t)img * npix;
+    if (L[p] < 0 || L[q] < 0) return;
+    const float* a = imgs + ((size_t)img * npix + p) * 3;
+    const float* b = imgs + ((size_t)img * npix + q) * 3;
+    if (sqdist(a[0], a[1], a[2], b[0], b[1], b[2]) > neighb_thresh) return;
+    bool ok = true;
+    union_g(L, p, q, npix, ok);
+    if (!ok) atomicOr(fault, BGS_FAULT_GLOBAL);
+}
+
+__global__ __launch_bounds__(256) void k_bgs_flatten(int* __restrict__ label, int* __restrict__ count, unsigned* __restrict__ fault, int npix) {
+    const int img = blockIdx.y;
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    int* L = label + (size_t)img * npix;
+    int* cnt = count + (size_t)img * npix;
+    int root = -1;
+    bool ok = true;
+    if (p < npix && ld_rel(&L[p]) >= 0) {
+        root = find_g(L, p, npix, ok);
+        __hip_atomic_store(&L[p], root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (!ok) atomicOr(fault, BGS_FAULT_GLOBAL);
+    // one atomic per distinct root of the wave (a wave is 64 consecutive pixels: mostly one root or none)
+    bool live = root >= 0;
+    for (int it = 0; it < 64; ++it) {
+        const unsigned long long m = __ballot(live);
+        if (!m) break;
+        const int leader = __ffsll((long long)m) - 1;
+        const int lr = __shfl(root, leader, 64);
+        const unsigned long long same = __ballot(live && root == lr);
+        if ((int)(threadIdx.x & 63) == leader) atomicAdd(&cnt[lr], __popcll(same));
+        if (live && root == lr) live = false;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_bgs_compact(const int* __restrict__ label, const int* __restrict__ count, BgsInfo* __restrict__ info,
+                                                     unsigned* __restrict__ fault, int npix, int min_pts) {
+    const int img = blockIdx.y;
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= npix) return;
+    const size_t o = (size_t)img * npix + p;
+    if (label[o] != p || count[o] < min_pts) return;
+    const int slot = atomicAdd(&info[img].n_kept, 1);
+    if (slot < BGS_LIST_CAP) info[img].list[slot] = p;
+    else atomicOr(fault, BGS_FAULT_LIST);
+}
+
+__global__ __launch_bounds__(1024) void k_bgs_ids(int* __restrict__ count, BgsInfo* __restrict__ info, int npix) {
+    __shared__ int s[BGS_LIST_CAP];
+    const int img = blockIdx.x, t = threadIdx.x;
+    BgsInfo& in = info[img];
+    const int nk = min(in.n_kept, BGS_LIST_CAP);
+    s[t] = t < nk ? in.list[t] : INT_MAX;
+    __syncthreads();
+    for (int k = 2; k <= BGS_LIST_CAP; k <<= 1)            // bitonic sort, ascending
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            const int o = t ^ j;
+            if (o > t) {
+                const int a = s[t], b = s[o];
+                if (((t & k) == 0) == (a > b)) { s[t] = b; s[o] = a; }
+            }
+            __syncthreads();
+        }
+    int* cnt = count + (size_t)img * npix;
+    if (t < nk) {
+        const int r = s[t], code = min(t, AVT_BGSUB_MAX_COMPS);
+        if (t < AVT_BGSUB_MAX_COMPS) { in.comps[t][0] = cnt[r]; in.comps[t][1] = t; }
+        cnt[r] = -1 - code;
+    }
+    if (t == 0) {
+        in.capped = nk >= AVT_BGSUB_MAX_COMPS;
+        in.cap_root = nk >= AVT_BGSUB_MAX_COMPS ? s[AVT_BGSUB_MAX_COMPS - 1] : INT_MAX;
+        in.n_comps = min(nk, AVT_BGSUB_MAX_COMPS);
+    }
+}
+
+__device__ __forceinline__ int wave_min(int v) {
+    for (int s = 32; s >= 1; s >>= 1) v = min(v, __shfl_xor(v, s, 64));
+    return v;
+}
+
+__global__ __launch_bounds__(256) void k_bgs_mask(const int* __restrict__ label, const int* __restrict__ count, BgsInfo* __restrict__ info,
+                                                  unsigned char* __restrict__ mask, int npix, int cols) {
+    const int img = blockIdx.y;
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    BgsInfo& in = info[img];
+    const int capped = in.capped, cap_root = in.cap_root;
+    int code = 255;
+    if (p < npix) {
+        const size_t o = (size_t)img * npix + p;
+        const int r = label[o];
+        if (r >= 0) {
+            const int v = count[(size_t)img * npix + r];
+            // a kept root carries -1 - its code; a small component is 255, or 254 when the run stopped before reaching it
+            code = v < 0 ? -1 - v : ((capped && r > cap_root) ? 254 : 255);
+        }
+        mask[o] = (unsigned char)code;
+    }
+    if (capped) return;                                     // the box keeps its previous value (:124)
+    const bool fg = code != 255;
+    if (!__ballot(fg)) return;
+    const int r = p / cols, c = p - r * cols;
+    const int a0 = wave_min(fg ? c : INT_MAX), a1 = wave_min(fg ? r : INT_MAX);
+    const int a2 = wave_min(fg ? -c : INT_MAX), a3 = wave_min(fg ? -r : INT_MAX);
+    if ((threadIdx.x & 63) == 0) {
+        atomicMin(&in.acc[0], a0); atomicMin(&in.acc[1], a1); atomicMin(&in.acc[2], a2); atomicMin(&in.acc[3], a3);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_bgs_depth(const float* __restrict__ imgs, const unsigned char* __restrict__ mask, BgsInfo* __restrict__ info,
+                                                   float* __restrict__ depth, int npix, int rows, int cols) {
+    const int img = blockIdx.y;
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    BgsInfo& in = info[img];
+    int tlx, tly, brx, bry;
+    if (in.capped) {
+        tlx = in.box[0]; tly = in.box[1]; brx = in.box[2]; bry = in.box[3];
+    } else if (in.acc[0] == INT_MAX) {                    // no foreground: the loop of :131-151 leaves the initial values
+        tlx = cols - 1; tly = rows - 1; brx = 0; bry = 0;
+    } else {
+        tlx = in.acc[0]; tly = in.acc[1]; brx = -in.acc[2]; bry = -in.acc[3];
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0 && !in.capped) { in.box[0] = tlx; in.box[1] = tly; in.box[2] = brx; in.box[3] = bry; }
+    bool fg = false;
+    if (p < npix) {
+        const size_t o = (size_t)img * npix + p;
+        const int r = p / cols, c = p - r * cols;
+        const bool inside = r >= tly && r <= bry && c >= tlx && c <= brx;
+        const unsigned char m = mask[o];
+        float z = imgs[o * 3 + 2];
+        if (inside && m >= 254) z = 0.f;
+        fg = inside && m < 254;
+        depth[o] = z;
+    }
+    const unsigned long long b = __ballot(fg);
+    if (b && (threadIdx.x & 63) == 0) atomicAdd(&in.fg_count, __popcll(b));
+}
+
+int reserve(avt_bgsub* bg, int n) {
+    if (n <= bg->cap) return 0;
+    BG_HIP(hipStreamSynchronize(bg->stream));
+    const size_t N = (size_t)bg->rows * bg->cols;
+    (void)hipFree(bg->d_img); (void)hipFree(bg->d_bgidx); (void)hipFree(bg->d_label); (void)hipFree(bg->d_count);
+    (void)hipFree(bg->d_mask); (void)hipFree(bg->d_depth); (void)hipFree(bg->d_info);
+    bg->d_img = nullptr; bg->d_bgidx = nullptr; bg->d_label = nullptr; bg->d_count = nullptr; bg->d_mask = nullptr;
+    bg->d_depth = nullptr; bg->d_info = nullptr; bg->cap = 0; bg->n_images = 0;
+    BG_HIP(hipMalloc((void**)&bg->d_img, (size_t)n * N * 3 * sizeof(float)));
+    BG_HIP(hipMalloc((void**)&bg->d_bgidx, (size_t)n * sizeof(int)));
+    BG_HIP(hipMalloc((void**)&bg->d_label, (size_t)n * N * sizeof(int)));
+    BG_HIP(hipMalloc((void**)&bg->d_count, (size_t)n * N * sizeof(int)));
+    BG_HIP(hipMalloc((void**)&bg->d_mask, (size_t)n * N));
+    BG_HIP(hipMalloc((void**)&bg->d_depth, (size_t)n * N * sizeof(float)));
+    BG_HIP(hipMalloc((void**)&bg->d_info, (size_t)n * sizeof(BgsInfo)));
+    BG_HIP(hipMemsetAsync(bg->d_info, 0, (size_t)n * sizeof(BgsInfo), bg->stream));    // previous boxes start at cv::Point()
+    bg->cap = n;
+    return 0;
+}
+
+// the reference's threshold (BGSubtractor.cpp:160-161): int pixel count, double arithmetic, rounded to float by ffill's parameter
+float thresh(int rows, int cols, float rel) { return (float)(1200000.0 / (rows * cols) * (double)rel); }
+
+int check_fault(avt_bgsub* bg) {
+    unsigned f = 0;
+    BG_HIP(hipMemcpyAsync(&f, bg->d_fault, sizeof(unsigned), hipMemcpyDeviceToHost, bg->stream));
+    BG_HIP(hipStreamSynchronize(bg->stream));
+    if (!f) return 0;
+    BG_HIP(hipMemsetAsync(bg->d_fault, 0, sizeof(unsigned), bg->stream));
+    BG_HIP(hipStreamSynchronize(bg->stream));
+    avt_set_error("avt_bgsub: a kernel ran out of a bounded retry (fault word " + std::to_string(f) + "); the result is not valid");
+    return AVT_STATUS_DEVICE_FAULT;
+}
+
+int create_impl(int device, int n_bg, int rows, int cols, const float* backgrounds, avt_bgsub** out) {
+    if (!out || n_bg <= 0 || rows <= 0 || cols <= 0 || cols >= 65536 || (long long)rows * cols >= (1ll << 30)) {
+        avt_set_error("avt_bgsub_create: bad arguments (rows, cols > 0, cols < 65536, n_backgrounds > 0)");
+        return 1;
+    }
+    BG_HIP(hipSetDevice(device));
+    avt_bgsub* bg = new avt_bgsub();
+    bg->device = device; bg->n_bg = n_bg; bg->rows = rows; bg->cols = cols;
+    const size_t bytes = (size_t)n_bg * rows * cols * 3 * sizeof(float);
+    auto fail = [&]() { avt_bgsub_destroy(bg); return 1; };
+    if (hipStreamCreateWithFlags(&bg->stream, hipStreamNonBlocking) != hipSuccess || hipMalloc((void**)&bg->d_bg, bytes) != hipSuccess ||
+        hipMalloc((void**)&bg->d_fault, sizeof(unsigned)) != hipSuccess) {
+        avt_set_error("avt_bgsub_create: device allocation failed");
+        return fail();
+    }
+    hipError_t e = backgrounds ? hipMemcpyAsync(bg->d_bg, backgrounds, bytes, hipMemcpyHostToDevice, bg->stream)
+                               : hipMemsetAsync(bg->d_bg, 0, bytes, bg->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(bg->d_fault, 0, sizeof(unsigned), bg->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(bg->stream);
+    if (e != hipSuccess) { avt_set_error(std::string("avt_bgsub_create: ") + hipGetErrorString(e)); return fail(); }
+    *out = bg;
+    return 0;
+}
+
+int set_background_impl(avt_bgsub* bg, int index, const float* xyz) {
+    if (!bg || !xyz || index < 0 || index >= bg->n_bg) { avt_set_error("avt_bgsub_set_background: bad arguments"); return 1; }
+    BG_HIP(hipSetDevice(bg->device));
+    const size_t n = (size_t)bg->rows * bg->cols * 3;
+    BG_HIP(hipMemcpyAsync(bg->d_bg + (size_t)index * n, xyz, n * sizeof(float), hipMemcpyHostToDevice, bg->stream));
+    BG_HIP(hipStreamSynchronize(bg->stream));
+    return 0;
+}
+
+int upload_impl(avt_bgsub* bg, int n, const float* images, const int* bg_index, const int* prev_boxes) {
+    if (!bg || !images || n <= 0) { avt_set_error("avt_bgsub_images_upload: bad arguments"); return 1; }
+    std::vector<int> idx(n);
+    for (int i = 0; i < n; ++i) {
+        idx[i] = bg_index ? bg_index[i] : i;
+        if (idx[i] < 0 || idx[i] >= bg->n_bg) { avt_set_error("avt_bgsub_images_upload: background index out of range"); return 1; }
+    }
+    BG_HIP(hipSetDevice(bg->device));
+    if (reserve(bg, n)) return 1;
+    const size_t N = (size_t)bg->rows * bg->cols;
+    BG_HIP(hipMemcpyAsync(bg->d_img, images, (size_t)n * N * 3 * sizeof(float), hipMemcpyHostToDevice, bg->stream));
+    BG_HIP(hipMemcpyAsync(bg->d_bgidx, idx.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, bg->stream));
+    if (prev_boxes)
+        for (int i = 0; i < n; ++i) BG_HIP(hipMemcpyAsync(bg->d_info[i].box, prev_boxes + 4 * (size_t)i, 4 * sizeof(int), hipMemcpyHostToDevice, bg->stream));
+    BG_HIP(hipStreamSynchronize(bg->stream));     // idx is on this stack frame
+    bg->n_images = n;
+    return 0;
+}
+
+int run_resident_impl(avt_bgsub* bg, float nn_rel, float neighb_rel) {
+    if (!bg || bg->n_images <= 0) { avt_set_error("avt_bgsub_run_resident: no images resident"); return 1; }
+    BG_HIP(hipSetDevice(bg->device));
+    const int rows = bg->rows, cols = bg->cols, n = bg->n_images, npix = rows * cols;
+    const float nn = thresh(rows, cols, nn_rel), nb = thresh(rows, cols, neighb_rel);
+    const int min_pts = std::max(npix / 1000, 100);                                   // BGSubtractor.cpp:19
+    const int tx = (cols + BGS_TILE - 1) / BGS_TILE, ty = (rows + BGS_TILE - 1) / BGS_TILE;
+    hipLaunchKernelGGL(k_bgs_local, dim3(tx, ty, n), dim3(256), 0, bg->stream, bg->d_bg, bg->d_bgidx, bg->d_img, bg->d_label, bg->d_count, bg->d_info,
+                       bg->d_fault, rows, cols, nn, nb);
+    const long long edges = (long long)(tx - 1) * rows + (long long)(ty - 1) * cols;
+    if (edges > 0)
+        hipLaunchKernelGGL(k_bgs_border, dim3((unsigned)((edges + 255) / 256), n), dim3(256), 0, bg->stream, bg->d_img, bg->d_label, bg->d_fault, rows,
+                           cols, nb, tx - 1, ty - 1);
+    const dim3 g1((npix + 255) / 256, n);
+    hipLaunchKernelGGL(k_bgs_flatten, g1, dim3(256), 0, bg->stream, bg->d_label, bg->d_count, bg->d_fault, npix);
+    hipLaunchKernelGGL(k_bgs_compact, g1, dim3(256), 0, bg->stream, bg->d_label, bg->d_count, bg->d_info, bg->d_fault, npix, min_pts);
+    hipLaunchKernelGGL(k_bgs_ids, dim3(n), dim3(BGS_LIST_CAP), 0, bg->stream, bg->d_count, bg->d_info, npix);
+    hipLaunchKernelGGL(k_bgs_mask, g1, dim3(256), 0, bg->stream, bg->d_label, bg->d_count, bg->d_info, bg->d_mask, npix, cols);
+    hipLaunchKernelGGL(k_bgs_depth, g1, dim3(256), 0, bg->stream, bg->d_img, bg->d_mask, bg->d_info, bg->d_depth, npix, rows, cols);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { avt_set_error(std::string("avt_bgsub_run_resident: launch failed: ") + hipGetErrorString(e)); return 1; }
+    return 0;
+}
+
+int download_impl(avt_bgsub* bg, int image, unsigned char* mask_out, float* depth_out, avt_bgsub_frame* info) {
+    if (!bg || image < 0 || image >= bg->n_images) { avt_set_error("avt_bgsub_download: bad arguments"); return 1; }
+    BG_HIP(hipSetDevice(bg->device));
+    const size_t N = (size_t)bg->rows * bg->cols;
+    if (mask_out) BG_HIP(hipMemcpyAsync(mask_out, bg->d_mask + image * N, N, hipMemcpyDeviceToHost, bg->stream));
+    if (depth_out) BG_HIP(hipMemcpyAsync(depth_out, bg->d_depth + image * N, N * sizeof(float), hipMemcpyDeviceToHost, bg->stream));
+    BgsInfo h;
+    BG_HIP(hipMemcpyAsync(&h, bg->d_info + image, offsetof(BgsInfo, list), hipMemcpyDeviceToHost, bg->stream));
+    if (int rc = check_fault(bg)) return rc;                                          // synchronises the stream
+    if (info) {
+        info->top_left[0] = h.box[0]; info->top_left[1] = h.box[1]; info->bot_right[0] = h.box[2]; info->bot_right[1] = h.box[3];
+        info->capped = h.capped; info->fg_count = h.fg_count; info->n_comps = h.n_comps;
+        std::vector<std::pair<int, int>> v(h.n_comps);
+        for (int i = 0; i < h.n_comps; ++i) v[i] = {h.comps[i][0], h.comps[i][1]};
+        if (!h.capped) std::sort(v.begin(), v.end(), [](const std::pair<int, int>& a, const std::pair<int, int>& b) { return a > b; });  // :153
+        for (int i = 0; i < h.n_comps; ++i) { info->comps[i][0] = v[i].first; info->comps[i][1] = v[i].second; }
+    }
+    return 0;
+}
+
+int run_impl(avt_bgsub* bg, int background_index, const float* xyz, float nn_rel, float neighb_rel, unsigned char* mask_out, float* depth_out,
+             avt_bgsub_frame* info) {
+    if (!bg || !xyz || !mask_out) { avt_set_error("avt_bgsub_run: null argument"); return 1; }
+    int box[4] = {0, 0, 0, 0};
+    if (info) { box[0] = info->top_left[0]; box[1] = info->top_left[1]; box[2] = info->bot_right[0]; box[3] = info->bot_right[1]; }
+    if (upload_impl(bg, 1, xyz, &background_index, box)) return 1;
+    if (run_resident_impl(bg, nn_rel, neighb_rel)) return 1;
+    return download_impl(bg, 0, mask_out, depth_out, info);
+}
+
+}  // namespace
+
+// ---- exported entry points: no C++ exception crosses the C ABI
+#define BG_ENTRY(name, call)                                                                       \
+    try { return call; }                                                                           \
+    catch (const std::exception& e) { avt_set_error(std::string(name ": ") + e.what()); return 1; } \
+    catch (...) { avt_set_error(name ": unknown exception"); return 1; }
+
+extern "C" {
+int avt_bgsub_create(int device, int n_backgrounds, int rows, int cols, const float* backgrounds, avt_bgsub** out) {
+    BG_ENTRY("avt_bgsub_create", create_impl(device, n_backgrounds, rows, cols, backgrounds, out))
+}
+
+void avt_bgsub_destroy(avt_bgsub* bg) {
+    if (!bg) return;
+    if (bg->stream) (void)hipStreamSynchronize(bg->stream);
+    for (void* p : {(void*)bg->d_bg, (void*)bg->d_img, (void*)bg->d_bgidx, (void*)bg->d_label, (void*)bg->d_count, (void*)bg->d_mask,
+                    (void*)bg->d_depth, (void*)bg->d_info, (void*)bg->d_fault})
+        if (p) (void)hipFree(p);
+    if (bg->stream) (void)hipStreamDestroy(bg->stream);
+    delete bg;
+}
+
+int avt_bgsub_set_background(avt_bgsub* bg, int index, const float* xyz) { BG_ENTRY("avt_bgsub_set_background", set_background_impl(bg, index, xyz)) }
+
+int avt_bgsub_run(avt_bgsub* bg, int background_index, const float* xyz, float nn_rel, float neighb_rel, unsigned char* mask_out,
+                  float* masked_depth_out, avt_bgsub_frame* info) {
+    BG_ENTRY("avt_bgsub_run", run_impl(bg, background_index, xyz, nn_rel, neighb_rel, mask_out, masked_depth_out, info))
+}
+
+int avt_bgsub_images_upload(avt_bgsub* bg, int n_images, const float* images, const int* bg_index, const int* prev_boxes) {
+    BG_ENTRY("avt_bgsub_images_upload", upload_impl(bg, n_images, images, bg_index, prev_boxes))
+}
+
+int avt_bgsub_run_resident(avt_bgsub* bg, float nn_rel, float neighb_rel) { BG_ENTRY("avt_bgsub_run_resident", run_resident_impl(bg, nn_rel, neighb_rel)) }
+
+int avt_bgsub_download(avt_bgsub* bg, int image, unsigned char* mask_out, float* masked_depth_out, avt_bgsub_frame* info) {
+    BG_ENTRY("avt_bgsub_download", download_impl(bg, image, mask_out, masked_depth_out, info))
+}
+
+int avt_bgsub_sync(avt_bgsub* bg) {
+    if (!bg) { avt_set_error("avt_bgsub_sync: null handle"); return 1; }
+    try { return check_fault(bg); }
+    catch (...) { avt_set_error("avt_bgsub_sync: unknown exception"); return 1; }
+}
+}  // extern "C"

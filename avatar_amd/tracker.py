@@ -2,7 +2,7 @@
 interval subsampling of the labelled depth image, the reinitialisation policy, per-frame ICP budgets and the temporal
 warm start (the avatar state simply carries over between frames).  SURVEY.md §8 row f3.
 
-Inputs per frame are what the reference's perception front-end produces (out of scope here): an XYZ map (H,W,3)
+Inputs per frame are what the reference's front end produces (bgsub.BGSubtractor, then rtree.RTree): an XYZ map (H,W,3)
 float32 in camera coordinates and a per-pixel body-part mask (H,W) uint8 with 255 = background, plus the foreground
 bounding box (top, left, bottom, right), inclusive.
 """

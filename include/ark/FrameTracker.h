@@ -3,7 +3,7 @@
 // tracking-loss / reinitialisation policy, the per-frame ICP budgets and the temporal warm start (the avatar state simply
 // carries over between frames).  SURVEY.md §8 row f3.  Header-only, no OpenCV: images are plain row-major buffers.
 //
-// Inputs per frame are what the reference's perception front-end produces (out of scope here): an XYZ map (height x width x 3
+// Inputs per frame are what the reference's front end produces (ark::BGSubtractor, then ark::RTree): an XYZ map (height x width x 3
 // float, camera coordinates, cv::Vec3f layout) and a per-pixel body-part mask (height x width uint8, 255 = background), plus
 // the foreground bounding box (bgsub.topLeft / bgsub.botRight, inclusive).
 #pragma once
