@@ -355,18 +355,27 @@ int reserve(avt_bgsub* bg, int n) {
     if (n <= bg->cap) return 0;
     BG_HIP(hipStreamSynchronize(bg->stream));
     const size_t N = (size_t)bg->rows * bg->cols;
+    const int old = bg->d_info ? bg->cap : 0;      // slots whose boxes carry over
     (void)hipFree(bg->d_img); (void)hipFree(bg->d_bgidx); (void)hipFree(bg->d_label); (void)hipFree(bg->d_count);
-    (void)hipFree(bg->d_mask); (void)hipFree(bg->d_depth); (void)hipFree(bg->d_info);
+    (void)hipFree(bg->d_mask); (void)hipFree(bg->d_depth);
     bg->d_img = nullptr; bg->d_bgidx = nullptr; bg->d_label = nullptr; bg->d_count = nullptr; bg->d_mask = nullptr;
-    bg->d_depth = nullptr; bg->d_info = nullptr; bg->cap = 0; bg->n_images = 0;
+    bg->d_depth = nullptr; bg->cap = 0; bg->n_images = 0;
     BG_HIP(hipMalloc((void**)&bg->d_img, (size_t)n * N * 3 * sizeof(float)));
     BG_HIP(hipMalloc((void**)&bg->d_bgidx, (size_t)n * sizeof(int)));
     BG_HIP(hipMalloc((void**)&bg->d_label, (size_t)n * N * sizeof(int)));
     BG_HIP(hipMalloc((void**)&bg->d_count, (size_t)n * N * sizeof(int)));
     BG_HIP(hipMalloc((void**)&bg->d_mask, (size_t)n * N));
     BG_HIP(hipMalloc((void**)&bg->d_depth, (size_t)n * N * sizeof(float)));
-    BG_HIP(hipMalloc((void**)&bg->d_info, (size_t)n * sizeof(BgsInfo)));
-    BG_HIP(hipMemsetAsync(bg->d_info, 0, (size_t)n * sizeof(BgsInfo), bg->stream));    // previous boxes start at cv::Point()
+    // the slots the handle had keep their previous boxes (avt_bgsub.h: a batch without prev_boxes uses them); only the
+    // new slots start at cv::Point()
+    BgsInfo* info = nullptr;
+    BG_HIP(hipMalloc((void**)&info, (size_t)n * sizeof(BgsInfo)));
+    hipError_t e = hipMemsetAsync(info + old, 0, (size_t)(n - old) * sizeof(BgsInfo), bg->stream);
+    if (e == hipSuccess && old) e = hipMemcpyAsync(info, bg->d_info, (size_t)old * sizeof(BgsInfo), hipMemcpyDeviceToDevice, bg->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(bg->stream);                         // before the old array is freed
+    if (e != hipSuccess) { (void)hipFree(info); BG_HIP(e); }
+    (void)hipFree(bg->d_info);
+    bg->d_info = info;
     bg->cap = n;
     return 0;
 }
