@@ -248,6 +248,7 @@ class Context:
         _check(self._lib.avt_ctx_create(C.c_int(device), model.h, C.c_int(num_parts), iptr(pm), C.c_int(max_points),
                                         C.c_int(max_frames), C.byref(self.h)))
         self.max_points, self.max_frames, self.num_parts = max_points, max_frames, num_parts
+        self.device = device
 
     def __del__(self):
         try:

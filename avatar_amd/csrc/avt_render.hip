@@ -1,6 +1,8 @@
 // avt_render.hip — synthetic depth-frame generator on the GPU: depth + body-part render of posed
 // avatars and back-projection into (data_cloud, data_part_labels), written straight into the context's resident frame
 // buffers so that batched benchmarks need no host rasteriser.
+// The second half of the file is ark::AvatarRenderer on the GPU (include/avt_render.h): the same painter's-order fills applied
+// to avatars that are already posed, with the renderer's own buffers.
 //
 // Behavioural counterpart of AvatarRenderer::renderDepth / renderPartMask (AvatarRenderer.cpp:72-101, :174-202), the
 // projection of AvatarRenderer.cpp:11-24, CameraIntrin::to3D (Calibration.cpp:68-74, float arithmetic) and the y flip of
@@ -8,7 +10,13 @@
 // reference's painter's algorithm; the two generators are bit-identical to each other (tests/test_gpu_render.py):
 // this translation unit is built with -ffp-contract=off and uses the same float expressions, and depth ties go to the
 // lowest face index (64-bit atomicMin on (depth bits, face id)) exactly like the host's in-order strict '<' test.
+#include <algorithm>
+#include <exception>
+#include <string>
+#include <vector>
+
 #include "avt_device.h"
+#include "../../include/avt_render.h"
 
 __device__ __forceinline__ void project(const double* p, double fx, double fy, double cx, double cy, float* px, float* py) {
     *px = (float)(p[0] * fx / p[2] + cx);
@@ -188,6 +196,46 @@ __device__ __forceinline__ void face_projection(const DeviceModel& dm, const dou
     for (int k = 0; k < 3; ++k) project(cl + 3 * (size_t)vid[k], fx, fy, cx, cy, &px[k], &py[k]);
 }
 
+// ---- per-face and per-pixel expressions shared by the two painter modes (the generator's AVT_RENDER_PAINTER and the renderer)
+
+// the face's sort key (AvatarRenderer.cpp:62-66) and its normal (b - a) x (c - a) through Eigen 3.3's normalized(): a zero
+// vector is returned unchanged (both painter modes use it)
+__device__ __forceinline__ float face_key_normal(const double* a, const double* b, const double* c, double n[3]) {
+    const double ab0 = b[0] - a[0], ab1 = b[1] - a[1], ab2 = b[2] - a[2], ac0 = c[0] - a[0], ac1 = c[1] - a[1], ac2 = c[2] - a[2];
+    const double n0 = ab1 * ac2 - ab2 * ac1, n1 = ab2 * ac0 - ab0 * ac2, n2 = ab0 * ac1 - ab1 * ac0;
+    const double z = n0 * n0 + n1 * n1 + n2 * n2;
+    if (z > 0.0) { const double s = sqrt(z); n[0] = n0 / s; n[1] = n1 / s; n[2] = n2 / s; }
+    else { n[0] = n0; n[1] = n1; n[2] = n2; }
+    return (float)((a[2] + b[2] + c[2]) / 3.f);
+}
+
+// paintTriangleBary's value at (row i, column j) of the face (AvatarHelpers.cpp:61-139): vertices sorted by y, the first
+// floored and the last ceiled, attribute zv of the face's vertex slots; std::min(std::max(v, 0.f), 255.f) (NaN stays NaN)
+__device__ __forceinline__ float bary_value(const float px[3], const float py[3], const float zv[3], int i, int j) {
+    int s[3];
+    sort3(py, s);
+    const float ax = px[s[0]], ay = floorf(py[s[0]]), bx = px[s[1]], by = py[s[1]], cxx = px[s[2]], cyy = ceilf(py[s[2]]);
+    const float az = zv[s[0]], bz = zv[s[1]], cz = zv[s[2]];
+    const float denom = 1.0f / ((bx - cxx) * (ay - cyy) + (cyy - by) * (ax - cxx));
+    const float w1v = (bx - cxx) * ((float)i - cyy), w2v = (cxx - ax) * ((float)i - cyy);
+    const float w1 = (w1v + (cyy - by) * ((float)j - cxx)) * denom, w2 = (w2v + (ay - cyy) * ((float)j - cxx)) * denom;
+    const float v = w1 * az + w2 * bz + (1.f - w1 - w2) * cz;
+    const float lo = (v < 0.0f) ? 0.0f : v;
+    return (255.0f < lo) ? 255.0f : lo;
+}
+
+// paintPartsTriangleNN's label at (row i, column j) of the face (AvatarHelpers.cpp:153-245): vertices sorted by x, the first
+// floored and the last ceiled, the part of the nearest one by int-truncated squared distances
+__device__ __forceinline__ unsigned char part_label(const float px[3], const float py[3], const int vid[3], const int* vertex_part, int i, int j) {
+    int s[3];
+    sort3(px, s);
+    const float ax = floorf(px[s[0]]), ay = py[s[0]], bx = px[s[1]], by = py[s[1]], cxx = ceilf(px[s[2]]), cyy = py[s[2]];
+    const int dista = cvt_x86((ax - (float)j) * (ax - (float)j) + (ay - (float)i) * (ay - (float)i));
+    const int distb = cvt_x86((bx - (float)j) * (bx - (float)j) + (by - (float)i) * (by - (float)i));
+    const int distc = cvt_x86((cxx - (float)j) * (cxx - (float)j) + (cyy - (float)i) * (cyy - (float)i));
+    return (unsigned char)((dista < distb && dista < distc) ? vertex_part[vid[s[0]]] : (distb < distc ? vertex_part[vid[s[1]]] : vertex_part[vid[s[2]]]));
+}
+
 // sort key (AvatarRenderer.cpp:62-66: doubles summed, divided by 3.f, stored as float) and the edge-on flag
 // (AvatarRenderer.cpp:88-90 with Eigen 3.3's normalized(): a zero vector is returned unchanged, so a degenerate face is edge-on)
 __global__ __launch_bounds__(256) void k_paint_keys(DeviceModel dm, FrameBuffers fb, float* fkey, unsigned char* fedge) {
@@ -198,12 +246,9 @@ __global__ __launch_bounds__(256) void k_paint_keys(DeviceModel dm, FrameBuffers
     const int ia = dm.mesh[face], ib = dm.mesh[(size_t)F + face], ic = dm.mesh[2 * (size_t)F + face];
     const double* cl = fb.cloud + (size_t)f * 3 * V;
     const double* a = cl + 3 * (size_t)ia; const double* b = cl + 3 * (size_t)ib; const double* c = cl + 3 * (size_t)ic;
-    fkey[(size_t)fl * F + face] = (float)((a[2] + b[2] + c[2]) / 3.f);
-    const double ab0 = b[0] - a[0], ab1 = b[1] - a[1], ab2 = b[2] - a[2], ac0 = c[0] - a[0], ac1 = c[1] - a[1], ac2 = c[2] - a[2];
-    const double n0 = ab1 * ac2 - ab2 * ac1, n1 = ab2 * ac0 - ab0 * ac2, n2 = ab0 * ac1 - ab1 * ac0;
-    const double z = n0 * n0 + n1 * n1 + n2 * n2;
-    const double nz = z > 0.0 ? n2 / sqrt(z) : n2;
-    fedge[(size_t)fl * F + face] = fabs(nz) < 0.1 ? 1 : 0;
+    double n[3];
+    fkey[(size_t)fl * F + face] = face_key_normal(a, b, c, n);
+    fedge[(size_t)fl * F + face] = fabs(n[2]) < 0.1 ? 1 : 0;
 }
 
 // position of every face in the painter's order = number of faces painted before it: those with a larger key, and those
@@ -324,17 +369,10 @@ __global__ __launch_bounds__(256) void k_paint_resolve(DeviceModel dm, FrameBuff
         if (kd != 0ull) {
             const int face = (int)(kd & 0xFFFFFFFFull);
             if (!fedge[(size_t)fl * F + face]) {
-                float px[3], py[3]; int vid[3], s[3];
+                float px[3], py[3]; int vid[3];
                 face_projection(dm, cl, face, fx, fy, cx, cy, px, py, vid);
-                sort3(py, s);
-                const float ax = px[s[0]], ay = floorf(py[s[0]]), bx = px[s[1]], by = py[s[1]], cxx = px[s[2]], cyy = ceilf(py[s[2]]);
-                const float az = (float)cl[3 * (size_t)vid[s[0]] + 2], bz = (float)cl[3 * (size_t)vid[s[1]] + 2], cz = (float)cl[3 * (size_t)vid[s[2]] + 2];
-                const float denom = 1.0f / ((bx - cxx) * (ay - cyy) + (cyy - by) * (ax - cxx));
-                const float w1v = (bx - cxx) * ((float)i - cyy), w2v = (cxx - ax) * ((float)i - cyy);
-                const float w1 = (w1v + (cyy - by) * ((float)j - cxx)) * denom, w2 = (w2v + (ay - cyy) * ((float)j - cxx)) * denom;
-                const float v = w1 * az + w2 * bz + (1.f - w1 - w2) * cz;
-                const float lo = (v < 0.0f) ? 0.0f : v;                // std::max(v, 0.0f): NaN stays NaN
-                depth = (255.0f < lo) ? 255.0f : lo;                   // std::min(., maxz = 255)
+                const float zv[3] = {(float)cl[3 * (size_t)vid[0] + 2], (float)cl[3 * (size_t)vid[1] + 2], (float)cl[3 * (size_t)vid[2] + 2]};
+                depth = bary_value(px, py, zv, i, j);
             }
         }
         unsigned char lab = 255;
@@ -342,14 +380,9 @@ __global__ __launch_bounds__(256) void k_paint_resolve(DeviceModel dm, FrameBuff
         if (km != 0ull) {
             const int face = (int)(km & 0xFFFFFFFFull);
             if (!fedge[(size_t)fl * F + face]) {
-                float px[3], py[3]; int vid[3], s[3];
+                float px[3], py[3]; int vid[3];
                 face_projection(dm, cl, face, fx, fy, cx, cy, px, py, vid);
-                sort3(px, s);
-                const float ax = floorf(px[s[0]]), ay = py[s[0]], bx = px[s[1]], by = py[s[1]], cxx = ceilf(px[s[2]]), cyy = py[s[2]];
-                const int dista = cvt_x86((ax - (float)j) * (ax - (float)j) + (ay - (float)i) * (ay - (float)i));
-                const int distb = cvt_x86((bx - (float)j) * (bx - (float)j) + (by - (float)i) * (by - (float)i));
-                const int distc = cvt_x86((cxx - (float)j) * (cxx - (float)j) + (cyy - (float)i) * (cyy - (float)i));
-                lab = (unsigned char)((dista < distb && dista < distc) ? vertex_part[vid[s[0]]] : (distb < distc ? vertex_part[vid[s[1]]] : vertex_part[vid[s[2]]]));
+                lab = part_label(px, py, vid, vertex_part, i, j);
             }
         }
         depth_img[(size_t)fl * npix + o] = depth;
@@ -403,3 +436,539 @@ int avt_render_enqueue(avt_ctx* c, int nframes, const int* d_vertex_part, unsign
                        (float)cy, width, height);
     return hipGetLastError() != hipSuccess;
 }
+
+// =====================================================================================================================
+// ark::AvatarRenderer on the GPU (include/avt_render.h): the painter's-order machinery above applied to avatars that are
+// already posed, with the reference's four outputs (AvatarRenderer.cpp:11-224).  The handle owns its clouds, its key
+// images and its outputs, so nothing here writes to a context.  Launch sequence of a run, every kernel batched over the
+// images on a grid dimension:
+//   k_rend_project  projected vertices and joints (float pairs, what getProjectedPoints / getProjectedJoints return)
+//   k_rend_faces    per face: the mean-depth key, the edge-on flag of renderDepth / renderPartMask (|n_z| < 0.1), the
+//                   normalized face normal and the visibility flag of renderLambert (|n_z| > 1e-2)
+//   k_rend_sort     one workgroup per image sorts its (key, face id) pairs in LDS: painter position <-> face
+//                   (or k_paint_rank + k_rend_scatter, the O(F^2) count; same positions)
+//   k_rend_vnormal  per vertex: the normals of its incident faces summed in painter order, divided by their norm (no zero
+//                   guard), turned to face the camera; the Lambert value of the two lights
+//   k_rend_cover    per face: its coverage marked in the selected key images with atomicMax(position + 1) (a position is
+//                   unique, so the key needs no face id); renderFaces' image is the key image itself (atomicMax(position)
+//                   over -1)
+//   k_rend_resolve  per pixel: what the winning face painted, with the reference's float expression order
+// =====================================================================================================================
+
+namespace {
+
+constexpr int REND_SORT_CAP = 16384;           // faces one workgroup sorts in LDS (128 KiB of (key, id) pairs)
+
+__global__ __launch_bounds__(256) void k_rend_project(const double* __restrict__ cloud, const double* __restrict__ joints, float2* proj,
+                                                      float2* jproj, int V, int J, double fx, double fy, double cx, double cy) {
+    const int img = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    float x, y;
+    if (i < V) {
+        project(cloud + ((size_t)img * V + i) * 3, fx, fy, cx, cy, &x, &y);
+        proj[(size_t)img * V + i] = make_float2(x, y);
+    }
+    if (i < J) {
+        project(joints + ((size_t)img * J + i) * 3, fx, fy, cx, cy, &x, &y);
+        jproj[(size_t)img * J + i] = make_float2(x, y);
+    }
+}
+
+// fflag bit 0: edge-on for renderDepth / renderPartMask (fabs(n_z) < 0.1); bit 1: visible for renderLambert
+// (fabs(n_z) > 1e-2: AvatarRenderer.cpp:131's abs() read as the double overload)
+__global__ __launch_bounds__(256) void k_rend_faces(const double* __restrict__ cloud, const int* __restrict__ mesh, int V, int F, float* fkey,
+                                                    unsigned char* fflag, double* fnorm) {
+    const int img = blockIdx.y, face = blockIdx.x * 256 + threadIdx.x;
+    if (face >= F) return;
+    const double* cl = cloud + (size_t)img * 3 * V;
+    const double* a = cl + 3 * (size_t)mesh[face];
+    const double* b = cl + 3 * (size_t)mesh[(size_t)F + face];
+    const double* c = cl + 3 * (size_t)mesh[2 * (size_t)F + face];
+    double n[3];
+    const size_t o = (size_t)img * F + face;
+    fkey[o] = face_key_normal(a, b, c, n);
+    fflag[o] = (fabs(n[2]) < 0.1 ? 1 : 0) | (fabs(n[2]) > 1e-2 ? 2 : 0);
+    fnorm[3 * o] = n[0]; fnorm[3 * o + 1] = n[1]; fnorm[3 * o + 2] = n[2];
+}
+
+// painter order of one image: (key, face id) pairs sorted in LDS, decreasing key, ties by ascending face id.  The pair is one
+// 64-bit word whose ascending order is that order: the high half is the key's bits mapped so that unsigned order is
+// decreasing float order (-0 folded onto +0, which compare equal), the low half the face id.  Bitonic sort over the next power
+// of two (padding all ones sorts last).
+__global__ __launch_bounds__(1024) void k_rend_sort(int F, const float* __restrict__ fkey, int* __restrict__ order, int* __restrict__ rank) {
+    __shared__ unsigned long long s[REND_SORT_CAP];
+    const int img = blockIdx.x, t = threadIdx.x;
+    int P = 1;
+    while (P < F) P <<= 1;
+    const float* key = fkey + (size_t)img * F;
+    for (int i = t; i < P; i += 1024) {
+        unsigned long long v = ~0ull;
+        if (i < F) {
+            const float k = key[i];
+            unsigned u = __float_as_uint(k == 0.0f ? 0.0f : k);
+            u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);           // ascending unsigned = ascending float
+            v = ((unsigned long long)(~u) << 32) | (unsigned)i;        // complemented: descending float
+        }
+        s[i] = v;
+    }
+    __syncthreads();
+    for (int k = 2; k <= P; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = t; i < P; i += 1024) {
+                const int l = i ^ j;
+                if (l > i) {
+                    const unsigned long long x = s[i], y = s[l];
+                    const bool up = (i & k) == 0;
+                    if (up ? x > y : x < y) { s[i] = y; s[l] = x; }
+                }
+            }
+            __syncthreads();
+        }
+    for (int i = t; i < F; i += 1024) {
+        const int face = (int)(s[i] & 0xFFFFFFFFull);
+        order[(size_t)img * F + i] = face;
+        rank[(size_t)img * F + face] = i;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_rend_scatter(int F, const int* __restrict__ rank, int* __restrict__ order) {
+    const int img = blockIdx.y, face = blockIdx.x * 256 + threadIdx.x;
+    if (face < F) order[(size_t)img * F + rank[(size_t)img * F + face]] = face;
+}
+
+// per vertex (AvatarRenderer.cpp:113-166): vertNormal.col(v) += normal for every incident face in painter order (a face that
+// names v twice adds twice), colwise().normalize() (VectorwiseOp: division by the column norm, no zero guard, so a zero sum is
+// NaN), negated if z > 0; then the Lambert value std::max(float(main . n * 0.8 + back . n * 0.2) * 255, 0.f) with the light
+// vectors (light - vertex).normalized().  Sums of 3 terms go left to right.
+__global__ __launch_bounds__(256) void k_rend_vnormal(const double* __restrict__ cloud, const int* __restrict__ vf_start, const int* __restrict__ vf,
+                                                      const int* __restrict__ rank, const double* __restrict__ fnorm, int V, int F, double* vnorm,
+                                                      float* lam) {
+    const int img = blockIdx.y, v = blockIdx.x * 256 + threadIdx.x;
+    if (v >= V) return;
+    const int* rk = rank + (size_t)img * F;
+    const double* fn = fnorm + (size_t)img * F * 3;
+    const int s0 = vf_start[v], s1 = vf_start[v + 1];
+    double n0 = 0.0, n1 = 0.0, n2 = 0.0;
+    // selection in (position, slot) order: valences are small, and a slot with a position already taken is skipped by the
+    // strict lexicographic step
+    int last_pos = -1, last_slot = -1;
+    for (int step = s0; step < s1; ++step) {
+        int best_pos = 0x7FFFFFFF, best_slot = -1;
+        for (int sl = s0; sl < s1; ++sl) {
+            const int p = rk[vf[sl]];
+            const bool after = p > last_pos || (p == last_pos && sl > last_slot);
+            if (after && (p < best_pos || (p == best_pos && sl < best_slot))) { best_pos = p; best_slot = sl; }
+        }
+        const double* n = fn + 3 * (size_t)vf[best_slot];
+        n0 += n[0]; n1 += n[1]; n2 += n[2];
+        last_pos = best_pos; last_slot = best_slot;
+    }
+    const double nrm = sqrt(n0 * n0 + n1 * n1 + n2 * n2);
+    n0 = n0 / nrm; n1 = n1 / nrm; n2 = n2 / nrm;
+    if (n2 > 0) { n0 = -n0; n1 = -n1; n2 = -n2; }
+    double* vn = vnorm + ((size_t)img * V + v) * 3;
+    vn[0] = n0; vn[1] = n1; vn[2] = n2;
+    const double* a = cloud + ((size_t)img * V + v) * 3;
+    double m0 = 0.8 - a[0], m1 = 1.5 - a[1], m2 = -1.2 - a[2];
+    double b0 = -0.2 - a[0], b1 = -1.5 - a[1], b2 = 0.4 - a[2];
+    const double mz = m0 * m0 + m1 * m1 + m2 * m2, bz = b0 * b0 + b1 * b1 + b2 * b2;
+    if (mz > 0.0) { const double q = sqrt(mz); m0 = m0 / q; m1 = m1 / q; m2 = m2 / q; }
+    if (bz > 0.0) { const double q = sqrt(bz); b0 = b0 / q; b1 = b1 / q; b2 = b2 / q; }
+    const double dm = m0 * n0 + m1 * n1 + m2 * n2, db = b0 * n0 + b1 * n1 + b2 * n2;
+    const float val = (float)(dm * 0.8 + db * 0.2) * 255.f;
+    lam[(size_t)img * V + v] = (val < 0.f) ? 0.f : val;
+}
+
+struct RendImgs {
+    unsigned* dkey; unsigned* mkey; unsigned* lkey; int* faces;   // [images][npix] each, NULL when not selected
+};
+
+// one lane per face: its coverage in every selected image (renderDepth and renderPartMask as k_paint_cover; renderLambert's
+// visible faces with the barycentric row fill; renderFaces' end-exclusive row fill for every face)
+__global__ __launch_bounds__(256) void k_rend_cover(const float2* __restrict__ proj, const int* __restrict__ mesh, const int* __restrict__ rank,
+                                                    const unsigned char* __restrict__ fflag, RendImgs im, int V, int F, int width, int height) {
+    const int img = blockIdx.y, face = blockIdx.x * 256 + threadIdx.x;
+    if (face >= F) return;
+    float px[3], py[3];
+    for (int k = 0; k < 3; ++k) {
+        const float2 q = proj[(size_t)img * V + mesh[(size_t)k * F + face]];
+        px[k] = q.x; py[k] = q.y;
+    }
+    const size_t npix = (size_t)width * height, base = (size_t)img * npix;
+    const int pos = rank[(size_t)img * F + face];
+    const unsigned key = (unsigned)pos + 1u;
+    const unsigned char fl = fflag[(size_t)img * F + face];
+    const bool eo = (fl & 1) != 0;
+    if (im.dkey) {
+        unsigned* k = im.dkey + base;
+        auto mark = [&](int r, int c) { atomicMax(k + (size_t)r * width + c, key); };
+        if (eo) cover_rows<false>(px, py, width, height, mark); else cover_rows<true>(px, py, width, height, mark);
+    }
+    if (im.mkey) {
+        unsigned* k = im.mkey + base;
+        auto mark = [&](int r, int c) { atomicMax(k + (size_t)r * width + c, key); };
+        if (eo) cover_rows<false>(px, py, width, height, mark); else cover_cols(px, py, width, height, mark);
+    }
+    if (im.lkey && (fl & 2)) {
+        unsigned* k = im.lkey + base;
+        cover_rows<true>(px, py, width, height, [&](int r, int c) { atomicMax(k + (size_t)r * width + c, key); });
+    }
+    if (im.faces) {
+        int* k = im.faces + base;
+        cover_rows<false>(px, py, width, height, [&](int r, int c) { atomicMax(k + (size_t)r * width + c, pos); });
+    }
+}
+
+__device__ __forceinline__ void face_points(const float2* pr, const int* mesh, int F, int face, float px[3], float py[3], int vid[3]) {
+    for (int k = 0; k < 3; ++k) {
+        vid[k] = mesh[(size_t)k * F + face];
+        const float2 q = pr[vid[k]];
+        px[k] = q.x; py[k] = q.y;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_rend_resolve(const double* __restrict__ cloud, const float2* __restrict__ proj, const int* __restrict__ mesh,
+                                                      const int* __restrict__ order, const unsigned char* __restrict__ fflag, const float* __restrict__ lam,
+                                                      const int* __restrict__ vertex_part, RendImgs im, float* depth_img, unsigned char* mask_img,
+                                                      unsigned char* lam_img, int V, int F, int width, int height) {
+    const int img = blockIdx.y;
+    const size_t npix = (size_t)width * height;
+    const size_t o = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (o >= npix) return;
+    const size_t po = (size_t)img * npix + o;
+    const int i = (int)(o / width), j = (int)(o % width);          // row, column
+    const float2* pr = proj + (size_t)img * V;
+    const int* ord = order + (size_t)img * F;
+    const unsigned char* ff = fflag + (size_t)img * F;
+    float px[3], py[3]; int vid[3];
+    if (im.dkey) {
+        float depth = 0.f;
+        const unsigned k = im.dkey[po];
+        if (k != 0u) {
+            const int face = ord[k - 1];
+            if (!(ff[face] & 1)) {
+                face_points(pr, mesh, F, face, px, py, vid);
+                const double* cl = cloud + (size_t)img * 3 * V;
+                const float zv[3] = {(float)cl[3 * (size_t)vid[0] + 2], (float)cl[3 * (size_t)vid[1] + 2], (float)cl[3 * (size_t)vid[2] + 2]};
+                depth = bary_value(px, py, zv, i, j);
+            }
+        }
+        depth_img[po] = depth;
+    }
+    if (im.mkey) {
+        unsigned char lab = 255;
+        const unsigned k = im.mkey[po];
+        if (k != 0u) {
+            const int face = ord[k - 1];
+            if (!(ff[face] & 1)) {
+                face_points(pr, mesh, F, face, px, py, vid);
+                lab = part_label(px, py, vid, vertex_part, i, j);
+            }
+        }
+        mask_img[po] = lab;
+    }
+    if (im.lkey) {
+        unsigned char g = 0;
+        const unsigned k = im.lkey[po];
+        if (k != 0u) {
+            const int face = ord[k - 1];
+            face_points(pr, mesh, F, face, px, py, vid);
+            const float* lm = lam + (size_t)img * V;
+            const float zv[3] = {lm[vid[0]], lm[vid[1]], lm[vid[2]]};
+            g = (unsigned char)cvt_x86(bary_value(px, py, zv, i, j));   // uint8_t(float) on x86: truncation, NaN -> 0
+        }
+        lam_img[po] = g;
+    }
+}
+
+}  // namespace
+
+struct avt_renderer {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev_in = nullptr, ev_out = nullptr;
+    int V = 0, F = 0, J = 0, W = 0, H = 0, cap = 0;
+    float fx = 0, fy = 0, cx = 0, cy = 0;
+    int ordering = 0;
+    int n_images = 0, rendered = 0;                 // resident avatars; AVT_RENDER_* bits of the last run
+    std::vector<int> mesh_soa, main_joint;
+    std::vector<char> has_joints;
+    int *d_mesh = nullptr, *d_vf_start = nullptr, *d_vf = nullptr, *d_vpart = nullptr;
+    double *d_cloud = nullptr, *d_joints = nullptr, *d_fnorm = nullptr, *d_vnorm = nullptr;
+    float2 *d_proj = nullptr, *d_jproj = nullptr;
+    float *d_fkey = nullptr, *d_lam = nullptr;
+    unsigned char* d_fflag = nullptr;
+    int *d_order = nullptr, *d_rank = nullptr;
+    unsigned *d_dkey = nullptr, *d_mkey = nullptr, *d_lkey = nullptr;
+    int* d_faces = nullptr;
+    float* d_depth = nullptr;
+    unsigned char *d_mask = nullptr, *d_lambert = nullptr;
+};
+
+namespace {
+
+#define RD_HIP(x)                                                                                       \
+    do {                                                                                                \
+        const hipError_t e_ = (x);                                                                      \
+        if (e_ != hipSuccess) { avt_set_error(std::string(#x) + ": " + hipGetErrorString(e_)); return 1; } \
+    } while (0)
+
+template <class T>
+int rd_alloc(T** p, size_t n) {
+    if (*p) return 0;
+    RD_HIP(hipMalloc((void**)p, n * sizeof(T) + 16));
+    return 0;
+}
+
+int rd_create(int device, const avt_model* m, int W, int H, float fx, float fy, float cx, float cy, int cap, avt_renderer** out) {
+    if (!m || !out || W <= 0 || H <= 0 || cap <= 0 || (long long)W * H >= (1ll << 31) || (long long)W * H * cap >= (1ll << 40)) {
+        avt_set_error("avt_renderer_create: bad arguments (model, width, height, max_images > 0)");
+        return 1;
+    }
+    const int V = m->d.V, F = m->d.F, J = m->d.J;
+    if (F <= 0 || V <= 0 || F >= (1 << 30)) { avt_set_error("avt_renderer_create: the model has no faces"); return 1; }
+    RD_HIP(hipSetDevice(device));
+    avt_renderer* r = new avt_renderer();
+    r->device = device; r->V = V; r->F = F; r->J = J; r->W = W; r->H = H; r->cap = cap;
+    r->fx = fx; r->fy = fy; r->cx = cx; r->cy = cy;
+    r->mesh_soa = m->mesh_soa; r->main_joint = m->main_joint;
+    r->has_joints.assign((size_t)cap, 0);
+    // vertex -> incident faces, one entry per face slot (counting sort by vertex, faces ascending within a vertex)
+    std::vector<int> start((size_t)V + 1, 0), vf((size_t)3 * F);
+    for (int k = 0; k < 3; ++k) for (int f = 0; f < F; ++f) ++start[(size_t)r->mesh_soa[(size_t)k * F + f] + 1];
+    for (int v = 0; v < V; ++v) start[(size_t)v + 1] += start[(size_t)v];
+    {
+        std::vector<int> fill(start.begin(), start.end() - 1);
+        for (int f = 0; f < F; ++f) for (int k = 0; k < 3; ++k) vf[(size_t)fill[(size_t)r->mesh_soa[(size_t)k * F + f]]++] = f;
+    }
+    auto fail = [&]() { avt_renderer_destroy(r); return 1; };
+    if (hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&r->ev_in, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&r->ev_out, hipEventDisableTiming) != hipSuccess) {
+        avt_set_error("avt_renderer_create: stream creation failed");
+        return fail();
+    }
+    const size_t ci = (size_t)cap;
+    if (rd_alloc(&r->d_mesh, (size_t)3 * F) || rd_alloc(&r->d_vf_start, (size_t)V + 1) || rd_alloc(&r->d_vf, (size_t)3 * F) ||
+        rd_alloc(&r->d_vpart, (size_t)V) || rd_alloc(&r->d_cloud, ci * 3 * V) || rd_alloc(&r->d_joints, ci * 3 * (J > 0 ? J : 1)) ||
+        rd_alloc(&r->d_fnorm, ci * 3 * F) || rd_alloc(&r->d_proj, ci * V) || rd_alloc(&r->d_jproj, ci * (J > 0 ? J : 1)) ||
+        rd_alloc(&r->d_fkey, ci * F) || rd_alloc(&r->d_lam, ci * V) || rd_alloc(&r->d_vnorm, ci * 3 * V) || rd_alloc(&r->d_fflag, ci * F) || rd_alloc(&r->d_order, ci * F) ||
+        rd_alloc(&r->d_rank, ci * F))
+        return fail();
+    hipError_t e = hipMemcpyAsync(r->d_mesh, r->mesh_soa.data(), (size_t)3 * F * sizeof(int), hipMemcpyHostToDevice, r->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(r->d_vf_start, start.data(), ((size_t)V + 1) * sizeof(int), hipMemcpyHostToDevice, r->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(r->d_vf, vf.data(), (size_t)3 * F * sizeof(int), hipMemcpyHostToDevice, r->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(r->d_vpart, r->main_joint.data(), (size_t)V * sizeof(int), hipMemcpyHostToDevice, r->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(r->d_joints, 0, ci * 3 * (J > 0 ? J : 1) * sizeof(double), r->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(r->stream);            // the host tables are on this stack frame
+    if (e != hipSuccess) { avt_set_error(std::string("avt_renderer_create: ") + hipGetErrorString(e)); return fail(); }
+    *out = r;
+    return 0;
+}
+
+int rd_set_part_map(avt_renderer* r, int n, const int* map) {
+    if (!r || n < 0) { avt_set_error("avt_renderer_set_part_map: bad arguments"); return 1; }
+    std::vector<int> vp((size_t)r->V);
+    for (int v = 0; v < r->V; ++v) {
+        const int j = r->main_joint[(size_t)v];
+        if (map && n > 0 && (j < 0 || j >= n)) { avt_set_error("avt_renderer_set_part_map: the part map has fewer entries than the model's joints"); return 1; }
+        vp[(size_t)v] = (map && n > 0) ? map[j] : j;
+    }
+    RD_HIP(hipSetDevice(r->device));
+    RD_HIP(hipMemcpyAsync(r->d_vpart, vp.data(), (size_t)r->V * sizeof(int), hipMemcpyHostToDevice, r->stream));
+    RD_HIP(hipStreamSynchronize(r->stream));
+    return 0;
+}
+
+int rd_upload(avt_renderer* r, int n, const double* clouds, const double* joints) {
+    if (!r || !clouds || n <= 0 || n > r->cap) { avt_set_error("avt_renderer_upload: bad arguments (1 <= n_images <= max_images)"); return 1; }
+    RD_HIP(hipSetDevice(r->device));
+    RD_HIP(hipMemcpyAsync(r->d_cloud, clouds, (size_t)n * 3 * r->V * sizeof(double), hipMemcpyHostToDevice, r->stream));
+    if (joints && r->J > 0) RD_HIP(hipMemcpyAsync(r->d_joints, joints, (size_t)n * 3 * r->J * sizeof(double), hipMemcpyHostToDevice, r->stream));
+    RD_HIP(hipStreamSynchronize(r->stream));
+    for (int i = 0; i < n; ++i) r->has_joints[(size_t)i] = joints ? 1 : 0;
+    r->n_images = n; r->rendered = -1;
+    return 0;
+}
+
+int rd_from_ctx(avt_renderer* r, avt_ctx* c, int n, const int* frames) {
+    if (!r || !c || n <= 0 || n > r->cap) { avt_set_error("avt_renderer_from_ctx: bad arguments (1 <= n_images <= max_images)"); return 1; }
+    if (c->dm.d.V != r->V || c->dm.d.F != r->F || c->dm.d.J != r->J || c->device != r->device) {
+        avt_set_error("avt_renderer_from_ctx: the context's model or device is not the renderer's");
+        return 1;
+    }
+    for (int i = 0; i < n; ++i) {
+        const int f = frames ? frames[i] : i;
+        if (f < 0 || f >= c->fb.max_frames) { avt_set_error("avt_renderer_from_ctx: frame index out of range"); return 1; }
+    }
+    RD_HIP(hipSetDevice(r->device));
+    // after everything queued on the context (its side streams join its main stream), and before anything queued on it later
+    RD_HIP(hipEventRecord(r->ev_in, c->stream));
+    RD_HIP(hipStreamWaitEvent(r->stream, r->ev_in, 0));
+    const size_t cb = (size_t)3 * r->V * sizeof(double), jb = (size_t)3 * r->J * sizeof(double);
+    for (int i = 0; i < n;) {
+        const int f = frames ? frames[i] : i;
+        int run = 1;                                                   // consecutive frames go in one copy
+        while (i + run < n && (frames ? frames[i + run] : i + run) == f + run) ++run;
+        RD_HIP(hipMemcpyAsync(r->d_cloud + (size_t)i * 3 * r->V, c->fb.cloud + (size_t)f * 3 * r->V, run * cb, hipMemcpyDeviceToDevice, r->stream));
+        if (r->J > 0)
+            RD_HIP(hipMemcpyAsync(r->d_joints + (size_t)i * 3 * r->J, c->fb.jointpos + (size_t)f * 3 * r->J, run * jb, hipMemcpyDeviceToDevice, r->stream));
+        i += run;
+    }
+    RD_HIP(hipEventRecord(r->ev_out, r->stream));
+    RD_HIP(hipStreamWaitEvent(c->stream, r->ev_out, 0));
+    for (int i = 0; i < n; ++i) r->has_joints[(size_t)i] = 1;
+    r->n_images = n; r->rendered = -1;
+    return 0;
+}
+
+int rd_run(avt_renderer* r, int what) {
+    if (!r || r->n_images <= 0) { avt_set_error("avt_renderer_run: no avatars resident"); return 1; }
+    if (what & ~(AVT_RENDER_DEPTH | AVT_RENDER_PART_MASK | AVT_RENDER_LAMBERT | AVT_RENDER_FACES)) { avt_set_error("avt_renderer_run: unknown output bits"); return 1; }
+    RD_HIP(hipSetDevice(r->device));
+    const int n = r->n_images, V = r->V, F = r->F, J = r->J, W = r->W, H = r->H;
+    const size_t npix = (size_t)W * H, tot = npix * n, ci = (size_t)r->cap * npix;
+    RendImgs im{nullptr, nullptr, nullptr, nullptr};
+    if (what & AVT_RENDER_DEPTH) { if (rd_alloc(&r->d_dkey, ci) || rd_alloc(&r->d_depth, ci)) return 1; im.dkey = r->d_dkey; }
+    if (what & AVT_RENDER_PART_MASK) { if (rd_alloc(&r->d_mkey, ci) || rd_alloc(&r->d_mask, ci)) return 1; im.mkey = r->d_mkey; }
+    if (what & AVT_RENDER_LAMBERT) { if (rd_alloc(&r->d_lkey, ci) || rd_alloc(&r->d_lambert, ci)) return 1; im.lkey = r->d_lkey; }
+    if (what & AVT_RENDER_FACES) { if (rd_alloc(&r->d_faces, ci)) return 1; im.faces = r->d_faces; }
+    hipStream_t s = r->stream;
+    if (im.dkey) RD_HIP(hipMemsetAsync(im.dkey, 0, tot * sizeof(unsigned), s));
+    if (im.mkey) RD_HIP(hipMemsetAsync(im.mkey, 0, tot * sizeof(unsigned), s));
+    if (im.lkey) RD_HIP(hipMemsetAsync(im.lkey, 0, tot * sizeof(unsigned), s));
+    if (im.faces) RD_HIP(hipMemsetAsync(im.faces, 0xFF, tot * sizeof(int), s));            // -1
+    const double fx = r->fx, fy = r->fy, cx = r->cx, cy = r->cy;                           // float intrinsics promoted (AvatarRenderer.cpp:16-19)
+    const int vb = (std::max(V, J) + 255) / 256, fb = (F + 255) / 256;
+    hipLaunchKernelGGL(k_rend_project, dim3(vb, n), dim3(256), 0, s, r->d_cloud, r->d_joints, r->d_proj, r->d_jproj, V, J, fx, fy, cx, cy);
+    hipLaunchKernelGGL(k_rend_faces, dim3(fb, n), dim3(256), 0, s, r->d_cloud, r->d_mesh, V, F, r->d_fkey, r->d_fflag, r->d_fnorm);
+    if (r->ordering == 0 && F <= REND_SORT_CAP) {
+        hipLaunchKernelGGL(k_rend_sort, dim3(n), dim3(1024), 0, s, F, r->d_fkey, r->d_order, r->d_rank);
+    } else {
+        hipLaunchKernelGGL(k_paint_rank, dim3(fb, n), dim3(256), 0, s, F, r->d_fkey, r->d_rank);
+        hipLaunchKernelGGL(k_rend_scatter, dim3(fb, n), dim3(256), 0, s, F, r->d_rank, r->d_order);
+    }
+    if (im.lkey)
+        hipLaunchKernelGGL(k_rend_vnormal, dim3((V + 255) / 256, n), dim3(256), 0, s, r->d_cloud, r->d_vf_start, r->d_vf, r->d_rank, r->d_fnorm, V, F, r->d_vnorm, r->d_lam);
+    if (what) {
+        hipLaunchKernelGGL(k_rend_cover, dim3(fb, n), dim3(256), 0, s, r->d_proj, r->d_mesh, r->d_rank, r->d_fflag, im, V, F, W, H);
+        if (im.dkey || im.mkey || im.lkey)
+            hipLaunchKernelGGL(k_rend_resolve, dim3((unsigned)((npix + 255) / 256), n), dim3(256), 0, s, r->d_cloud, r->d_proj, r->d_mesh, r->d_order, r->d_fflag,
+                               r->d_lam, r->d_vpart, im, r->d_depth, r->d_mask, r->d_lambert, V, F, W, H);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { avt_set_error(std::string("avt_renderer_run: launch failed: ") + hipGetErrorString(e)); return 1; }
+    r->rendered = what;
+    return 0;
+}
+
+int rd_download(avt_renderer* r, int image, float* depth, unsigned char* mask, unsigned char* lam, int* faces) {
+    if (!r || image < 0 || image >= r->n_images || r->rendered < 0) { avt_set_error("avt_renderer_download: bad image, or no run since the avatars changed"); return 1; }
+    if ((depth && !(r->rendered & AVT_RENDER_DEPTH)) || (mask && !(r->rendered & AVT_RENDER_PART_MASK)) || (lam && !(r->rendered & AVT_RENDER_LAMBERT)) ||
+        (faces && !(r->rendered & AVT_RENDER_FACES))) {
+        avt_set_error("avt_renderer_download: an image the last run did not render was asked for");
+        return 1;
+    }
+    RD_HIP(hipSetDevice(r->device));
+    const size_t npix = (size_t)r->W * r->H, o = (size_t)image * npix;
+    if (depth) RD_HIP(hipMemcpyAsync(depth, r->d_depth + o, npix * sizeof(float), hipMemcpyDeviceToHost, r->stream));
+    if (mask) RD_HIP(hipMemcpyAsync(mask, r->d_mask + o, npix, hipMemcpyDeviceToHost, r->stream));
+    if (lam) RD_HIP(hipMemcpyAsync(lam, r->d_lambert + o, npix, hipMemcpyDeviceToHost, r->stream));
+    if (faces) RD_HIP(hipMemcpyAsync(faces, r->d_faces + o, npix * sizeof(int), hipMemcpyDeviceToHost, r->stream));
+    RD_HIP(hipStreamSynchronize(r->stream));
+    return 0;
+}
+
+int rd_projection(avt_renderer* r, int image, float* pts, float* jts, float* keys, int* faces, int* face_pos) {
+    if (!r || image < 0 || image >= r->n_images || r->rendered < 0) { avt_set_error("avt_renderer_projection: bad image, or no run since the avatars changed"); return 1; }
+    if (jts && !r->has_joints[(size_t)image]) { avt_set_error("avt_renderer_projection: no joints were given for this image"); return 1; }
+    RD_HIP(hipSetDevice(r->device));
+    const int F = r->F;
+    std::vector<int> order((size_t)F);
+    std::vector<float> fk((size_t)F);
+    if (pts) RD_HIP(hipMemcpyAsync(pts, r->d_proj + (size_t)image * r->V, (size_t)r->V * sizeof(float2), hipMemcpyDeviceToHost, r->stream));
+    if (jts && r->J > 0) RD_HIP(hipMemcpyAsync(jts, r->d_jproj + (size_t)image * r->J, (size_t)r->J * sizeof(float2), hipMemcpyDeviceToHost, r->stream));
+    if (face_pos) RD_HIP(hipMemcpyAsync(face_pos, r->d_rank + (size_t)image * F, (size_t)F * sizeof(int), hipMemcpyDeviceToHost, r->stream));
+    if (keys || faces) {
+        RD_HIP(hipMemcpyAsync(order.data(), r->d_order + (size_t)image * F, (size_t)F * sizeof(int), hipMemcpyDeviceToHost, r->stream));
+        RD_HIP(hipMemcpyAsync(fk.data(), r->d_fkey + (size_t)image * F, (size_t)F * sizeof(float), hipMemcpyDeviceToHost, r->stream));
+    }
+    RD_HIP(hipStreamSynchronize(r->stream));
+    for (int p = 0; p < F && (keys || faces); ++p) {
+        const int f = order[(size_t)p];
+        if (f < 0 || f >= F) { avt_set_error("avt_renderer_projection: the painter order is not a permutation"); return AVT_STATUS_DEVICE_FAULT; }
+        if (keys) keys[p] = fk[(size_t)f];
+        if (faces) for (int k = 0; k < 3; ++k) faces[3 * (size_t)p + k] = r->mesh_soa[(size_t)k * F + f];
+    }
+    return 0;
+}
+
+int rd_shading(avt_renderer* r, int image, double* normals, float* lam) {
+    if (!r || image < 0 || image >= r->n_images || r->rendered < 0 || !(r->rendered & AVT_RENDER_LAMBERT)) {
+        avt_set_error("avt_renderer_vertex_shading: bad image, or the last run did not render the Lambert image");
+        return 1;
+    }
+    RD_HIP(hipSetDevice(r->device));
+    const size_t V = (size_t)r->V;
+    if (normals) RD_HIP(hipMemcpyAsync(normals, r->d_vnorm + (size_t)image * 3 * V, 3 * V * sizeof(double), hipMemcpyDeviceToHost, r->stream));
+    if (lam) RD_HIP(hipMemcpyAsync(lam, r->d_lam + (size_t)image * V, V * sizeof(float), hipMemcpyDeviceToHost, r->stream));
+    RD_HIP(hipStreamSynchronize(r->stream));
+    return 0;
+}
+
+}  // namespace
+
+#define RD_ENTRY(name, call)                                                                       \
+    try { return call; }                                                                           \
+    catch (const std::exception& e) { avt_set_error(std::string(name ": ") + e.what()); return 1; } \
+    catch (...) { avt_set_error(name ": unknown exception"); return 1; }
+
+extern "C" {
+int avt_renderer_create(int device, const avt_model* m, int width, int height, float fx, float fy, float cx, float cy, int max_images,
+                        avt_renderer** out) {
+    RD_ENTRY("avt_renderer_create", rd_create(device, m, width, height, fx, fy, cx, cy, max_images, out))
+}
+
+void avt_renderer_destroy(avt_renderer* r) {
+    if (!r) return;
+    (void)hipSetDevice(r->device);
+    if (r->stream) (void)hipStreamSynchronize(r->stream);
+    for (void* p : {(void*)r->d_mesh, (void*)r->d_vf_start, (void*)r->d_vf, (void*)r->d_vpart, (void*)r->d_cloud, (void*)r->d_joints, (void*)r->d_fnorm,
+                    (void*)r->d_proj, (void*)r->d_jproj, (void*)r->d_fkey, (void*)r->d_lam, (void*)r->d_vnorm, (void*)r->d_fflag, (void*)r->d_order, (void*)r->d_rank,
+                    (void*)r->d_dkey, (void*)r->d_mkey, (void*)r->d_lkey, (void*)r->d_faces, (void*)r->d_depth, (void*)r->d_mask, (void*)r->d_lambert})
+        if (p) (void)hipFree(p);
+    if (r->ev_in) (void)hipEventDestroy(r->ev_in);
+    if (r->ev_out) (void)hipEventDestroy(r->ev_out);
+    if (r->stream) (void)hipStreamDestroy(r->stream);
+    delete r;
+}
+
+int avt_renderer_set_part_map(avt_renderer* r, int n_joints, const int* part_map) {
+    RD_ENTRY("avt_renderer_set_part_map", rd_set_part_map(r, n_joints, part_map))
+}
+int avt_renderer_upload(avt_renderer* r, int n_images, const double* clouds, const double* joints) {
+    RD_ENTRY("avt_renderer_upload", rd_upload(r, n_images, clouds, joints))
+}
+int avt_renderer_from_ctx(avt_renderer* r, avt_ctx* c, int n_images, const int* frames) {
+    RD_ENTRY("avt_renderer_from_ctx", rd_from_ctx(r, c, n_images, frames))
+}
+int avt_renderer_run(avt_renderer* r, int what) { RD_ENTRY("avt_renderer_run", rd_run(r, what)) }
+int avt_renderer_download(avt_renderer* r, int image, float* depth, unsigned char* part_mask, unsigned char* lambert, int* faces) {
+    RD_ENTRY("avt_renderer_download", rd_download(r, image, depth, part_mask, lambert, faces))
+}
+int avt_renderer_projection(avt_renderer* r, int image, float* points_2xV, float* joints_2xJ, float* face_keys, int* faces_3xF, int* face_pos) {
+    RD_ENTRY("avt_renderer_projection", rd_projection(r, image, points_2xV, joints_2xJ, face_keys, faces_3xF, face_pos))
+}
+int avt_renderer_vertex_shading(avt_renderer* r, int image, double* normals_3xV, float* lambert_v) {
+    RD_ENTRY("avt_renderer_vertex_shading", rd_shading(r, image, normals_3xV, lambert_v))
+}
+int avt_renderer_sync(avt_renderer* r) {
+    if (!r) { avt_set_error("avt_renderer_sync: null handle"); return 1; }
+    const hipError_t e = hipStreamSynchronize(r->stream);
+    if (e != hipSuccess) { avt_set_error(std::string("avt_renderer_sync: ") + hipGetErrorString(e)); return 1; }
+    return 0;
+}
+int avt_renderer_set_ordering(avt_renderer* r, int ordering) {
+    if (!r || (ordering != 0 && ordering != 1)) { avt_set_error("avt_renderer_set_ordering: bad arguments (0 = sort, 1 = rank count)"); return 1; }
+    r->ordering = ordering;
+    return 0;
+}
+}  // extern "C"

@@ -209,6 +209,12 @@ class MultiFrameTracker:
         """(cloud (V,3), jointPos (J,3), jointTrans (J,12)) of the stream's last fit (one download; avt_get_posed)."""
         return self.ctx.posed(stream)
 
+    def render(self, streams, size, intrin, what=None, part_map=None):
+        """The last fit of the given streams rendered on the device in one run, read straight from the context (no cloud download;
+        avatar_amd.render): a list of dicts as render.Renderer.download returns them.  `what`: render.* bits, Lambert by default."""
+        from . import render
+        return render.render_streams(self, streams, size, intrin, render.LAMBERT if what is None else what, part_map)
+
     def rotations(self, stream):
         """The stream's joint rotations (J,3,3), as FrameTracker's Avatar.r holds them."""
         return api.quat_to_rot(self.q[stream])

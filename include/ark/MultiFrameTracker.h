@@ -11,7 +11,9 @@
 #include <cstdint>
 #include <vector>
 
+#include "../avt_render.h"
 #include "AvatarOptimizer.h"
+#include "RTree.h"
 #include "TrackerPolicy.h"
 
 namespace ark {
@@ -35,8 +37,12 @@ class MultiFrameTracker {
           stats((size_t)num_streams), clouds((size_t)num_streams), labels((size_t)num_streams), cnz((size_t)num_streams) {
         for (int s = 0; s < S; ++s) for (int j = 0; j < J; ++j) q[((size_t)s * J + j) * 4 + 3] = 1.0;
         ARK_AVT_CHECK(avt_ctx_create(device, model.handle, num_parts, part_map.data(), max_points_per_frame, num_streams, &ctx));
+        device_ = device;
     }
-    ~MultiFrameTracker() { if (ctx) avt_ctx_destroy(ctx); }
+    ~MultiFrameTracker() {
+        avt_renderer_destroy(rend);
+        if (ctx) avt_ctx_destroy(ctx);
+    }
     MultiFrameTracker(const MultiFrameTracker&) = delete;
     MultiFrameTracker& operator=(const MultiFrameTracker&) = delete;
 
@@ -111,6 +117,33 @@ class MultiFrameTracker {
     void posed(int s, double* cloud_3xV, double* joint_pos_3xJ = nullptr, double* joint_trans_12xJ = nullptr) {
         ARK_AVT_CHECK(avt_get_posed(ctx, s, cloud_3xV, joint_pos_3xJ, joint_trans_12xJ));
     }
+    /** Renders the last fit of the given streams on the device in one run (avt_render.h): the posed clouds are read from the
+     *  context, not downloaded.  what: AVT_RENDER_* bits; part_map as AvatarRenderer::renderPartMask.  Image i of the run
+     *  belongs to streams[i]: fetch it with renderedDepth / renderedPartMask / renderedLambert / renderedFaces. */
+    void render(const std::vector<int>& stream_ids, const Size& image_size, const CameraIntrin& intrin, int what = AVT_RENDER_LAMBERT,
+                const std::vector<int>& part_map = {}) {
+        if (!rend || image_size.width != rendW || image_size.height != rendH || intrin.fx != rendIntrin.fx || intrin.fy != rendIntrin.fy ||
+            intrin.cx != rendIntrin.cx || intrin.cy != rendIntrin.cy) {
+            avt_renderer_destroy(rend);
+            rend = nullptr;
+            ARK_AVT_CHECK(avt_renderer_create(device_, model.handle, image_size.width, image_size.height, intrin.fx, intrin.fy, intrin.cx,
+                                              intrin.cy, S, &rend));
+            rendW = image_size.width; rendH = image_size.height; rendIntrin = intrin;
+        }
+        if (what & AVT_RENDER_PART_MASK)
+            ARK_AVT_CHECK(avt_renderer_set_part_map(rend, (int)part_map.size(), part_map.empty() ? nullptr : part_map.data()));
+        ARK_AVT_CHECK(avt_renderer_from_ctx(rend, ctx, (int)stream_ids.size(), stream_ids.data()));
+        ARK_AVT_CHECK(avt_renderer_run(rend, what));
+    }
+    ImageF renderedDepth(int i) const { ImageF o(rendH, rendW); ARK_AVT_CHECK(avt_renderer_download(rend, i, o.data(), nullptr, nullptr, nullptr)); return o; }
+    Image8 renderedPartMask(int i) const { Image8 o(rendH, rendW); ARK_AVT_CHECK(avt_renderer_download(rend, i, nullptr, o.data(), nullptr, nullptr)); return o; }
+    Image8 renderedLambert(int i) const { Image8 o(rendH, rendW); ARK_AVT_CHECK(avt_renderer_download(rend, i, nullptr, nullptr, o.data(), nullptr)); return o; }
+    Image<int32_t> renderedFaces(int i) const {
+        Image<int32_t> o(rendH, rendW);
+        ARK_AVT_CHECK(avt_renderer_download(rend, i, nullptr, nullptr, nullptr, o.data()));
+        return o;
+    }
+
     const double* pos(int s) const { return &p[3 * (size_t)s]; }
     const double* shape(int s) const { return &w[(size_t)K * s]; }
     const double* quats(int s) const { return &q[4 * (size_t)J * s]; }           // J quaternions (x, y, z, w)
@@ -136,6 +169,10 @@ class MultiFrameTracker {
 
    private:
     avt_ctx* ctx = nullptr;
+    int device_ = 0;
+    avt_renderer* rend = nullptr;                  // render(): created on first use, again when the size or the intrinsics change
+    int rendW = 0, rendH = 0;
+    CameraIntrin rendIntrin;
     bool stateResident = false;
     std::vector<CloudType> clouds;
     std::vector<VectorXi> labels;
