@@ -972,3 +972,18 @@ int avt_renderer_set_ordering(avt_renderer* r, int ordering) {
     return 0;
 }
 }  // extern "C"
+
+// The forest trainer's device-to-device path (avt_rtree_train.cpp): the last run's depth and part-mask images of all resident
+// avatars, made visible to stream `s` after everything queued on the renderer.  The caller waits for its own work on `s`
+// before the renderer may run again (avt_rtree_trainer_add_rendered and avt_rtree_transfer_rendered return after it).
+int avt_renderer_images_for(avt_renderer* r, hipStream_t s, const float** depth, const unsigned char** mask, int* n, int* width, int* height) {
+    if (!r || r->n_images <= 0 || r->rendered < 0 || !(r->rendered & AVT_RENDER_DEPTH) || !(r->rendered & AVT_RENDER_PART_MASK)) {
+        avt_set_error("renderer: the last run rendered no depth and part mask (avt_renderer_run(r, AVT_RENDER_DEPTH | AVT_RENDER_PART_MASK))");
+        return 1;
+    }
+    RD_HIP(hipSetDevice(r->device));
+    RD_HIP(hipEventRecord(r->ev_out, r->stream));
+    RD_HIP(hipStreamWaitEvent(s, r->ev_out, 0));
+    *depth = r->d_depth; *mask = r->d_mask; *n = r->n_images; *width = r->W; *height = r->H;
+    return 0;
+}

@@ -47,9 +47,8 @@ int validate(const avt_rtree* rt) {
     return 0;
 }
 
-int upload_tree(avt_rtree* rt) {
-    if (rt->device < 0) return 0;   // host-only tree: file formats and post-processing work, inference refuses
-    RT_HIP(hipSetDevice(rt->device));
+// the device image of the tree: one packing for the first upload and for the re-upload after trainTransfer
+std::vector<RtNodeDev> pack_nodes(const avt_rtree* rt) {
     const int n = (int)(rt->links.size() / 3);
     std::vector<RtNodeDev> dev(n);
     for (int i = 0; i < n; ++i) {
@@ -58,6 +57,14 @@ int upload_tree(avt_rtree* rt) {
         dev[i] = RtNodeDev{f[0], f[1], f[2], f[3], f[4], leaf < 0 ? rt->links[3 * i] : (int)rt->leaf_best[leaf], leaf < 0 ? rt->links[3 * i + 1] : leaf,
                            leaf < 0 ? 0 : 1};
     }
+    return dev;
+}
+
+int upload_tree(avt_rtree* rt) {
+    if (rt->device < 0) return 0;   // host-only tree: file formats and post-processing work, inference refuses
+    RT_HIP(hipSetDevice(rt->device));
+    const int n = (int)(rt->links.size() / 3);
+    const std::vector<RtNodeDev> dev = pack_nodes(rt);
     RT_HIP(hipStreamCreateWithFlags(&rt->stream, hipStreamNonBlocking));
     RT_HIP(hipMalloc((void**)&rt->d_nodes, sizeof(RtNodeDev) * n));
     RT_HIP(hipMemcpyAsync(rt->d_nodes, dev.data(), sizeof(RtNodeDev) * n, hipMemcpyHostToDevice, rt->stream));
@@ -157,6 +164,18 @@ struct Filler {
 };
 
 }  // namespace
+
+int avt_rtree_refresh_leaves(avt_rtree* rt) {
+    best_match_table(rt);
+    if (rt->device < 0 || !rt->d_nodes) return 0;
+    RT_HIP(hipSetDevice(rt->device));
+    const int n = (int)(rt->links.size() / 3);
+    const std::vector<RtNodeDev> dev = pack_nodes(rt);
+    RT_HIP(hipMemcpyAsync(rt->d_nodes, dev.data(), sizeof(RtNodeDev) * n, hipMemcpyHostToDevice, rt->stream));
+    RT_HIP(hipMemcpyAsync(rt->d_leaf, rt->leaf_data.data(), sizeof(float) * rt->leaf_data.size(), hipMemcpyHostToDevice, rt->stream));
+    RT_HIP(hipStreamSynchronize(rt->stream));
+    return 0;
+}
 
 extern "C" {
 
@@ -290,6 +309,7 @@ void avt_rtree_destroy(avt_rtree* rt) {
     if (rt->d_leaf) (void)hipFree(rt->d_leaf);
     if (rt->d_depth) (void)hipFree(rt->d_depth);
     if (rt->d_labels) (void)hipFree(rt->d_labels);
+    if (rt->d_tcount) (void)hipFree(rt->d_tcount);
     if (rt->stream) (void)hipStreamDestroy(rt->stream);
     delete rt;
 }

@@ -33,7 +33,10 @@ struct avt_rtree {
     unsigned char* d_labels = nullptr;
     size_t cap_pixels = 0;           // capacity of d_depth / d_labels in pixels
     int n_images = 0, rows = 0, cols = 0;
+    unsigned long long* d_tcount = nullptr;   // trainTransfer's (leaf, part) counts since the last avt_rtree_transfer_finish
 };
 
 int avt_rtree_launch_predict_dist(avt_rtree* rt, int rows, int cols, float* d_out);
 int avt_rtree_launch_predict(avt_rtree* rt, int n_images, int rows, int cols, int interval, int tlx, int tly, int brx, int bry, int fill);
+// after leaf_data changed (trainTransfer): re-derives leafBestMatch and uploads nodes and distributions again (avt_rtree.cpp)
+int avt_rtree_refresh_leaves(avt_rtree* rt);

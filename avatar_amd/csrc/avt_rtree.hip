@@ -5,11 +5,11 @@
 // dependent loads (node -> two depth probes -> next node), so the kernel is bound by L2 / MALL latency, not by
 // arithmetic; the tree (32 B per node) and the probed part of the image stay cache-resident, and thousands of
 // independent walks per CU hide the latency.  Arithmetic is the reference's float32 sequence exactly (this file is
-// built with -ffp-contract=off): u / depth per component, round-half-away (std::round), int32 cast, bounds against the
-// REGION OF INTEREST, zero depth -> BACKGROUND_DEPTH (RTree.cpp:325), zu - zv < thresh -> left child.
+// built with -ffp-contract=off; rt_score_by_feature in avt_rtree_score.h, shared with the trainer): u / depth per component,
+// round-half-away (std::round), int32 cast, bounds against the REGION OF INTEREST, zero depth -> BACKGROUND_DEPTH
+// (RTree.cpp:325), zu - zv < thresh -> left child.
 #include "avt_rtree.h"
-
-#define RT_BACKGROUND_DEPTH 20.f
+#include "avt_rtree_score.h"
 
 __global__ __launch_bounds__(256) void k_rtree_predict(const RtNodeDev* __restrict__ nodes, const float* __restrict__ depth,
                                                        unsigned char* __restrict__ labels, int rows, int cols, int interval, int tlx, int tly,
@@ -30,12 +30,7 @@ __global__ __launch_bounds__(256) void k_rtree_predict(const RtNodeDev* __restri
             const float4 a = nv[2 * nodeid], b = nv[2 * nodeid + 1];
             const int lnode = __float_as_int(b.y);
             if (__float_as_int(b.w)) { lab = (unsigned char)lnode; break; }
-            const int ux = (int)roundf(__fdiv_rn(a.x, sample)) + c, uy = (int)roundf(__fdiv_rn(a.y, sample)) + r;
-            const int vx = (int)roundf(__fdiv_rn(a.z, sample)) + c, vy = (int)roundf(__fdiv_rn(a.w, sample)) + r;
-            float zu = RT_BACKGROUND_DEPTH, zv = RT_BACKGROUND_DEPTH;
-            if (!(ux < tlx || uy < tly || ux > brx || uy > bry)) { zu = d[(size_t)uy * cols + ux]; if (zu == 0.0f) zu = RT_BACKGROUND_DEPTH; }
-            if (!(vx < tlx || vy < tly || vx > brx || vy > bry)) { zv = d[(size_t)vy * cols + vx]; if (zv == 0.0f) zv = RT_BACKGROUND_DEPTH; }
-            nodeid = (zu - zv < b.x) ? lnode : __float_as_int(b.z);
+            nodeid = (rt_score_by_feature(d, cols, 0, 0, tlx, tly, brx, bry, c, r, sample, a) < b.x) ? lnode : __float_as_int(b.z);
         }
     }
     if (fill && interval > 1) {       // upscaleGrid: the cell [r, r+interval) x [c, c+interval), rows <= bot_right.y, width clamped
@@ -63,12 +58,7 @@ __global__ __launch_bounds__(256) void k_rtree_predict_dist(const RtNodeDev* __r
     for (;;) {
         const float4 a = nv[2 * nodeid], b = nv[2 * nodeid + 1];
         if (__float_as_int(b.w)) { leaf = __float_as_int(b.z); break; }
-        const int ux = (int)roundf(__fdiv_rn(a.x, sample)) + c, uy = (int)roundf(__fdiv_rn(a.y, sample)) + r;
-        const int vx = (int)roundf(__fdiv_rn(a.z, sample)) + c, vy = (int)roundf(__fdiv_rn(a.w, sample)) + r;
-        float zu = RT_BACKGROUND_DEPTH, zv = RT_BACKGROUND_DEPTH;
-        if (!(ux < 0 || uy < 0 || ux >= cols || uy >= rows)) { zu = depth[(size_t)uy * cols + ux]; if (zu == 0.0f) zu = RT_BACKGROUND_DEPTH; }
-        if (!(vx < 0 || vy < 0 || vx >= cols || vy >= rows)) { zv = depth[(size_t)vy * cols + vx]; if (zv == 0.0f) zv = RT_BACKGROUND_DEPTH; }
-        nodeid = (zu - zv < b.x) ? __float_as_int(b.y) : __float_as_int(b.z);
+        nodeid = (rt_score_by_feature(depth, cols, 0, 0, 0, 0, cols - 1, rows - 1, c, r, sample, a) < b.x) ? __float_as_int(b.y) : __float_as_int(b.z);
     }
     const float* d = leaf_data + (size_t)leaf * num_parts;
     for (int i = 0; i < num_parts; ++i) out[(size_t)i * plane + o] = d[i];

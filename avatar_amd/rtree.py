@@ -68,6 +68,70 @@ class RTree:
         self._refresh()
         return self
 
+    @classmethod
+    def _from_handle(cls, handle, device=0):
+        self = cls(None, device)
+        self._h = handle
+        self._refresh()
+        return self
+
+    # ---- training on the GPU (include/avt_rtree_train.h, avatar_amd/rtree_train.py) ----
+    @classmethod
+    def train_from_images(cls, depth, part_mask, num_parts, num_points_per_image=2000, num_features=5000, max_probe_offset=170.0,
+                          min_samples=1, max_tree_depth=20, min_samples_per_feature=20, seed=0, part_map=None, part_map_type=0, batch=None,
+                          device=0, return_stats=False):
+        """RTree::train's V3 trainer (RTree.cpp:2338-2950) on in-memory images: depth (n, rows, cols) float32 metres, part_mask
+        (n, rows, cols) uint8 (255 = none).  Defaults: `rtree-train`'s command line.  `batch` images are added per call (the tree
+        does not depend on it)."""
+        from . import rtree_train
+        tr = rtree_train.Trainer(num_parts, num_points_per_image, num_features, max_probe_offset, min_samples, max_tree_depth,
+                                 min_samples_per_feature, seed, device)
+        d, m = rtree_train._images(depth, part_mask)
+        step = batch or len(d)
+        for i in range(0, len(d), step):
+            tr.add_images(d[i:i + step], m[i:i + step])
+        tree, stats = tr.run(part_map, part_map_type)
+        return (tree, stats) if return_stats else tree
+
+    @classmethod
+    def trainFromAvatar(cls, model, intrin, image_size, num_threads=0, verbose=False, num_images=30000, num_points_per_image=5000,
+                        num_features=2000, num_features_filtered=200, max_probe_offset=225, min_samples=100, max_tree_depth=20,
+                        min_samples_per_feature=20, frac_samples_per_feature=0.01, threshes_per_feature=15, part_map=None,
+                        max_images_loaded=50, mem_limit_mb=12000, train_partial_save_path="", seed=0, batch=64, device=0):
+        """RTree::trainFromAvatar (include/RTree.h:112-132, the empty pose-sequence branch) with the reference's defaults: image
+        idx is `model`'s avatar posed by Avatar.randomize(True, True, True, idx ^ xor_key), rendered (renderDepth /
+        renderPartMask) on the GPU and handed to the trainer device to device.  Python's randomize draws from numpy's generator,
+        so the poses differ from the C++ facade's (std::mt19937); xor_key is rtree_train.xor_key(seed) in both.  num_threads, num_features_filtered, frac_samples_per_feature, threshes_per_feature,
+        max_images_loaded, mem_limit_mb and train_partial_save_path do not change V3's result and are ignored."""
+        from . import api, render, rtree_train
+        pm = np.arange(model.numJoints(), dtype=np.int32) if part_map is None else np.asarray(part_map, np.int32)
+        num_parts = int(pm.max()) + 1
+        W, H = image_size
+        tr = rtree_train.Trainer(num_parts, num_points_per_image, num_features, float(max_probe_offset), min_samples, max_tree_depth,
+                                 min_samples_per_feature, seed, device)
+        xor_key = rtree_train.xor_key(seed)
+        rend = render.Renderer(model, W, H, intrin, max_images=batch, device=device)
+        rend.set_part_map(pm)
+        ava = api.Avatar(model)
+        for i0 in range(0, num_images, batch):
+            k = min(batch, num_images - i0)
+            clouds = []
+            for idx in range(i0, i0 + k):
+                ava.randomize(True, True, True, (idx ^ xor_key) & 0xFFFFFFFF)
+                ava.update()
+                clouds.append(ava.cloud.copy())
+            rend.upload(np.stack(clouds))
+            rend.run(render.DEPTH | render.PART_MASK)
+            tr.add_rendered(rend)                 # device to device: the images never leave the GPU
+        tree, _ = tr.run(pm, 0)
+        return tree
+
+    def trainTransfer(self, depth, part_mask):
+        """RTree::trainTransfer (RTree.cpp:3332-3420) over in-memory images (n, rows, cols): leaves reached by a labelled pixel get
+        the integer counts' distribution, the others keep theirs; returns how many were never reached."""
+        from . import rtree_train
+        return rtree_train.transfer(self, depth, part_mask)
+
     def __del__(self):
         if getattr(self, "_h", None) and self._h.value:
             self._lib.avt_rtree_destroy(self._h)

@@ -2,7 +2,9 @@
 // same class name, member names, defaults and call protocol for the inference side (loadFile, exportFile, predictBest,
 // postProcess, numParts, partMap, leafData, leafBestMatch).  cv::Mat is replaced by the two plain row-major images
 // below, cv::Point by ark::Point, Eigen::Matrix<double,2,Dynamic> by MatrixNX<2> (same column-major layout).
-// The trainers (RTree.cpp:330-2955, train / trainFromAvatar / trainTransfer) are out of scope.
+// Training runs on the GPU (include/avt_rtree_train.h): trainFromAvatar is the V3 trainer (RTree.cpp:2338-2950) on avatars
+// skinned, rendered and sampled on the device; train(images...) feeds it in-memory depth images and part masks;
+// trainTransfer(images...) re-fits the leaves (:3332-3420).  The V2 trainer of train(depth_dir, part_mask_dir, ...) is not built.
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -12,6 +14,8 @@
 
 #include "../avt.h"
 #include "../avt_rtree.h"
+#include "../avt_rtree_train.h"
+#include "Avatar.h"
 #include "Types.h"
 
 namespace ark {
@@ -89,6 +93,97 @@ public:
         return result;
     }
 
+    /** The V3 trainer (RTree.cpp:2338-2950) on in-memory images, parameters in the reference's order (include/RTree.h:88-105;
+     *  defaults: rtree-train's command line).  num_threads and verbose are accepted and ignored.  Replaces this tree (numParts
+     *  must be set); like the rest of this class a failure is fatal (message + exit). */
+    void train(const std::vector<ImageF>& depth, const std::vector<Image8>& part_mask, int /*num_threads*/ = 0, bool /*verbose*/ = false,
+               int num_points_per_image = 2000, int num_features = 5000, int max_probe_offset = 170, int min_samples = 1, int max_tree_depth = 20,
+               int min_samples_per_feature = 20, uint64_t seed = 0, const std::vector<int>& part_map = {}, int part_map_type = 0) {
+        if (depth.empty() || depth.size() != part_mask.size()) fatal("train", "need as many part masks as depth images, at least one");
+        avt_rtree_trainer* tr = trainer(num_points_per_image, num_features, max_probe_offset, min_samples, max_tree_depth, min_samples_per_feature, seed);
+        std::vector<float> d;
+        std::vector<uint8_t> m;
+        for (size_t i = 0; i < depth.size();) {          // runs of same-size images go in one call
+            size_t j = i;
+            d.clear(); m.clear();
+            for (; j < depth.size() && depth[j].rows == depth[i].rows && depth[j].cols == depth[i].cols; ++j) {
+                if (part_mask[j].rows != depth[j].rows || part_mask[j].cols != depth[j].cols) fatal("train", "a part mask differs in size from its depth image");
+                d.insert(d.end(), depth[j].a.begin(), depth[j].a.end());
+                m.insert(m.end(), part_mask[j].a.begin(), part_mask[j].a.end());
+            }
+            if (avt_rtree_trainer_add_images(tr, (int)(j - i), depth[i].rows, depth[i].cols, d.data(), m.data()) != 0) die("train");
+            i = j;
+        }
+        finish_training(tr, part_map, part_map_type);
+    }
+
+    /** RTree::trainFromAvatar (include/RTree.h:112-132; the empty pose-sequence branch of AvatarDataSource, RTree.cpp:421-549):
+     *  image idx is avatar_model posed by Avatar::randomize(true, true, true, idx ^ xorKey) (xorKey = avt_rt_xor_key(seed)),
+     *  skinned by avt_lbs_update into a context of this call and rendered by the GPU renderer (renderDepth, renderPartMask with
+     *  part_map), `batch` images at a time, handed to the trainer device to device.  numParts must be set; an empty part_map
+     *  is the joint id itself.  The parameters V3 does not read are accepted and ignored. */
+    void trainFromAvatar(AvatarModel& avatar_model, const CameraIntrin& intrin, const Size& image_size, int /*num_threads*/ = 0, bool /*verbose*/ = false,
+                         int num_images = 30000, int num_points_per_image = 5000, int num_features = 2000, int /*num_features_filtered*/ = 200,
+                         int max_probe_offset = 225, int min_samples = 100, int max_tree_depth = 20, int min_samples_per_feature = 20,
+                         float /*frac_samples_per_feature*/ = 0.01f, int /*threshes_per_feature*/ = 15, const std::vector<int>& part_map = {},
+                         int /*max_images_loaded*/ = 50, int /*mem_limit_mb*/ = 12000, const std::string& /*train_partial_save_path*/ = "",
+                         uint64_t seed = 0, int batch = 64) {
+        const int J = avatar_model.numJoints(), K = avatar_model.numShapeKeys();
+        std::vector<int> pm(part_map);
+        if (pm.empty()) for (int j = 0; j < J; ++j) pm.push_back(j);
+        if ((int)pm.size() < J || num_images < 1 || batch < 1) fatal("trainFromAvatar", "part_map needs one entry per joint; num_images, batch >= 1");
+        int np = 0;
+        for (int v : pm) np = v + 1 > np ? v + 1 : np;
+        avt_rtree_trainer* tr = trainer(num_points_per_image, num_features, max_probe_offset, min_samples, max_tree_depth, min_samples_per_feature, seed);
+        avt_ctx* ctx = nullptr;
+        avt_renderer* rend = nullptr;
+        if (avt_ctx_create(device_, avatar_model.handle, np, pm.data(), 64, batch, &ctx) != 0 ||
+            avt_renderer_create(device_, avatar_model.handle, image_size.width, image_size.height, intrin.fx, intrin.fy, intrin.cx, intrin.cy, batch,
+                                &rend) != 0 ||
+            avt_renderer_set_part_map(rend, (int)pm.size(), pm.data()) != 0)
+            die("trainFromAvatar");
+        const uint32_t xorKey = avt_rt_xor_key(seed);
+        Avatar ava(avatar_model);
+        std::vector<double> w, p, R;
+        for (int i0 = 0; i0 < num_images; i0 += batch) {
+            const int k = num_images - i0 < batch ? num_images - i0 : batch;
+            w.assign((size_t)K * k, 0.0); p.assign((size_t)3 * k, 0.0); R.assign((size_t)9 * J * k, 0.0);
+            for (int i = 0; i < k; ++i) {
+                ava.randomize(true, true, true, (uint32_t)(i0 + i) ^ xorKey);
+                for (int c = 0; c < K; ++c) w[(size_t)i * K + c] = ava.w[c];
+                for (int c = 0; c < 3; ++c) p[(size_t)i * 3 + c] = ava.p(c);
+                for (int j = 0; j < J; ++j)
+                    for (int c = 0; c < 9; ++c) R[((size_t)i * J + j) * 9 + c] = ava.r[j].data()[c];
+            }
+            if (avt_lbs_update(ctx, k, w.data(), p.data(), R.data(), nullptr, nullptr, nullptr) != 0 || avt_renderer_from_ctx(rend, ctx, k, nullptr) != 0 ||
+                avt_renderer_run(rend, AVT_RENDER_DEPTH | AVT_RENDER_PART_MASK) != 0 || avt_rtree_trainer_add_rendered(tr, rend) != 0)
+                die("trainFromAvatar");
+        }
+        avt_renderer_destroy(rend);
+        avt_ctx_destroy(ctx);
+        finish_training(tr, pm, 0);
+    }
+
+    /** RTree::trainTransfer (RTree.cpp:3332-3420) over in-memory images of one size: returns the number of leaves never reached
+     *  (they keep their weights); a failure is fatal. */
+    int trainTransfer(const std::vector<ImageF>& depth, const std::vector<Image8>& part_mask, int /*num_threads*/ = 0, bool /*verbose*/ = false) {
+        if (!ensure()) fatal("trainTransfer", "no tree");
+        if (depth.empty() || depth.size() != part_mask.size()) fatal("trainTransfer", "need as many part masks as depth images, at least one");
+        const int rows = depth[0].rows, cols = depth[0].cols;
+        std::vector<float> d;
+        std::vector<uint8_t> m;
+        for (size_t i = 0; i < depth.size(); ++i) {
+            if (depth[i].rows != rows || depth[i].cols != cols || part_mask[i].rows != rows || part_mask[i].cols != cols)
+                fatal("trainTransfer", "the images must share one size");
+            d.insert(d.end(), depth[i].a.begin(), depth[i].a.end());
+            m.insert(m.end(), part_mask[i].a.begin(), part_mask[i].a.end());
+        }
+        int unvisited = 0;
+        if (avt_rtree_transfer_images(h_, (int)depth.size(), rows, cols, d.data(), m.data(), &unvisited) != 0) die("trainTransfer");
+        pull();
+        return unvisited;
+    }
+
     /** RTree.h:150-166 */
     void postProcess(Image8& image, MatrixNX<2>& com_pre, int interval = 1, int /*num_threads*/ = 1, Point top_left = Point(0, 0),
                      Point bot_right = Point(-1, -1), double dist_to_pre_weight = 0.001) {
@@ -140,6 +235,25 @@ private:
         }
         leafData.assign(nl, Distribution());
         for (int i = 0; i < nl; ++i) leafData[i].assign(ld.begin() + (size_t)i * numParts, ld.begin() + (size_t)(i + 1) * numParts);
+    }
+    avt_rtree_trainer* trainer(int k, int f, int probe, int min_samples, int depth, int T, uint64_t seed) {
+        avt_rtree_train_params p{numParts, k, f, (float)probe, min_samples, depth, T, seed};
+        avt_rtree_trainer* tr = nullptr;
+        if (avt_rtree_trainer_create(device_, &p, &tr) != 0) die("train");
+        return tr;
+    }
+    void finish_training(avt_rtree_trainer* tr, const std::vector<int>& part_map, int part_map_type) {
+        avt_rtree* out = nullptr;
+        const int rc = avt_rtree_trainer_run(tr, (int)part_map.size(), part_map.data(), part_map_type, &out, nullptr);
+        avt_rtree_trainer_destroy(tr);
+        if (rc != 0) die("train");
+        avt_rtree_destroy(h_);
+        h_ = out;
+        pull();
+    }
+    [[noreturn]] void fatal(const char* what, const char* why) {
+        fprintf(stderr, "FATAL: RTree::%s: %s\n", what, why);
+        std::exit(1);
     }
     [[noreturn]] void die(const char* what) {   // the reference's failure mode for this class is a fatal message + exit (RTree.cpp:2984-2996)
         fprintf(stderr, "FATAL: RTree::%s: %s\n", what, avt_last_error());
