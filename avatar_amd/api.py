@@ -15,18 +15,7 @@ import os
 import numpy as np
 
 from . import capi
-from .capi import ModelArrays, Options, Profile, Stats, bptr, dptr, iptr
-
-
-class AvtError(RuntimeError):
-    pass
-
-
-def _check(rc):
-    if rc != 0:
-        e = AvtError(capi.load_library().avt_last_error().decode())
-        e.status = rc            # avt.h: AVT_STATUS_NO_DEVICE 2, AVT_STATUS_DEVICE_FAULT 3
-        raise e
+from .capi import AvtError, ModelArrays, Options, Profile, Stats, bptr, check, dptr, iptr
 
 
 # ---- rotation <-> quaternion exactly as optimize() converts (AvatarOptimizer.cpp:1250-1254, :1494-1496):
@@ -113,21 +102,21 @@ class AvatarModel:
         if handle is not None:      # an avt_model* built elsewhere (avt_model_unpack / avt_shard_broadcast_model): adopt it
             self.h = handle
             V, J, K, F, P = (C.c_int() for _ in range(5))
-            _check(self._lib.avt_model_dims(self.h, C.byref(V), C.byref(J), C.byref(K), C.byref(F), C.byref(P)))
+            check(self._lib.avt_model_dims(self.h, C.byref(V), C.byref(J), C.byref(K), C.byref(F), C.byref(P)))
             a = self.arrays
             if (V.value, J.value, K.value, F.value, P.value) != (a.V, a.J, a.K, a.F, a.P):
                 raise AvtError("AvatarModel: adopted handle and host arrays disagree on the model dimensions")
         else:
             self.h = C.c_void_p()
-            _check(self._lib.avt_model_create(C.byref(self._desc), C.byref(self.h)))
+            check(self._lib.avt_model_create(C.byref(self._desc), C.byref(self.h)))
         self.parent = self.arrays.parent
         self.mesh = self.arrays.mesh
         ijp = np.empty(3 * self.numJoints()); jsr = np.empty(3 * self.numJoints() * self.numShapeKeys())
-        _check(self._lib.avt_model_joint_regression(self.h, dptr(ijp), dptr(jsr)))
+        check(self._lib.avt_model_joint_regression(self.h, dptr(ijp), dptr(jsr)))
         self.initialJointPos = ijp.reshape(-1, 3)
         self.jointShapeReg = jsr.reshape(self.numShapeKeys(), -1).T
         mj = np.empty(self.numPoints(), np.int32)
-        _check(self._lib.avt_model_main_joint(self.h, iptr(mj)))
+        check(self._lib.avt_model_main_joint(self.h, iptr(mj)))
         self.mainJoint = mj
         self._default_ctx = None
 
@@ -245,8 +234,8 @@ class Context:
         if len(pm) < model.numJoints():
             raise AvtError("part_map must have at least numJoints entries (AvatarOptimizer.cpp:1229)")
         self.h = C.c_void_p()
-        _check(self._lib.avt_ctx_create(C.c_int(device), model.h, C.c_int(num_parts), iptr(pm), C.c_int(max_points),
-                                        C.c_int(max_frames), C.byref(self.h)))
+        check(self._lib.avt_ctx_create(C.c_int(device), model.h, C.c_int(num_parts), iptr(pm), C.c_int(max_points),
+                                       C.c_int(max_frames), C.byref(self.h)))
         self.max_points, self.max_frames, self.num_parts = max_points, max_frames, num_parts
         self.device = device
 
@@ -266,20 +255,20 @@ class Context:
         F = w.shape[0]
         Rcm = np.ascontiguousarray(np.transpose(R, (0, 1, 3, 2)))  # column-major 3x3 blocks
         cloud = np.empty((F, m.numPoints(), 3)); jp = np.empty((F, m.numJoints(), 3)); jt = np.empty((F, m.numJoints(), 12))
-        _check(self._lib.avt_lbs_update(self.h, C.c_int(F), dptr(w), dptr(p), dptr(Rcm), dptr(cloud), dptr(jp), dptr(jt)))
+        check(self._lib.avt_lbs_update(self.h, C.c_int(F), dptr(w), dptr(p), dptr(Rcm), dptr(cloud), dptr(jp), dptr(jt)))
         return cloud, jp, jt
 
     def visibility(self, cloud, enable=True):
         cloud = np.ascontiguousarray(cloud, np.float64)
         vis = np.empty(self.model.numPoints(), np.uint8)
-        _check(self._lib.avt_visibility(self.h, dptr(cloud), C.c_int(int(enable)), bptr(vis)))
+        check(self._lib.avt_visibility(self.h, dptr(cloud), C.c_int(int(enable)), bptr(vis)))
         return vis
 
     def nn(self, model_cloud, visible, data, labels):
         mc = np.ascontiguousarray(model_cloud, np.float64); vis = np.ascontiguousarray(visible, np.uint8)
         data = np.ascontiguousarray(data, np.float64); labels = np.ascontiguousarray(labels, np.int32)
         out = np.empty(len(labels), np.int32)
-        _check(self._lib.avt_nn(self.h, dptr(mc), bptr(vis), dptr(data), iptr(labels), C.c_int(len(labels)), iptr(out)))
+        check(self._lib.avt_nn(self.h, dptr(mc), bptr(vis), dptr(data), iptr(labels), C.c_int(len(labels)), iptr(out)))
         return out
 
     def optimize_batch(self, datas, labels, opt: Options, p, q, w):
@@ -293,8 +282,8 @@ class Context:
         p = np.array(p, np.float64).reshape(F, 3).copy(); q = np.array(q, np.float64).reshape(F, -1).copy()
         w = np.array(w, np.float64).reshape(F, -1).copy()
         st = (Stats * F)()
-        _check(self._lib.avt_optimize_batch(self.h, C.c_int(F), dptr(data), iptr(lab), iptr(offs), C.byref(opt), dptr(p),
-                                            dptr(q), dptr(w), st))
+        check(self._lib.avt_optimize_batch(self.h, C.c_int(F), dptr(data), iptr(lab), iptr(offs), C.byref(opt), dptr(p),
+                                           dptr(q), dptr(w), st))
         return p, q.reshape(F, -1, 4), w, list(st)
 
     def optimize_posed(self, data, labels, opt: Options, p, q, w):
@@ -305,8 +294,8 @@ class Context:
         p = np.array(p, np.float64).reshape(3).copy(); q = np.array(q, np.float64).reshape(-1).copy(); w = np.array(w, np.float64).reshape(-1).copy()
         st = Stats()
         cloud = np.empty((m.numPoints(), 3)); jp = np.empty((m.numJoints(), 3)); jt = np.empty((m.numJoints(), 12))
-        _check(self._lib.avt_optimize_posed(self.h, dptr(data), iptr(lab), C.c_int(len(lab)), C.byref(opt), dptr(p), dptr(q), dptr(w), C.byref(st),
-                                            dptr(cloud), dptr(jp), dptr(jt)))
+        check(self._lib.avt_optimize_posed(self.h, dptr(data), iptr(lab), C.c_int(len(lab)), C.byref(opt), dptr(p), dptr(q), dptr(w), C.byref(st),
+                                           dptr(cloud), dptr(jp), dptr(jt)))
         self._N = np.array([len(lab)], np.int32)
         return p, q.reshape(-1, 4), w, st, cloud, jp, jt
 
@@ -324,7 +313,7 @@ class Context:
 
         def call():
             p[:] = ps; q[:] = qs; w[:] = ws
-            _check(fn(h, a_d, a_l, n, a_o, a_p, a_q, a_w, a_s))
+            check(fn(h, a_d, a_l, n, a_o, a_p, a_q, a_w, a_s))
         call._keep = (data, lab, opt)
         return call, p, q, w, st
 
@@ -335,7 +324,7 @@ class Context:
             offs[f + 1] = offs[f] + len(labels[f])
         data = np.ascontiguousarray(np.concatenate([np.asarray(d, np.float64).reshape(-1, 3) for d in datas], 0))
         lab = np.ascontiguousarray(np.concatenate([np.asarray(l, np.int32) for l in labels]))
-        _check(self._lib.avt_frames_upload(self.h, C.c_int(F), dptr(data), iptr(lab), iptr(offs)))
+        check(self._lib.avt_frames_upload(self.h, C.c_int(F), dptr(data), iptr(lab), iptr(offs)))
         self._F = F
 
     def render_frames(self, w, p, R, intrin=None, res_scale=1, painter=False):
@@ -350,10 +339,10 @@ class Context:
         F = w.shape[0]
         Rcm = np.ascontiguousarray(np.transpose(R, (0, 1, 3, 2)))
         n = np.zeros(F, np.int32)
-        _check(self._lib.avt_synth_render_frames_mode(self.h, C.c_int(F), dptr(w), dptr(p), dptr(Rcm), C.c_double(k["fx"] * res_scale),
-                                                      C.c_double(k["fy"] * res_scale), C.c_double(k["cx"] * res_scale),
-                                                      C.c_double(k["cy"] * res_scale), C.c_int(k["width"] * res_scale),
-                                                      C.c_int(k["height"] * res_scale), C.c_int(1 if painter else 0), iptr(n)))
+        check(self._lib.avt_synth_render_frames_mode(self.h, C.c_int(F), dptr(w), dptr(p), dptr(Rcm), C.c_double(k["fx"] * res_scale),
+                                                     C.c_double(k["fy"] * res_scale), C.c_double(k["cx"] * res_scale),
+                                                     C.c_double(k["cy"] * res_scale), C.c_int(k["width"] * res_scale),
+                                                     C.c_int(k["height"] * res_scale), C.c_int(1 if painter else 0), iptr(n)))
         self._F = F
         self._N = n
         self._img_shape = (k["height"] * res_scale, k["width"] * res_scale)
@@ -364,31 +353,31 @@ class Context:
         what AvatarRenderer::renderDepth / renderPartMask return."""
         H, W = self._img_shape
         depth = np.empty((H, W), np.float32); mask = np.empty((H, W), np.uint8)
-        _check(self._lib.avt_synth_render_images(self.h, C.c_int(frame), depth.ctypes.data_as(C.POINTER(C.c_float)),
-                                                 mask.ctypes.data_as(C.POINTER(C.c_ubyte))))
+        check(self._lib.avt_synth_render_images(self.h, C.c_int(frame), capi.ptr(depth, C.c_float),
+                                                capi.ptr(mask, C.c_ubyte)))
         return depth, mask
 
     def frame_download(self, frame):
         n = int(self._N[frame])
         data = np.empty((n, 3)); lab = np.empty(n, np.int32)
-        _check(self._lib.avt_frames_download(self.h, C.c_int(frame), dptr(data), iptr(lab)))
+        check(self._lib.avt_frames_download(self.h, C.c_int(frame), dptr(data), iptr(lab)))
         return data, lab
 
     def state_upload(self, p, q, w):
         F = self._F
         p = np.ascontiguousarray(np.asarray(p, np.float64).reshape(F, 3)); q = np.ascontiguousarray(np.asarray(q, np.float64).reshape(F, -1))
         w = np.ascontiguousarray(np.asarray(w, np.float64).reshape(F, -1))
-        _check(self._lib.avt_state_upload(self.h, C.c_int(F), dptr(p), dptr(q), dptr(w)))
+        check(self._lib.avt_state_upload(self.h, C.c_int(F), dptr(p), dptr(q), dptr(w)))
 
     def optimize_resident(self, opt: Options):
-        _check(self._lib.avt_optimize_resident(self.h, C.byref(opt)))
+        check(self._lib.avt_optimize_resident(self.h, C.byref(opt)))
 
     def optimize_resident_budgets(self, opt: Options, budgets):
         """avt_optimize_resident with a per-frame ICP budget (one int per resident frame, 0 .. opt.icp_iters; 0 = not fitted)."""
         b = np.ascontiguousarray(np.asarray(budgets, np.int32).reshape(-1))
         if len(b) != self._F:
             raise AvtError(f"optimize_resident_budgets: {len(b)} budgets for {self._F} resident frames")
-        _check(self._lib.avt_optimize_resident_budgets(self.h, C.byref(opt), iptr(b)))
+        check(self._lib.avt_optimize_resident_budgets(self.h, C.byref(opt), iptr(b)))
 
     def state_upload_frames(self, frames, p, q, w):
         """Overwrite the resident state of the listed frames (working and start copies); the other frames keep theirs."""
@@ -398,57 +387,57 @@ class Context:
         if p.size != 3 * n or q.size != 4 * J * n or w.size != K * n:
             raise AvtError(f"state_upload_frames: want p ({n},3), q ({n},{J},4), w ({n},{K}); got sizes {p.size}, {q.size}, {w.size}")
         p = np.ascontiguousarray(p.reshape(n, 3)); q = np.ascontiguousarray(q.reshape(n, 4 * J)); w = np.ascontiguousarray(w.reshape(n, K))
-        _check(self._lib.avt_state_upload_frames(self.h, C.c_int(n), iptr(fr), dptr(p), dptr(q), dptr(w)))
+        check(self._lib.avt_state_upload_frames(self.h, C.c_int(n), iptr(fr), dptr(p), dptr(q), dptr(w)))
 
     def state_reset(self):
         """Asynchronous device-side reinstall of the last uploaded start state (no host transfer, no synchronisation)."""
-        _check(self._lib.avt_state_reset(self.h))
+        check(self._lib.avt_state_reset(self.h))
 
     def sync(self):
-        _check(self._lib.avt_sync(self.h))
+        check(self._lib.avt_sync(self.h))
 
     def state_download(self):
         F = self._F; m = self.model
         p = np.empty((F, 3)); q = np.empty((F, m.numJoints() * 4)); w = np.empty((F, m.numShapeKeys()))
         st = (Stats * F)()
-        _check(self._lib.avt_state_download(self.h, dptr(p), dptr(q), dptr(w), st))
+        check(self._lib.avt_state_download(self.h, dptr(p), dptr(q), dptr(w), st))
         return p, q.reshape(F, -1, 4), w, list(st)
 
     def correspondences(self, frame, n):
         out = np.empty(n, np.int32)
-        _check(self._lib.avt_get_correspondences(self.h, C.c_int(frame), iptr(out)))
+        check(self._lib.avt_get_correspondences(self.h, C.c_int(frame), iptr(out)))
         return out
 
     def cloud(self, frame=0):
         out = np.empty((self.model.numPoints(), 3))
-        _check(self._lib.avt_get_cloud(self.h, C.c_int(frame), dptr(out)))
+        check(self._lib.avt_get_cloud(self.h, C.c_int(frame), dptr(out)))
         return out
 
     def posed(self, frame=0):
         """(cloud (V,3), jointPos (J,3), jointTrans (J,12)) left by the update() that ends optimize()."""
         m = self.model
         cloud = np.empty((m.numPoints(), 3)); jp = np.empty((m.numJoints(), 3)); jt = np.empty((m.numJoints(), 12))
-        _check(self._lib.avt_get_posed(self.h, C.c_int(frame), dptr(cloud), dptr(jp), dptr(jt)))
+        check(self._lib.avt_get_posed(self.h, C.c_int(frame), dptr(cloud), dptr(jp), dptr(jt)))
         return cloud, jp, jt
 
     def normal_equations(self, frame=0):
         P = self.model.arrays.P
         H = np.empty((P, P)); g = np.empty(P); cost = C.c_double()
-        _check(self._lib.avt_get_normal_equations(self.h, C.c_int(frame), dptr(H), dptr(g), C.byref(cost)))
+        check(self._lib.avt_get_normal_equations(self.h, C.c_int(frame), dptr(H), dptr(g), C.byref(cost)))
         return H, g, cost.value
 
     def cost_trace(self, frame=0, n=11):
         """Objective at entry of the last ICP iteration and after each of its GN iterations (avt_debug_trace): entry i + 1 < entry i
         means iteration i + 1 accepted its trial point."""
         buf = np.zeros(64)
-        _check(self._lib.avt_debug_trace(self.h, C.c_int(frame), dptr(buf)))
+        check(self._lib.avt_debug_trace(self.h, C.c_int(frame), dptr(buf)))
         return buf[:n].copy()
 
     def mfma_count(self, frame=0):
         """fp64 matrix instructions (2048 flop each) the kernels execute for `frame` with the last optimize()'s correspondences, from their
         own trip counts (avt_debug_mfma_count): dict eval_rows / moments / solve, None where the form did not run."""
         a, b, c = C.c_longlong(), C.c_longlong(), C.c_longlong()
-        _check(self._lib.avt_debug_mfma_count(self.h, C.c_int(frame), C.byref(a), C.byref(b), C.byref(c)))
+        check(self._lib.avt_debug_mfma_count(self.h, C.c_int(frame), C.byref(a), C.byref(b), C.byref(c)))
         return {k: (None if v.value < 0 else int(v.value)) for k, v in (("eval_rows", a), ("moments", b), ("solve", c))}
 
     DATA_TERM_ROWS, DATA_TERM_MOMENTS, DATA_TERM_AUTO = 0, 1, 2
@@ -456,7 +445,7 @@ class Context:
     def tuning(self):
         """The knobs this context runs with (include/avt.h avt_tuning) as a capi.Tuning."""
         t = capi.Tuning()
-        _check(self._lib.avt_ctx_get_tuning(self.h, C.byref(t)))
+        check(self._lib.avt_ctx_get_tuning(self.h, C.byref(t)))
         return t
 
     def set_tuning(self, **kw):
@@ -466,12 +455,12 @@ class Context:
             if k not in dict(t._fields_):
                 raise KeyError(k)
             setattr(t, k, int(v))
-        _check(self._lib.avt_ctx_set_tuning(self.h, C.byref(t)))
+        check(self._lib.avt_ctx_set_tuning(self.h, C.byref(t)))
         return self
 
     def set_data_term(self, form):
         """How the ICP data term of a GN iteration is evaluated (include/avt.h: AVT_DATA_TERM_ROWS / AVT_DATA_TERM_MOMENTS)."""
-        _check(self._lib.avt_set_data_term(self.h, C.c_int(int(form))))
+        check(self._lib.avt_set_data_term(self.h, C.c_int(int(form))))
 
     def data_term(self):
         return int(self._lib.avt_get_data_term(self.h))
@@ -479,17 +468,17 @@ class Context:
     def launch_shape(self):
         """(groups, frames per group, k_eval workgroups per frame) of optimize() over the resident frames."""
         g, n, G = C.c_int(), C.c_int(), C.c_int()
-        _check(self._lib.avt_launch_shape(self.h, C.byref(g), C.byref(n), C.byref(G)))
+        check(self._lib.avt_launch_shape(self.h, C.byref(g), C.byref(n), C.byref(G)))
         return g.value, n.value, G.value
 
     def profile_begin(self, classes=None):
         mask = 0xffffffff if classes is None else sum(1 << capi.AVT_K_NAMES.index(c) for c in classes)
-        _check(self._lib.avt_profile_select(self.h, C.c_uint(mask)))
-        _check(self._lib.avt_profile_begin(self.h))
+        check(self._lib.avt_profile_select(self.h, C.c_uint(mask)))
+        check(self._lib.avt_profile_begin(self.h))
 
     def profile_end(self):
         pr = Profile()
-        _check(self._lib.avt_profile_end(self.h, C.byref(pr)))
+        check(self._lib.avt_profile_end(self.h, C.byref(pr)))
         return {capi.AVT_K_NAMES[i]: (pr.ms[i], pr.launches[i]) for i in range(capi.AVT_K_COUNT)}
 
 

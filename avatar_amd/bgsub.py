@@ -25,16 +25,6 @@ class Frame(C.Structure):
                 ("comps", (C.c_int * 2) * MAX_COMPS)]
 
 
-def _fp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_float))
-
-
-def _check(lib, rc):
-    if rc != 0:
-        lib.avt_last_error.restype = C.c_char_p
-        raise RuntimeError((lib.avt_last_error() or b"?").decode())
-
-
 def _xyz(a, shape):
     a = np.ascontiguousarray(a, np.float32)
     if a.shape[-3:] != shape:
@@ -77,8 +67,8 @@ class BGSubtractor:
             raise ValueError("BGSubtractor: background must be (rows, cols, 3) or (n, rows, cols, 3)")
         self._shape = bgs.shape[1:]
         self._bgs = bgs.copy()
-        _check(self._lib, self._lib.avt_bgsub_create(C.c_int(device), C.c_int(bgs.shape[0]), C.c_int(bgs.shape[1]), C.c_int(bgs.shape[2]),
-                                                     _fp(bgs), C.byref(self._h)))
+        capi.check(self._lib.avt_bgsub_create(C.c_int(device), C.c_int(bgs.shape[0]), C.c_int(bgs.shape[1]), C.c_int(bgs.shape[2]),
+                                              capi.ptr(bgs, C.c_float), C.byref(self._h)))
         self._n = 0
 
     def __del__(self):
@@ -96,7 +86,7 @@ class BGSubtractor:
 
     def set_background(self, xyz, index=0):
         a = _xyz(xyz, self._shape)
-        _check(self._lib, self._lib.avt_bgsub_set_background(self._h, C.c_int(index), _fp(a)))
+        capi.check(self._lib.avt_bgsub_set_background(self._h, C.c_int(index), capi.ptr(a, C.c_float)))
         self._bgs[index] = a
 
     def run(self, image, comps_by_size=False, background_index=0):
@@ -108,9 +98,9 @@ class BGSubtractor:
         fr = Frame()
         fr.top_left[:] = self.topLeft
         fr.bot_right[:] = self.botRight
-        _check(self._lib, self._lib.avt_bgsub_run(self._h, C.c_int(background_index), _fp(a), C.c_float(self.nnDistThreshRel),
-                                                  C.c_float(self.neighbThreshRel), mask.ctypes.data_as(C.POINTER(C.c_ubyte)), _fp(depth),
-                                                  C.byref(fr)))
+        capi.check(self._lib.avt_bgsub_run(self._h, C.c_int(background_index), capi.ptr(a, C.c_float), C.c_float(self.nnDistThreshRel),
+                                           C.c_float(self.neighbThreshRel), capi.ptr(mask, C.c_ubyte), capi.ptr(depth, C.c_float),
+                                           C.byref(fr)))
         self._n = 1
         res = Result(mask, depth, fr)
         self.topLeft, self.botRight, self.maskedDepth, self.fgCount, self.capped = res.topLeft, res.botRight, depth, res.fg_count, res.capped
@@ -124,23 +114,22 @@ class BGSubtractor:
         n = a.shape[0]
         bi = None if bg_index is None else np.ascontiguousarray(bg_index, np.int32)
         pb = None if prev_boxes is None else np.ascontiguousarray(prev_boxes, np.int32).reshape(n, 4)
-        ip = C.POINTER(C.c_int)
-        _check(self._lib, self._lib.avt_bgsub_images_upload(self._h, C.c_int(n), _fp(a), None if bi is None else bi.ctypes.data_as(ip),
-                                                            None if pb is None else pb.ctypes.data_as(ip)))
+        capi.check(self._lib.avt_bgsub_images_upload(self._h, C.c_int(n), capi.ptr(a, C.c_float), capi.ptr(bi, C.c_int),
+                                                     capi.ptr(pb, C.c_int)))
         self._n = n
 
     def run_resident(self):
-        _check(self._lib, self._lib.avt_bgsub_run_resident(self._h, C.c_float(self.nnDistThreshRel), C.c_float(self.neighbThreshRel)))
+        capi.check(self._lib.avt_bgsub_run_resident(self._h, C.c_float(self.nnDistThreshRel), C.c_float(self.neighbThreshRel)))
 
     def sync(self):
-        _check(self._lib, self._lib.avt_bgsub_sync(self._h))
+        capi.check(self._lib.avt_bgsub_sync(self._h))
 
     def download(self, image, with_depth=True) -> Result:
         mask = np.empty(self._shape[:2], np.uint8)
         depth = np.empty(self._shape[:2], np.float32) if with_depth else None
         fr = Frame()
-        _check(self._lib, self._lib.avt_bgsub_download(self._h, C.c_int(image), mask.ctypes.data_as(C.POINTER(C.c_ubyte)),
-                                                       None if depth is None else _fp(depth), C.byref(fr)))
+        capi.check(self._lib.avt_bgsub_download(self._h, C.c_int(image), capi.ptr(mask, C.c_ubyte),
+                                                capi.ptr(depth, C.c_float), C.byref(fr)))
         return Result(mask, depth, fr)
 
     def run_batch(self, images, bg_index=None, prev_boxes=None):

@@ -121,6 +121,23 @@ def bptr(a):
     return a.ctypes.data_as(c_ubyte_p)
 
 
+def ptr(a, ctype):
+    """Pointer to the data of a numpy array as POINTER(ctype); None stays None (an optional argument of the C ABI)."""
+    return None if a is None else a.ctypes.data_as(C.POINTER(ctype))
+
+
+class AvtError(RuntimeError):
+    """A call of the C ABI failed: the message is avt_last_error(), `.status` the code it returned (include/avt.h: 1, AVT_STATUS_NO_DEVICE 2,
+    AVT_STATUS_DEVICE_FAULT 3)."""
+
+
+def check(rc):
+    if rc != 0:
+        e = AvtError((load_library().avt_last_error() or b"?").decode())
+        e.status = rc
+        raise e
+
+
 class ModelArrays:
     """Host arrays in the layout avt_model_desc wants, built from SMPL-npz-style arrays
     (AvatarModel.cpp:26-104: v_template (V,3), f (F,3), kintree_table (2,J), J_regressor (J,V),
@@ -183,6 +200,82 @@ class ModelArrays:
         return d
 
 
+_vp = C.c_void_p
+# argument types of every exported function of include/avt.h and include/avt_shard.h (restype: load_library)
+SIGNATURES = {
+    "avt_options_default": [C.POINTER(Options)],
+    "avt_options_fixed_factors": [C.POINTER(Options)],
+    "avt_model_create": [C.POINTER(ModelDesc), C.POINTER(_vp)],
+    "avt_model_destroy": [_vp],
+    "avt_model_dims": [_vp, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p],
+    "avt_model_main_joint": [_vp, c_int_p],
+    "avt_model_joint_regression": [_vp, c_double_p, c_double_p],
+    "avt_model_tile_layout": [_vp, c_int_p, c_int_p, C.POINTER(C.c_ushort), c_int_p],
+    "avt_ctx_create": [C.c_int, _vp, C.c_int, c_int_p, C.c_int, C.c_int, C.POINTER(_vp)],
+    "avt_ctx_destroy": [_vp],
+    "avt_sync": [_vp],
+    "avt_lbs_update": [_vp, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p],
+    "avt_visibility": [_vp, c_double_p, C.c_int, c_ubyte_p],
+    "avt_nn": [_vp, c_double_p, c_ubyte_p, c_double_p, c_int_p, C.c_int, c_int_p],
+    "avt_optimize": [_vp, c_double_p, c_int_p, C.c_int, C.POINTER(Options), c_double_p, c_double_p, c_double_p,
+                     C.POINTER(Stats)],
+    "avt_optimize_posed": [_vp, c_double_p, c_int_p, C.c_int, C.POINTER(Options), c_double_p, c_double_p, c_double_p, C.POINTER(Stats),
+                           c_double_p, c_double_p, c_double_p],
+    "avt_optimize_batch": [_vp, C.c_int, c_double_p, c_int_p, c_int_p, C.POINTER(Options), c_double_p, c_double_p,
+                           c_double_p, C.POINTER(Stats)],
+    "avt_frames_upload": [_vp, C.c_int, c_double_p, c_int_p, c_int_p],
+    "avt_synth_render_frames": [_vp, C.c_int, c_double_p, c_double_p, c_double_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, c_int_p],
+    "avt_synth_render_frames_mode": [_vp, C.c_int, c_double_p, c_double_p, c_double_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int,
+                                     C.c_int, c_int_p],
+    "avt_synth_render_images": [_vp, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_ubyte)],
+    "avt_frames_download": [_vp, C.c_int, c_double_p, c_int_p],
+    "avt_state_upload": [_vp, C.c_int, c_double_p, c_double_p, c_double_p],
+    "avt_optimize_resident": [_vp, C.POINTER(Options)],
+    "avt_optimize_resident_budgets": [_vp, C.POINTER(Options), c_int_p],
+    "avt_state_upload_frames": [_vp, C.c_int, c_int_p, c_double_p, c_double_p, c_double_p],
+    "avt_state_reset": [_vp],
+    "avt_state_download": [_vp, c_double_p, c_double_p, c_double_p, C.POINTER(Stats)],
+    "avt_get_correspondences": [_vp, C.c_int, c_int_p],
+    "avt_get_cloud": [_vp, C.c_int, c_double_p],
+    "avt_get_posed": [_vp, C.c_int, c_double_p, c_double_p, c_double_p],
+    "avt_get_normal_equations": [_vp, C.c_int, c_double_p, c_double_p, c_double_p],
+    "avt_ctx_get_tuning": [_vp, C.POINTER(Tuning)],
+    "avt_ctx_set_tuning": [_vp, C.POINTER(Tuning)],
+    "avt_set_data_term": [_vp, C.c_int],
+    "avt_get_data_term": [_vp],
+    "avt_debug_trace": [_vp, C.c_int, c_double_p],
+    "avt_debug_mfma_count": [_vp, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)],
+    "avt_launch_shape": [_vp, c_int_p, c_int_p, c_int_p],
+    "avt_profile_begin": [_vp],
+    "avt_profile_select": [_vp, C.c_uint],
+    "avt_profile_end": [_vp, C.POINTER(Profile)],
+    # include/avt_shard.h
+    "avt_shard_owner": [C.c_int, C.c_int],
+    "avt_shard_local_count": [C.c_int, C.c_int, C.c_int],
+    "avt_shard_local_index": [C.c_int, C.c_int],
+    "avt_shard_global_frame": [C.c_int, C.c_int, C.c_int],
+    "avt_model_pack_size": [C.POINTER(ModelDesc), C.POINTER(C.c_size_t)],
+    "avt_model_pack": [C.POINTER(ModelDesc), _vp, C.c_size_t],
+    "avt_model_unpack": [_vp, C.c_size_t, C.POINTER(_vp)],
+    "avt_shard_unique_id": [C.c_char_p],
+    "avt_shard_create": [C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(_vp)],
+    "avt_shard_create_loopback": [C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(_vp)],
+    "avt_shard_create_shm": [C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(_vp)],
+    "avt_shard_destroy": [_vp],
+    "avt_shard_rank": [_vp],
+    "avt_shard_world": [_vp],
+    "avt_shard_backend": [_vp],
+    "avt_shard_broadcast_model": [_vp, C.c_int, C.POINTER(ModelDesc), C.POINTER(_vp)],
+    "avt_shard_scatter_frames": [_vp, _vp, C.c_int, C.c_int, c_double_p, c_int_p, c_int_p, c_double_p, c_double_p, c_double_p],
+    "avt_shard_gather_enqueue": [_vp, _vp, C.c_int],
+    "avt_shard_gather_wait": [_vp],
+    "avt_shard_gather_download": [_vp, _vp, C.c_int, c_double_p, c_double_p, c_double_p, C.POINTER(Stats)],
+    "avt_shard_gather_results": [_vp, _vp, C.c_int, c_double_p, c_double_p, c_double_p, C.POINTER(Stats)],
+    "avt_shard_set_self_exchange": [_vp, C.c_int],
+    "avt_shard_barrier": [_vp, _vp],
+}
+EXPORTED_SYMBOLS = ["avt_last_error", "avt_kernel_name"] + list(SIGNATURES)
+
 _lib = None
 
 
@@ -203,98 +296,15 @@ def load_library():
     lib.avt_last_error.restype = C.c_char_p
     lib.avt_kernel_name.restype = C.c_char_p
     lib.avt_kernel_name.argtypes = [C.c_int]
-    vp = C.c_void_p
-    sigs = {
-        "avt_options_default": [C.POINTER(Options)],
-        "avt_model_create": [C.POINTER(ModelDesc), C.POINTER(vp)],
-        "avt_model_destroy": [vp],
-        "avt_model_dims": [vp, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p],
-        "avt_model_main_joint": [vp, c_int_p],
-        "avt_model_joint_regression": [vp, c_double_p, c_double_p],
-        "avt_model_tile_layout": [vp, c_int_p, c_int_p, C.POINTER(C.c_ushort), c_int_p],
-        "avt_ctx_create": [C.c_int, vp, C.c_int, c_int_p, C.c_int, C.c_int, C.POINTER(vp)],
-        "avt_ctx_destroy": [vp],
-        "avt_sync": [vp],
-        "avt_lbs_update": [vp, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p],
-        "avt_visibility": [vp, c_double_p, C.c_int, c_ubyte_p],
-        "avt_nn": [vp, c_double_p, c_ubyte_p, c_double_p, c_int_p, C.c_int, c_int_p],
-        "avt_optimize": [vp, c_double_p, c_int_p, C.c_int, C.POINTER(Options), c_double_p, c_double_p, c_double_p,
-                         C.POINTER(Stats)],
-        "avt_optimize_batch": [vp, C.c_int, c_double_p, c_int_p, c_int_p, C.POINTER(Options), c_double_p, c_double_p,
-                               c_double_p, C.POINTER(Stats)],
-        "avt_frames_upload": [vp, C.c_int, c_double_p, c_int_p, c_int_p],
-        "avt_synth_render_frames": [vp, C.c_int, c_double_p, c_double_p, c_double_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, c_int_p],
-        "avt_synth_render_frames_mode": [vp, C.c_int, c_double_p, c_double_p, c_double_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int,
-                                         C.c_int, c_int_p],
-        "avt_synth_render_images": [vp, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_ubyte)],
-        "avt_frames_download": [vp, C.c_int, c_double_p, c_int_p],
-        "avt_state_upload": [vp, C.c_int, c_double_p, c_double_p, c_double_p],
-        "avt_optimize_resident": [vp, C.POINTER(Options)],
-        "avt_optimize_resident_budgets": [vp, C.POINTER(Options), c_int_p],
-        "avt_state_upload_frames": [vp, C.c_int, c_int_p, c_double_p, c_double_p, c_double_p],
-        "avt_state_reset": [vp],
-        "avt_state_download": [vp, c_double_p, c_double_p, c_double_p, C.POINTER(Stats)],
-        "avt_get_correspondences": [vp, C.c_int, c_int_p],
-        "avt_get_cloud": [vp, C.c_int, c_double_p],
-        "avt_get_posed": [vp, C.c_int, c_double_p, c_double_p, c_double_p],
-        "avt_get_normal_equations": [vp, C.c_int, c_double_p, c_double_p, c_double_p],
-        "avt_ctx_get_tuning": [vp, C.POINTER(Tuning)],
-        "avt_ctx_set_tuning": [vp, C.POINTER(Tuning)],
-        "avt_set_data_term": [vp, C.c_int],
-        "avt_get_data_term": [vp],
-        "avt_debug_trace": [vp, C.c_int, c_double_p],
-        "avt_debug_mfma_count": [vp, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)],
-        "avt_launch_shape": [vp, c_int_p, c_int_p, c_int_p],
-        "avt_profile_begin": [vp],
-        "avt_profile_select": [vp, C.c_uint],
-        "avt_profile_end": [vp, C.POINTER(Profile)],
-        # include/avt_shard.h
-        "avt_shard_owner": [C.c_int, C.c_int],
-        "avt_shard_local_count": [C.c_int, C.c_int, C.c_int],
-        "avt_shard_local_index": [C.c_int, C.c_int],
-        "avt_shard_global_frame": [C.c_int, C.c_int, C.c_int],
-        "avt_model_pack_size": [C.POINTER(ModelDesc), C.POINTER(C.c_size_t)],
-        "avt_model_pack": [C.POINTER(ModelDesc), vp, C.c_size_t],
-        "avt_model_unpack": [vp, C.c_size_t, C.POINTER(vp)],
-        "avt_shard_unique_id": [C.c_char_p],
-        "avt_shard_create": [C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(vp)],
-        "avt_shard_create_loopback": [C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(vp)],
-        "avt_shard_create_shm": [C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(vp)],
-        "avt_shard_destroy": [vp],
-        "avt_shard_rank": [vp],
-        "avt_shard_world": [vp],
-        "avt_shard_backend": [vp],
-        "avt_shard_broadcast_model": [vp, C.c_int, C.POINTER(ModelDesc), C.POINTER(vp)],
-        "avt_shard_scatter_frames": [vp, vp, C.c_int, C.c_int, c_double_p, c_int_p, c_int_p, c_double_p, c_double_p, c_double_p],
-        "avt_shard_gather_enqueue": [vp, vp, C.c_int],
-        "avt_shard_gather_wait": [vp],
-        "avt_shard_gather_download": [vp, vp, C.c_int, c_double_p, c_double_p, c_double_p, C.POINTER(Stats)],
-        "avt_shard_gather_results": [vp, vp, C.c_int, c_double_p, c_double_p, c_double_p, C.POINTER(Stats)],
-        "avt_shard_barrier": [vp, vp],
-    }
-    for name, args in sigs.items():
+    for name, args in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
         fn.argtypes = args
         if name == "avt_shard_backend":
             fn.restype = C.c_char_p
-        elif name not in ("avt_model_destroy", "avt_ctx_destroy", "avt_options_default", "avt_shard_destroy"):
+        elif name not in ("avt_model_destroy", "avt_ctx_destroy", "avt_options_default", "avt_options_fixed_factors", "avt_shard_destroy"):
             fn.restype = C.c_int
         else:
             fn.restype = None
     _lib = lib
     return lib
 
-
-EXPORTED_SYMBOLS = [
-    "avt_last_error", "avt_kernel_name", "avt_options_default", "avt_options_fixed_factors", "avt_model_create", "avt_model_destroy",
-    "avt_model_dims", "avt_model_main_joint", "avt_model_joint_regression", "avt_model_tile_layout", "avt_ctx_create", "avt_ctx_destroy",
-    "avt_sync", "avt_lbs_update", "avt_visibility", "avt_nn", "avt_optimize", "avt_optimize_posed", "avt_optimize_batch",
-    "avt_frames_upload", "avt_synth_render_frames", "avt_synth_render_frames_mode", "avt_synth_render_images", "avt_frames_download", "avt_state_upload", "avt_optimize_resident", "avt_state_reset", "avt_state_download",
-    "avt_optimize_resident_budgets", "avt_state_upload_frames",
-    "avt_get_correspondences", "avt_get_cloud", "avt_get_posed", "avt_get_normal_equations", "avt_ctx_get_tuning", "avt_ctx_set_tuning", "avt_set_data_term", "avt_get_data_term", "avt_debug_trace", "avt_debug_mfma_count", "avt_launch_shape", "avt_profile_begin", "avt_profile_select", "avt_profile_end",
-    # include/avt_shard.h
-    "avt_shard_owner", "avt_shard_local_count", "avt_shard_local_index", "avt_shard_global_frame", "avt_model_pack_size", "avt_model_pack",
-    "avt_model_unpack", "avt_shard_unique_id", "avt_shard_create", "avt_shard_create_loopback", "avt_shard_create_shm", "avt_shard_destroy", "avt_shard_rank", "avt_shard_world", "avt_shard_backend",
-    "avt_shard_broadcast_model", "avt_shard_scatter_frames", "avt_shard_gather_enqueue", "avt_shard_gather_wait", "avt_shard_gather_download",
-    "avt_shard_gather_results", "avt_shard_barrier", "avt_shard_set_self_exchange",
-]

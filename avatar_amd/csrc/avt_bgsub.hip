@@ -22,7 +22,6 @@
 #include <algorithm>
 #include <climits>
 #include <cstddef>
-#include <exception>
 #include <string>
 #include <vector>
 
@@ -47,21 +46,19 @@ struct BgsInfo {               // per image, device resident
 struct avt_bgsub {
     int device = 0, n_bg = 0, rows = 0, cols = 0;
     hipStream_t stream = nullptr;
-    float* d_bg = nullptr;                 // n_bg x N x 3
-    float* d_img = nullptr;                // cap x N x 3
-    int* d_bgidx = nullptr;                // cap
-    int* d_label = nullptr;                // cap x N: parent / root index, -1 not a candidate
-    int* d_count = nullptr;                // cap x N: size at a root; after k_bgs_ids -1 - code at a kept root
-    unsigned char* d_mask = nullptr;       // cap x N
-    float* d_depth = nullptr;              // cap x N
-    BgsInfo* d_info = nullptr;             // cap
-    unsigned* d_fault = nullptr;           // sticky fault word of the handle
-    int cap = 0, n_images = 0;
+    DevBuf<float> d_bg;                    // n_bg x N x 3
+    DevBuf<float> d_img;                   // cap x N x 3, cap = d_info.cap images (reserve() grows d_info last)
+    DevBuf<int> d_bgidx;                   // cap
+    DevBuf<int> d_label;                   // cap x N: parent / root index, -1 not a candidate
+    DevBuf<int> d_count;                   // cap x N: size at a root; after k_bgs_ids -1 - code at a kept root
+    DevBuf<unsigned char> d_mask;          // cap x N
+    DevBuf<float> d_depth;                 // cap x N
+    DevBuf<BgsInfo> d_info;                // cap
+    DevBuf<unsigned> d_fault;              // sticky fault word of the handle
+    int n_images = 0;
 };
 
 namespace {
-
-#define BG_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { avt_set_error(std::string(#x) + ": " + hipGetErrorString(e_)); return 1; } } while (0)
 
 __device__ __forceinline__ float sqdist(float a0, float a1, float a2, float b0, float b1, float b2) {
     const float d0 = a0 - b0, d1 = a1 - b1, d2 = a2 - b2;
@@ -352,32 +349,29 @@ __global__ __launch_bounds__(256) void k_bgs_depth(const float* __restrict__ img
 }
 
 int reserve(avt_bgsub* bg, int n) {
-    if (n <= bg->cap) return 0;
-    BG_HIP(hipStreamSynchronize(bg->stream));
+    // d_info stands for the whole group: it grows last, and it is released when anything below fails, so that a call after
+    // a failure allocates again whatever is missing (and, as ever after a failure, every slot starts at cv::Point())
+    const size_t old = bg->d_info.cap;             // slots whose boxes carry over
+    if ((size_t)n <= old) return 0;
+    AVT_HIP(hipStreamSynchronize(bg->stream));
     const size_t N = (size_t)bg->rows * bg->cols;
-    const int old = bg->d_info ? bg->cap : 0;      // slots whose boxes carry over
-    (void)hipFree(bg->d_img); (void)hipFree(bg->d_bgidx); (void)hipFree(bg->d_label); (void)hipFree(bg->d_count);
-    (void)hipFree(bg->d_mask); (void)hipFree(bg->d_depth);
-    bg->d_img = nullptr; bg->d_bgidx = nullptr; bg->d_label = nullptr; bg->d_count = nullptr; bg->d_mask = nullptr;
-    bg->d_depth = nullptr; bg->cap = 0; bg->n_images = 0;
-    BG_HIP(hipMalloc((void**)&bg->d_img, (size_t)n * N * 3 * sizeof(float)));
-    BG_HIP(hipMalloc((void**)&bg->d_bgidx, (size_t)n * sizeof(int)));
-    BG_HIP(hipMalloc((void**)&bg->d_label, (size_t)n * N * sizeof(int)));
-    BG_HIP(hipMalloc((void**)&bg->d_count, (size_t)n * N * sizeof(int)));
-    BG_HIP(hipMalloc((void**)&bg->d_mask, (size_t)n * N));
-    BG_HIP(hipMalloc((void**)&bg->d_depth, (size_t)n * N * sizeof(float)));
-    // the slots the handle had keep their previous boxes (avt_bgsub.h: a batch without prev_boxes uses them); only the
-    // new slots start at cv::Point()
-    BgsInfo* info = nullptr;
-    BG_HIP(hipMalloc((void**)&info, (size_t)n * sizeof(BgsInfo)));
-    hipError_t e = hipMemsetAsync(info + old, 0, (size_t)(n - old) * sizeof(BgsInfo), bg->stream);
-    if (e == hipSuccess && old) e = hipMemcpyAsync(info, bg->d_info, (size_t)old * sizeof(BgsInfo), hipMemcpyDeviceToDevice, bg->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(bg->stream);                         // before the old array is freed
-    if (e != hipSuccess) { (void)hipFree(info); BG_HIP(e); }
-    (void)hipFree(bg->d_info);
-    bg->d_info = info;
-    bg->cap = n;
-    return 0;
+    bg->n_images = 0;
+    const int rc = [&]() -> int {
+        if (bg->d_img.reserve(n * N * 3)) return 1;
+        if (bg->d_bgidx.reserve(n)) return 1;
+        if (bg->d_label.reserve(n * N)) return 1;
+        if (bg->d_count.reserve(n * N)) return 1;
+        if (bg->d_mask.reserve(n * N)) return 1;
+        if (bg->d_depth.reserve(n * N)) return 1;
+        // the slots the handle had keep their previous boxes (avt_bgsub.h: a batch without prev_boxes uses them); only the
+        // new slots start at cv::Point()
+        if (bg->d_info.grow(n, old, bg->stream, false)) return 1;
+        AVT_HIP(hipMemsetAsync(bg->d_info + old, 0, (n - old) * sizeof(BgsInfo), bg->stream));
+        AVT_HIP(hipStreamSynchronize(bg->stream));
+        return 0;
+    }();
+    if (rc) bg->d_info.release();
+    return rc;
 }
 
 // the reference's threshold (BGSubtractor.cpp:160-161): int pixel count, double arithmetic, rounded to float by ffill's parameter
@@ -385,11 +379,11 @@ float thresh(int rows, int cols, float rel) { return (float)(1200000.0 / (rows *
 
 int check_fault(avt_bgsub* bg) {
     unsigned f = 0;
-    BG_HIP(hipMemcpyAsync(&f, bg->d_fault, sizeof(unsigned), hipMemcpyDeviceToHost, bg->stream));
-    BG_HIP(hipStreamSynchronize(bg->stream));
+    AVT_HIP(hipMemcpyAsync(&f, bg->d_fault, sizeof(unsigned), hipMemcpyDeviceToHost, bg->stream));
+    AVT_HIP(hipStreamSynchronize(bg->stream));
     if (!f) return 0;
-    BG_HIP(hipMemsetAsync(bg->d_fault, 0, sizeof(unsigned), bg->stream));
-    BG_HIP(hipStreamSynchronize(bg->stream));
+    AVT_HIP(hipMemsetAsync(bg->d_fault, 0, sizeof(unsigned), bg->stream));
+    AVT_HIP(hipStreamSynchronize(bg->stream));
     avt_set_error("avt_bgsub: a kernel ran out of a bounded retry (fault word " + std::to_string(f) + "); the result is not valid");
     return AVT_STATUS_DEVICE_FAULT;
 }
@@ -399,13 +393,12 @@ int create_impl(int device, int n_bg, int rows, int cols, const float* backgroun
         avt_set_error("avt_bgsub_create: bad arguments (rows, cols > 0, cols < 65536, n_backgrounds > 0)");
         return 1;
     }
-    BG_HIP(hipSetDevice(device));
+    AVT_HIP(hipSetDevice(device));
     avt_bgsub* bg = new avt_bgsub();
     bg->device = device; bg->n_bg = n_bg; bg->rows = rows; bg->cols = cols;
-    const size_t bytes = (size_t)n_bg * rows * cols * 3 * sizeof(float);
+    const size_t floats = (size_t)n_bg * rows * cols * 3, bytes = floats * sizeof(float);
     auto fail = [&]() { avt_bgsub_destroy(bg); return 1; };
-    if (hipStreamCreateWithFlags(&bg->stream, hipStreamNonBlocking) != hipSuccess || hipMalloc((void**)&bg->d_bg, bytes) != hipSuccess ||
-        hipMalloc((void**)&bg->d_fault, sizeof(unsigned)) != hipSuccess) {
+    if (hipStreamCreateWithFlags(&bg->stream, hipStreamNonBlocking) != hipSuccess || bg->d_bg.reserve(floats) || bg->d_fault.reserve(1)) {
         avt_set_error("avt_bgsub_create: device allocation failed");
         return fail();
     }
@@ -420,10 +413,10 @@ int create_impl(int device, int n_bg, int rows, int cols, const float* backgroun
 
 int set_background_impl(avt_bgsub* bg, int index, const float* xyz) {
     if (!bg || !xyz || index < 0 || index >= bg->n_bg) { avt_set_error("avt_bgsub_set_background: bad arguments"); return 1; }
-    BG_HIP(hipSetDevice(bg->device));
+    AVT_HIP(hipSetDevice(bg->device));
     const size_t n = (size_t)bg->rows * bg->cols * 3;
-    BG_HIP(hipMemcpyAsync(bg->d_bg + (size_t)index * n, xyz, n * sizeof(float), hipMemcpyHostToDevice, bg->stream));
-    BG_HIP(hipStreamSynchronize(bg->stream));
+    AVT_HIP(hipMemcpyAsync(bg->d_bg + (size_t)index * n, xyz, n * sizeof(float), hipMemcpyHostToDevice, bg->stream));
+    AVT_HIP(hipStreamSynchronize(bg->stream));
     return 0;
 }
 
@@ -434,21 +427,21 @@ int upload_impl(avt_bgsub* bg, int n, const float* images, const int* bg_index, 
         idx[i] = bg_index ? bg_index[i] : i;
         if (idx[i] < 0 || idx[i] >= bg->n_bg) { avt_set_error("avt_bgsub_images_upload: background index out of range"); return 1; }
     }
-    BG_HIP(hipSetDevice(bg->device));
+    AVT_HIP(hipSetDevice(bg->device));
     if (reserve(bg, n)) return 1;
     const size_t N = (size_t)bg->rows * bg->cols;
-    BG_HIP(hipMemcpyAsync(bg->d_img, images, (size_t)n * N * 3 * sizeof(float), hipMemcpyHostToDevice, bg->stream));
-    BG_HIP(hipMemcpyAsync(bg->d_bgidx, idx.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, bg->stream));
+    AVT_HIP(hipMemcpyAsync(bg->d_img, images, (size_t)n * N * 3 * sizeof(float), hipMemcpyHostToDevice, bg->stream));
+    AVT_HIP(hipMemcpyAsync(bg->d_bgidx, idx.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, bg->stream));
     if (prev_boxes)
-        for (int i = 0; i < n; ++i) BG_HIP(hipMemcpyAsync(bg->d_info[i].box, prev_boxes + 4 * (size_t)i, 4 * sizeof(int), hipMemcpyHostToDevice, bg->stream));
-    BG_HIP(hipStreamSynchronize(bg->stream));     // idx is on this stack frame
+        for (int i = 0; i < n; ++i) AVT_HIP(hipMemcpyAsync(bg->d_info[i].box, prev_boxes + 4 * (size_t)i, 4 * sizeof(int), hipMemcpyHostToDevice, bg->stream));
+    AVT_HIP(hipStreamSynchronize(bg->stream));     // idx is on this stack frame
     bg->n_images = n;
     return 0;
 }
 
 int run_resident_impl(avt_bgsub* bg, float nn_rel, float neighb_rel) {
     if (!bg || bg->n_images <= 0) { avt_set_error("avt_bgsub_run_resident: no images resident"); return 1; }
-    BG_HIP(hipSetDevice(bg->device));
+    AVT_HIP(hipSetDevice(bg->device));
     const int rows = bg->rows, cols = bg->cols, n = bg->n_images, npix = rows * cols;
     const float nn = thresh(rows, cols, nn_rel), nb = thresh(rows, cols, neighb_rel);
     const int min_pts = std::max(npix / 1000, 100);                                   // BGSubtractor.cpp:19
@@ -472,12 +465,12 @@ int run_resident_impl(avt_bgsub* bg, float nn_rel, float neighb_rel) {
 
 int download_impl(avt_bgsub* bg, int image, unsigned char* mask_out, float* depth_out, avt_bgsub_frame* info) {
     if (!bg || image < 0 || image >= bg->n_images) { avt_set_error("avt_bgsub_download: bad arguments"); return 1; }
-    BG_HIP(hipSetDevice(bg->device));
+    AVT_HIP(hipSetDevice(bg->device));
     const size_t N = (size_t)bg->rows * bg->cols;
-    if (mask_out) BG_HIP(hipMemcpyAsync(mask_out, bg->d_mask + image * N, N, hipMemcpyDeviceToHost, bg->stream));
-    if (depth_out) BG_HIP(hipMemcpyAsync(depth_out, bg->d_depth + image * N, N * sizeof(float), hipMemcpyDeviceToHost, bg->stream));
+    if (mask_out) AVT_HIP(hipMemcpyAsync(mask_out, bg->d_mask + image * N, N, hipMemcpyDeviceToHost, bg->stream));
+    if (depth_out) AVT_HIP(hipMemcpyAsync(depth_out, bg->d_depth + image * N, N * sizeof(float), hipMemcpyDeviceToHost, bg->stream));
     BgsInfo h;
-    BG_HIP(hipMemcpyAsync(&h, bg->d_info + image, offsetof(BgsInfo, list), hipMemcpyDeviceToHost, bg->stream));
+    AVT_HIP(hipMemcpyAsync(&h, bg->d_info + image, offsetof(BgsInfo, list), hipMemcpyDeviceToHost, bg->stream));
     if (int rc = check_fault(bg)) return rc;                                          // synchronises the stream
     if (info) {
         info->top_left[0] = h.box[0]; info->top_left[1] = h.box[1]; info->bot_right[0] = h.box[2]; info->bot_right[1] = h.box[3];
@@ -503,46 +496,42 @@ int run_impl(avt_bgsub* bg, int background_index, const float* xyz, float nn_rel
 }  // namespace
 
 // ---- exported entry points: no C++ exception crosses the C ABI
-#define BG_ENTRY(name, call)                                                                       \
-    try { return call; }                                                                           \
-    catch (const std::exception& e) { avt_set_error(std::string(name ": ") + e.what()); return 1; } \
-    catch (...) { avt_set_error(name ": unknown exception"); return 1; }
-
 extern "C" {
 int avt_bgsub_create(int device, int n_backgrounds, int rows, int cols, const float* backgrounds, avt_bgsub** out) {
-    BG_ENTRY("avt_bgsub_create", create_impl(device, n_backgrounds, rows, cols, backgrounds, out))
+    return avt_guard("avt_bgsub_create", [&]() -> int { return create_impl(device, n_backgrounds, rows, cols, backgrounds, out); });
 }
 
 void avt_bgsub_destroy(avt_bgsub* bg) {
     if (!bg) return;
     if (bg->stream) (void)hipStreamSynchronize(bg->stream);
-    for (void* p : {(void*)bg->d_bg, (void*)bg->d_img, (void*)bg->d_bgidx, (void*)bg->d_label, (void*)bg->d_count, (void*)bg->d_mask,
-                    (void*)bg->d_depth, (void*)bg->d_info, (void*)bg->d_fault})
-        if (p) (void)hipFree(p);
+    // the buffers go with `delete`, after the stream: it has just been drained, so nothing is queued on them either way
     if (bg->stream) (void)hipStreamDestroy(bg->stream);
     delete bg;
 }
 
-int avt_bgsub_set_background(avt_bgsub* bg, int index, const float* xyz) { BG_ENTRY("avt_bgsub_set_background", set_background_impl(bg, index, xyz)) }
+int avt_bgsub_set_background(avt_bgsub* bg, int index, const float* xyz) {
+    return avt_guard("avt_bgsub_set_background", [&]() -> int { return set_background_impl(bg, index, xyz); });
+}
 
 int avt_bgsub_run(avt_bgsub* bg, int background_index, const float* xyz, float nn_rel, float neighb_rel, unsigned char* mask_out,
                   float* masked_depth_out, avt_bgsub_frame* info) {
-    BG_ENTRY("avt_bgsub_run", run_impl(bg, background_index, xyz, nn_rel, neighb_rel, mask_out, masked_depth_out, info))
+    return avt_guard("avt_bgsub_run", [&]() -> int { return run_impl(bg, background_index, xyz, nn_rel, neighb_rel, mask_out, masked_depth_out, info); });
 }
 
 int avt_bgsub_images_upload(avt_bgsub* bg, int n_images, const float* images, const int* bg_index, const int* prev_boxes) {
-    BG_ENTRY("avt_bgsub_images_upload", upload_impl(bg, n_images, images, bg_index, prev_boxes))
+    return avt_guard("avt_bgsub_images_upload", [&]() -> int { return upload_impl(bg, n_images, images, bg_index, prev_boxes); });
 }
 
-int avt_bgsub_run_resident(avt_bgsub* bg, float nn_rel, float neighb_rel) { BG_ENTRY("avt_bgsub_run_resident", run_resident_impl(bg, nn_rel, neighb_rel)) }
+int avt_bgsub_run_resident(avt_bgsub* bg, float nn_rel, float neighb_rel) {
+    return avt_guard("avt_bgsub_run_resident", [&]() -> int { return run_resident_impl(bg, nn_rel, neighb_rel); });
+}
 
 int avt_bgsub_download(avt_bgsub* bg, int image, unsigned char* mask_out, float* masked_depth_out, avt_bgsub_frame* info) {
-    BG_ENTRY("avt_bgsub_download", download_impl(bg, image, mask_out, masked_depth_out, info))
+    return avt_guard("avt_bgsub_download", [&]() -> int { return download_impl(bg, image, mask_out, masked_depth_out, info); });
 }
 
 int avt_bgsub_sync(avt_bgsub* bg) {
     if (!bg) { avt_set_error("avt_bgsub_sync: null handle"); return 1; }
-    try { return check_fault(bg); }
-    catch (...) { avt_set_error("avt_bgsub_sync: unknown exception"); return 1; }
+    return avt_guard("avt_bgsub_sync", [&]() -> int { return check_fault(bg); });
 }
 }  // extern "C"

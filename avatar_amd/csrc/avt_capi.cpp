@@ -6,18 +6,11 @@
 #include <cstdlib>
 #include <cstring>
 
-#include <exception>
 #include <mutex>
 
 #include "avt_internal.h"
 
 static std::mutex g_graph_mutex;      // every hipGraph call of the process (see run_optimize)
-
-// No C++ exception may cross the C ABI: every entry point that allocates runs inside this guard.
-#define AVT_API_GUARD_BEGIN try {
-#define AVT_API_GUARD_END(fn)                                                                      \
-    } catch (const std::exception& e) { avt_set_error(std::string(fn) + ": " + e.what()); return 1; } \
-    catch (...) { avt_set_error(std::string(fn) + ": unknown exception"); return 1; }
 
 int avt_solve_set_attributes();
 int avt_eval_set_attributes();
@@ -28,21 +21,12 @@ int avt_paint_enqueue(avt_ctx* c, int nframes, const int* d_vertex_part, unsigne
                       double cy, int width, int height);
 void avt_eval_report_occupancy(const AvtDims& d);
 
-#define HIP_OK(expr)                                                                          \
-    do {                                                                                      \
-        hipError_t _e = (expr);                                                               \
-        if (_e != hipSuccess) {                                                               \
-            avt_set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                 \
-            return 1;                                                                         \
-        }                                                                                     \
-    } while (0)
-
 namespace {
 
 template <class T>
 int dev_alloc(avt_ctx* c, T** p, size_t n) {
     void* q = nullptr;
-    HIP_OK(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));
+    AVT_HIP(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));   // an empty table still gets a pointer the kernels may be handed
     c->allocs.push_back(q);
     *p = (T*)q;
     return 0;
@@ -52,8 +36,8 @@ int dev_upload(avt_ctx* c, T** p, const std::vector<T>& v) {
     if (dev_alloc(c, p, v.size())) return 1;
     // (never the legacy stream: another thread of the host may be capturing a graph, and the legacy stream synchronises with it)
     if (!v.empty()) {
-        HIP_OK(hipMemcpyAsync(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
+        AVT_HIP(hipMemcpyAsync(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, c->stream));
+        AVT_HIP(hipStreamSynchronize(c->stream));
     }
     return 0;
 }
@@ -260,8 +244,8 @@ int sync_params(avt_ctx* c, const avt_options* o) {
     pr.ftol = o->function_tolerance;
     if (c->params_valid && std::memcmp(&pr, &c->params_host, sizeof pr) == 0) return 0;
     c->params_host = pr;
-    HIP_OK(hipMemcpyAsync((void*)c->fb.params, &c->params_host, sizeof pr, hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));     // params_host may be rewritten by the next call
+    AVT_HIP(hipMemcpyAsync((void*)c->fb.params, &c->params_host, sizeof pr, hipMemcpyHostToDevice, c->stream));
+    AVT_HIP(hipStreamSynchronize(c->stream));     // params_host may be rewritten by the next call
     c->params_valid = true;
     return 0;
 }
@@ -333,7 +317,7 @@ int run_optimize(avt_ctx* c, const avt_options* o, const int* budget = nullptr) 
     if (!hit) {
         hipGraph_t graph = nullptr;
         hipGraphExec_t exec = nullptr;
-        HIP_OK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+        AVT_HIP(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
         bool bad = false;
         auto cap = [&](hipError_t e) { if (e != hipSuccess && !bad) { bad = true; avt_set_error(std::string("optimize graph capture: ") + hipGetErrorString(e)); } };
         if (ngroups > 1) {
@@ -364,7 +348,7 @@ int run_optimize(avt_ctx* c, const avt_options* o, const int* budget = nullptr) 
         if (c->graphs.size() >= GRAPH_CACHE_ENTRIES) {      // evict the least recently used launch shape
             size_t lru = 0;
             for (size_t i = 1; i < c->graphs.size(); ++i) if (c->graphs[i].last_used < c->graphs[lru].last_used) lru = i;
-            HIP_OK(hipStreamSynchronize(c->stream));
+            AVT_HIP(hipStreamSynchronize(c->stream));
             (void)hipGraphExecDestroy(c->graphs[lru].exec);
             c->graphs.erase(c->graphs.begin() + lru);
         }
@@ -372,7 +356,7 @@ int run_optimize(avt_ctx* c, const avt_options* o, const int* budget = nullptr) 
         hit = &c->graphs.back();
     }
     hit->last_used = ++c->graph_clock;
-    HIP_OK(hipGraphLaunch(hit->exec, c->stream));
+    AVT_HIP(hipGraphLaunch(hit->exec, c->stream));
     c->ran_icp_iters = o->icp_iters;
     note_products(c, o);
     return 0;
@@ -404,12 +388,12 @@ int install_frames(avt_ctx* c, int nframes, const int* counts, const double* dat
     for (int f = 0; f < nframes; ++f) {
         const size_t N = (size_t)counts[f], o = (size_t)c->frame_off[f];
         if (N == 0) continue;
-        HIP_OK(hipMemcpyAsync(c->fb.data_raw + (size_t)f * c->fb.max_points * 3, data + o * 3, N * 3 * sizeof(double), kind, c->stream));
-        HIP_OK(hipMemcpyAsync(c->fb.labels_raw + (size_t)f * c->fb.max_points, labels + o, N * sizeof(int), kind, c->stream));
+        AVT_HIP(hipMemcpyAsync(c->fb.data_raw + (size_t)f * c->fb.max_points * 3, data + o * 3, N * 3 * sizeof(double), kind, c->stream));
+        AVT_HIP(hipMemcpyAsync(c->fb.labels_raw + (size_t)f * c->fb.max_points, labels + o, N * sizeof(int), kind, c->stream));
     }
     for (AvtFrameCtl* dst : {c->fb.ctl, c->fb.ctl_start})
-        HIP_OK(hipMemcpy2DAsync(&dst->N, sizeof(AvtFrameCtl), c->frame_N.data(), sizeof(int), sizeof(int), (size_t)nframes, hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
+        AVT_HIP(hipMemcpy2DAsync(&dst->N, sizeof(AvtFrameCtl), c->frame_N.data(), sizeof(int), sizeof(int), (size_t)nframes, hipMemcpyHostToDevice, c->stream));
+    AVT_HIP(hipStreamSynchronize(c->stream));
     c->frames_valid = true;
     if (!same_shape) c->state_valid = false;     // a different number of frames needs a new start state
     return 0;
@@ -436,11 +420,11 @@ int upload_state(avt_ctx* c, int nframes, const double* p, const double* q, cons
         ctl[f].N = c->frame_N[f];
         ctl[f].comp_cur = -1;
     }
-    HIP_OK(hipMemcpyAsync(c->fb.x, xs.data(), xs.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemcpyAsync(c->fb.ctl, ctl.data(), ctl.size() * sizeof(AvtFrameCtl), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemcpyAsync(c->fb.x_start, c->fb.x, xs.size() * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    HIP_OK(hipMemcpyAsync(c->fb.ctl_start, c->fb.ctl, ctl.size() * sizeof(AvtFrameCtl), hipMemcpyDeviceToDevice, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));  // host vectors go out of scope
+    AVT_HIP(hipMemcpyAsync(c->fb.x, xs.data(), xs.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    AVT_HIP(hipMemcpyAsync(c->fb.ctl, ctl.data(), ctl.size() * sizeof(AvtFrameCtl), hipMemcpyHostToDevice, c->stream));
+    AVT_HIP(hipMemcpyAsync(c->fb.x_start, c->fb.x, xs.size() * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    AVT_HIP(hipMemcpyAsync(c->fb.ctl_start, c->fb.ctl, ctl.size() * sizeof(AvtFrameCtl), hipMemcpyDeviceToDevice, c->stream));
+    AVT_HIP(hipStreamSynchronize(c->stream));  // host vectors go out of scope
     c->state_valid = true;
     c->results_fresh = false;
     return 0;
@@ -451,19 +435,19 @@ int download_state(avt_ctx* c, double* p, double* q, double* w, avt_stats* st) {
     const int nf = c->nframes;
     std::vector<double> xs((size_t)nf * 2 * d.xsize);
     std::vector<AvtFrameCtl> ctl(nf);
-    HIP_OK(hipMemcpyAsync(xs.data(), c->fb.x, xs.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipMemcpyAsync(ctl.data(), c->fb.ctl, ctl.size() * sizeof(AvtFrameCtl), hipMemcpyDeviceToHost, c->stream));
+    AVT_HIP(hipMemcpyAsync(xs.data(), c->fb.x, xs.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    AVT_HIP(hipMemcpyAsync(ctl.data(), c->fb.ctl, ctl.size() * sizeof(AvtFrameCtl), hipMemcpyDeviceToHost, c->stream));
     std::vector<unsigned> fault(nf, 0u);
-    HIP_OK(hipMemcpyAsync(fault.data(), c->fb.fault, fault.size() * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
+    AVT_HIP(hipMemcpyAsync(fault.data(), c->fb.fault, fault.size() * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    AVT_HIP(hipStreamSynchronize(c->stream));
     int bad = -1, nbad = 0;
     for (int f = 0; f < nf; ++f) if (fault[f]) { if (bad < 0) bad = f; ++nbad; }
     if (bad >= 0) {     // reported once, then cleared: the next optimize() starts clean
         char msg[256];
         snprintf(msg, sizeof msg, "optimize: %d frame(s) carry a device fault (first: frame %d, bits 0x%x%s); their result is not valid", nbad, bad,
                  fault[bad], (fault[bad] & AVT_FAULT_RIDE_TIMEOUT) ? ": a solver gave up waiting for the in-launch reduction" : "");
-        HIP_OK(hipMemsetAsync(c->fb.fault, 0, (size_t)c->fb.max_frames * sizeof(unsigned), c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
+        AVT_HIP(hipMemsetAsync(c->fb.fault, 0, (size_t)c->fb.max_frames * sizeof(unsigned), c->stream));
+        AVT_HIP(hipStreamSynchronize(c->stream));
         c->results_fresh = false;      //  the result records carry the word that was just cleared: a later gather packs them again
         avt_set_error(msg);
         return AVT_STATUS_DEVICE_FAULT;
@@ -515,11 +499,11 @@ int optimize_host_to_host(avt_ctx* c, int nframes, const double* data, const int
     //  the pinned block grows with the largest call and shrinks again when a call needs less than a quarter of it: a tracker that once
     // fitted a dense 512-frame batch does not keep gigabytes pinned for its one-frame calls
     if (c->host_pin_cap < need || (c->host_pin_cap > (64u << 20) && need < c->host_pin_cap / 4)) {
-        HIP_OK(hipStreamSynchronize(c->stream));
+        AVT_HIP(hipStreamSynchronize(c->stream));
         if (c->host_pin) (void)hipHostFree(c->host_pin);
         c->host_pin = nullptr; c->host_pin_cap = 0;
         const size_t cap = need + need / 4;
-        HIP_OK(hipHostMalloc((void**)&c->host_pin, cap, hipHostMallocDefault));
+        AVT_HIP(hipHostMalloc((void**)&c->host_pin, cap, hipHostMallocDefault));
         c->host_pin_cap = cap;
     }
     char* pin = c->host_pin;
@@ -547,30 +531,30 @@ int optimize_host_to_host(avt_ctx* c, int nframes, const double* data, const int
     for (int f = 0; f < nframes; ++f) {
         const size_t N = (size_t)c->frame_N[f], off = (size_t)c->frame_off[f];
         if (N == 0) continue;
-        HIP_OK(hipMemcpyAsync(c->fb.data_raw + (size_t)f * c->fb.max_points * 3, h_data + off * 3, N * 24, hipMemcpyHostToDevice, c->stream));
-        HIP_OK(hipMemcpyAsync(c->fb.labels_raw + (size_t)f * c->fb.max_points, h_lab + off, N * 4, hipMemcpyHostToDevice, c->stream));
+        AVT_HIP(hipMemcpyAsync(c->fb.data_raw + (size_t)f * c->fb.max_points * 3, h_data + off * 3, N * 24, hipMemcpyHostToDevice, c->stream));
+        AVT_HIP(hipMemcpyAsync(c->fb.labels_raw + (size_t)f * c->fb.max_points, h_lab + off, N * 4, hipMemcpyHostToDevice, c->stream));
     }
     if (nframes == c->fb.max_frames) {      // [x | ctl] and [x_start | ctl_start] are contiguous on the device as they are in the pinned block
-        HIP_OK(hipMemcpyAsync(c->fb.x, h_x, b_x + b_ctl, hipMemcpyHostToDevice, c->stream));
-        HIP_OK(hipMemcpyAsync(c->fb.x_start, h_x, b_x + b_ctl, hipMemcpyHostToDevice, c->stream));
+        AVT_HIP(hipMemcpyAsync(c->fb.x, h_x, b_x + b_ctl, hipMemcpyHostToDevice, c->stream));
+        AVT_HIP(hipMemcpyAsync(c->fb.x_start, h_x, b_x + b_ctl, hipMemcpyHostToDevice, c->stream));
     } else {
-        HIP_OK(hipMemcpyAsync(c->fb.x, h_x, b_x, hipMemcpyHostToDevice, c->stream));
-        HIP_OK(hipMemcpyAsync(c->fb.ctl, h_ctl, b_ctl, hipMemcpyHostToDevice, c->stream));
-        HIP_OK(hipMemcpyAsync(c->fb.x_start, c->fb.x, b_x, hipMemcpyDeviceToDevice, c->stream));
-        HIP_OK(hipMemcpyAsync(c->fb.ctl_start, c->fb.ctl, b_ctl, hipMemcpyDeviceToDevice, c->stream));
+        AVT_HIP(hipMemcpyAsync(c->fb.x, h_x, b_x, hipMemcpyHostToDevice, c->stream));
+        AVT_HIP(hipMemcpyAsync(c->fb.ctl, h_ctl, b_ctl, hipMemcpyHostToDevice, c->stream));
+        AVT_HIP(hipMemcpyAsync(c->fb.x_start, c->fb.x, b_x, hipMemcpyDeviceToDevice, c->stream));
+        AVT_HIP(hipMemcpyAsync(c->fb.ctl_start, c->fb.ctl, b_ctl, hipMemcpyDeviceToDevice, c->stream));
     }
     c->frames_valid = c->state_valid = true;
     c->results_fresh = false;
     if (run_optimize(c, o)) { c->results_fresh = false; return 1; }
     if (!c->results_fresh) { launch_pack_results(c, nframes, c->fb.results, stride); c->results_fresh = true; }      // (a call without ICP iterations has no closing k_lbs launch)
-    HIP_OK(hipMemcpyAsync(h_res, c->fb.results, b_res, hipMemcpyDeviceToHost, c->stream));
+    AVT_HIP(hipMemcpyAsync(h_res, c->fb.results, b_res, hipMemcpyDeviceToHost, c->stream));
     double* h_posed = (double*)(pin + b_data + b_lab + b_x + b_ctl + b_res);
     if (want_posed) {      // frame 0's posed outputs into the pinned block, behind the fit, in front of the one synchronisation
-        HIP_OK(hipMemcpyAsync(h_posed, c->fb.cloud, (size_t)3 * d.V * 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipMemcpyAsync(h_posed + 3 * d.V, c->fb.jointpos, (size_t)3 * d.J * 8, hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipMemcpyAsync(h_posed + 3 * d.V + 3 * d.J, c->fb.jointtrans, (size_t)12 * d.J * 8, hipMemcpyDeviceToHost, c->stream));
+        AVT_HIP(hipMemcpyAsync(h_posed, c->fb.cloud, (size_t)3 * d.V * 8, hipMemcpyDeviceToHost, c->stream));
+        AVT_HIP(hipMemcpyAsync(h_posed + 3 * d.V, c->fb.jointpos, (size_t)3 * d.J * 8, hipMemcpyDeviceToHost, c->stream));
+        AVT_HIP(hipMemcpyAsync(h_posed + 3 * d.V + 3 * d.J, c->fb.jointtrans, (size_t)12 * d.J * 8, hipMemcpyDeviceToHost, c->stream));
     }
-    HIP_OK(hipStreamSynchronize(c->stream));      // the one synchronisation of the call
+    AVT_HIP(hipStreamSynchronize(c->stream));      // the one synchronisation of the call
     int bad = -1, nbad = 0;
     unsigned badbits = 0;
     for (int f = 0; f < nframes; ++f) {
@@ -581,8 +565,8 @@ int optimize_host_to_host(avt_ctx* c, int nframes, const double* data, const int
         char msg[256];
         snprintf(msg, sizeof msg, "optimize: %d frame(s) carry a device fault (first: frame %d, bits 0x%x%s); their result is not valid", nbad, bad,
                  badbits, (badbits & AVT_FAULT_RIDE_TIMEOUT) ? ": a solver gave up waiting for the in-launch reduction" : "");
-        HIP_OK(hipMemsetAsync(c->fb.fault, 0, (size_t)c->fb.max_frames * sizeof(unsigned), c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
+        AVT_HIP(hipMemsetAsync(c->fb.fault, 0, (size_t)c->fb.max_frames * sizeof(unsigned), c->stream));
+        AVT_HIP(hipStreamSynchronize(c->stream));
         c->results_fresh = false;      //  the records carry the word that was just cleared: a later gather packs them again
         avt_set_error(msg);
         return AVT_STATUS_DEVICE_FAULT;
@@ -624,7 +608,7 @@ static int ctx_create_impl(int device, const avt_model* m, int num_parts, const 
         return 2;
     }
     if (device < 0 || device >= ndev) { avt_set_error("avt_ctx_create: device index out of range"); return 1; }
-    HIP_OK(hipSetDevice(device));
+    AVT_HIP(hipSetDevice(device));
     avt_ctx* c = new avt_ctx();     // value-initialised: every handle starts null, avt_ctx_destroy copes with a partial context
     *out = c;
     c->device = device;
@@ -649,15 +633,12 @@ static int ctx_create_impl(int device, const avt_model* m, int num_parts, const 
     c->have_moments = c->have_records = false;
     c->concurrent_groups = 1;
     c->host_pin = nullptr; c->host_pin_cap = 0; c->results_fresh = false;
-    c->render_zkey = nullptr; c->render_label = nullptr; c->render_block = nullptr; c->render_cap_pix = c->render_cap_blk = 0;
-    c->render_mkey = nullptr; c->render_depth = nullptr; c->render_fkey = nullptr; c->render_frank = nullptr; c->render_fedge = nullptr;
-    c->render_cap_paint_pix = c->render_cap_paint_face = 0;
     c->render_img_frames = c->render_img_w = c->render_img_h = 0;
-    HIP_OK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    HIP_OK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+    AVT_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    AVT_HIP(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
     for (int i = 0; i < AVT_MAX_GROUPS - 1; ++i) {
-        HIP_OK(hipStreamCreateWithFlags(&c->side[i], hipStreamNonBlocking));
-        HIP_OK(hipEventCreateWithFlags(&c->ev_join[i], hipEventDisableTiming));
+        AVT_HIP(hipStreamCreateWithFlags(&c->side[i], hipStreamNonBlocking));
+        AVT_HIP(hipEventCreateWithFlags(&c->ev_join[i], hipEventDisableTiming));
     }
     c->cur_stream = c->stream;
     if (avt_solve_set_attributes() || avt_eval_set_attributes() || avt_lbs_set_attributes() || avt_moments_set_attributes()) { avt_set_error("avt_ctx_create: hipFuncSetAttribute failed"); return 1; }
@@ -741,7 +722,7 @@ static int ctx_create_impl(int device, const avt_model* m, int num_parts, const 
         if (dev_alloc(c, &fb.mom_T, (size_t)max_frames * avt_moments_T_doubles(d)) || dev_alloc(c, &fb.mom_D, (size_t)max_frames * J * d.mom_npsi * 3) ||
             dev_alloc(c, &fb.mom_E, (size_t)max_frames * 2) || dev_alloc(c, &fb.mom_rec, (size_t)max_frames * avt_moments_frame_scratch(d)))
             return 1;
-        HIP_OK(hipMemsetAsync(fb.mom_D, 0, (size_t)max_frames * J * d.mom_npsi * 3 * sizeof(double), c->stream));      // joints no vertex is assigned to keep zeros
+        AVT_HIP(hipMemsetAsync(fb.mom_D, 0, (size_t)max_frames * J * d.mom_npsi * 3 * sizeof(double), c->stream));      // joints no vertex is assigned to keep zeros
     }
     c->data_term = AVT_DATA_TERM_AUTO;
     // (tun.mom_min_frames = 8, round 5 - ms per step moments / rows, frames per launch [frames per GPU]: 4 [4] 0.701 / 0.648, 6 [6] 0.710 / 0.692, 8 [8] 0.709 / 0.724,
@@ -760,16 +741,16 @@ static int ctx_create_impl(int device, const avt_model* m, int num_parts, const 
         return 1;
     fb.fsum = (long long*)cntsum;                                   // 8-byte aligned first
     fb.cnt = (int*)(cntsum + FV * 3 * sizeof(long long));
-    HIP_OK(hipMemsetAsync(fb.trace, 0, (size_t)max_frames * 64 * sizeof(double), c->stream));
-    HIP_OK(hipMemsetAsync(fb.ctl, 0, (size_t)max_frames * sizeof(AvtFrameCtl), c->stream));
-    HIP_OK(hipMemsetAsync(fb.ride_ctr, 0, (size_t)max_frames * sizeof(unsigned), c->stream));
-    HIP_OK(hipMemsetAsync(fb.fault, 0, (size_t)max_frames * sizeof(unsigned), c->stream));
+    AVT_HIP(hipMemsetAsync(fb.trace, 0, (size_t)max_frames * 64 * sizeof(double), c->stream));
+    AVT_HIP(hipMemsetAsync(fb.ctl, 0, (size_t)max_frames * sizeof(AvtFrameCtl), c->stream));
+    AVT_HIP(hipMemsetAsync(fb.ride_ctr, 0, (size_t)max_frames * sizeof(unsigned), c->stream));
+    AVT_HIP(hipMemsetAsync(fb.fault, 0, (size_t)max_frames * sizeof(unsigned), c->stream));
     fb.ride_timeout = c->tun.ride_timeout_us * 100;      // wall_clock64() ticks at 100 MHz; 0 makes every wait that is not already satisfied fail (tests)
     fb.xcd_frames = c->tun.xcd_frames;
-    HIP_OK(hipMemsetAsync(fb.spec, 0, (size_t)max_frames * sizeof(AvtSpecCtl), c->stream));
+    AVT_HIP(hipMemsetAsync(fb.spec, 0, (size_t)max_frames * sizeof(AvtSpecCtl), c->stream));
     fb.nspec = 0; fb.seq = 0;
-    HIP_OK(hipMemsetAsync(fb.part_cnt, 0, (size_t)max_frames * 2 * (AVT_MAX_PARTS + 1) * sizeof(int), c->stream));   // invariant of launch_bucket
-    HIP_OK(hipStreamSynchronize(c->stream));
+    AVT_HIP(hipMemsetAsync(fb.part_cnt, 0, (size_t)max_frames * 2 * (AVT_MAX_PARTS + 1) * sizeof(int), c->stream));   // invariant of launch_bucket
+    AVT_HIP(hipStreamSynchronize(c->stream));
     if (c->tun.debug) avt_eval_report_occupancy(dm.d);
     return 0;
 }
@@ -777,10 +758,7 @@ static int ctx_create_impl(int device, const avt_model* m, int num_parts, const 
 
 int avt_ctx_create(int device, const avt_model* m, int num_parts, const int* part_map, int max_points, int max_frames, avt_ctx** out) {
     if (out) *out = nullptr;
-    int rc = 1;
-    try {
-        rc = ctx_create_impl(device, m, num_parts, part_map, max_points, max_frames, out);
-    } catch (const std::exception& e) { avt_set_error(std::string("avt_ctx_create: ") + e.what()); rc = 1; }
+    const int rc = avt_guard("avt_ctx_create", [&]() -> int { return ctx_create_impl(device, m, num_parts, part_map, max_points, max_frames, out); });
     if (rc != 0 && out && *out) {     // streams, events and every allocation made so far are released
         const std::string keep = avt_last_error();
         avt_ctx_destroy(*out);
@@ -796,11 +774,8 @@ void avt_ctx_destroy(avt_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (void* p : c->allocs) (void)hipFree(p);
     if (c->host_pin) (void)hipHostFree(c->host_pin);
-    if (c->render_zkey) (void)hipFree(c->render_zkey);
-    if (c->render_label) (void)hipFree(c->render_label);
-    if (c->render_block) (void)hipFree(c->render_block);
-    for (void* p : {(void*)c->render_mkey, (void*)c->render_depth, (void*)c->render_fkey, (void*)c->render_frank, (void*)c->render_fedge})
-        if (p) (void)hipFree(p);
+    // the render scratch (DevBuf members) goes with `delete`, after the events and the streams: the main stream has just been
+    // drained and every side stream joins it, so nothing is queued on those buffers either way
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
     { std::lock_guard<std::mutex> graph_lock(g_graph_mutex); for (auto& g : c->graphs) (void)hipGraphExecDestroy(g.exec); }
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
@@ -813,80 +788,80 @@ void avt_ctx_destroy(avt_ctx* c) {
 }
 
 int avt_sync(avt_ctx* c) {
-    HIP_OK(hipStreamSynchronize(c->stream));
+    AVT_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }
 
 int avt_lbs_update(avt_ctx* c, int nframes, const double* w, const double* p, const double* R, double* cloud, double* joint_pos,
                    double* joint_trans) {
-    AVT_API_GUARD_BEGIN
-    if (!c || !w || !p || !R) { avt_set_error("avt_lbs_update: null argument"); return 1; }
-    const AvtDims& d = c->dm.d;
-    if (nframes <= 0 || nframes > c->fb.max_frames) { avt_set_error("avt_lbs_update: nframes out of range"); return 1; }
-    HIP_OK(hipSetDevice(c->device));
-    c->frames_valid = c->state_valid = false;    // frame slots' posed clouds / skeleton scratch are overwritten
-    // stage the parameters in the (otherwise unused here) prep buffer: w | p | R
-    double* dw = c->fb.prep;
-    double* dp = dw + (size_t)nframes * d.K;
-    double* dR = dp + (size_t)nframes * 3;
-    if ((size_t)nframes * (d.K + 3 + 9 * d.J) > (size_t)c->fb.max_frames * 2 * d.prep_size) { avt_set_error("avt_lbs_update: staging overflow"); return 1; }
-    HIP_OK(hipMemcpyAsync(dw, w, (size_t)nframes * d.K * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemcpyAsync(dp, p, (size_t)nframes * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemcpyAsync(dR, R, (size_t)nframes * 9 * d.J * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    { ProfScope ps(c, AVT_K_LBS); launch_lbs(c, nframes, nullptr, dw, dp, dR, 0, -1); }
-    if (check_launch("k_lbs")) return 1;
-    if (cloud) HIP_OK(hipMemcpyAsync(cloud, c->fb.cloud, (size_t)nframes * 3 * d.V * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (joint_pos) HIP_OK(hipMemcpyAsync(joint_pos, c->fb.jointpos, (size_t)nframes * 3 * d.J * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (joint_trans) HIP_OK(hipMemcpyAsync(joint_trans, c->fb.jointtrans, (size_t)nframes * 12 * d.J * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    return 0;
-    AVT_API_GUARD_END("avt_lbs_update")
+    return avt_guard("avt_lbs_update", [&]() -> int {
+        if (!c || !w || !p || !R) { avt_set_error("avt_lbs_update: null argument"); return 1; }
+        const AvtDims& d = c->dm.d;
+        if (nframes <= 0 || nframes > c->fb.max_frames) { avt_set_error("avt_lbs_update: nframes out of range"); return 1; }
+        AVT_HIP(hipSetDevice(c->device));
+        c->frames_valid = c->state_valid = false;    // frame slots' posed clouds / skeleton scratch are overwritten
+        // stage the parameters in the (otherwise unused here) prep buffer: w | p | R
+        double* dw = c->fb.prep;
+        double* dp = dw + (size_t)nframes * d.K;
+        double* dR = dp + (size_t)nframes * 3;
+        if ((size_t)nframes * (d.K + 3 + 9 * d.J) > (size_t)c->fb.max_frames * 2 * d.prep_size) { avt_set_error("avt_lbs_update: staging overflow"); return 1; }
+        AVT_HIP(hipMemcpyAsync(dw, w, (size_t)nframes * d.K * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        AVT_HIP(hipMemcpyAsync(dp, p, (size_t)nframes * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        AVT_HIP(hipMemcpyAsync(dR, R, (size_t)nframes * 9 * d.J * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        { ProfScope ps(c, AVT_K_LBS); launch_lbs(c, nframes, nullptr, dw, dp, dR, 0, -1); }
+        if (check_launch("k_lbs")) return 1;
+        if (cloud) AVT_HIP(hipMemcpyAsync(cloud, c->fb.cloud, (size_t)nframes * 3 * d.V * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (joint_pos) AVT_HIP(hipMemcpyAsync(joint_pos, c->fb.jointpos, (size_t)nframes * 3 * d.J * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (joint_trans) AVT_HIP(hipMemcpyAsync(joint_trans, c->fb.jointtrans, (size_t)nframes * 12 * d.J * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        AVT_HIP(hipStreamSynchronize(c->stream));
+        return 0;
+    });
 }
 
 int avt_visibility(avt_ctx* c, const double* cloud, int enable, unsigned char* visible) {
     if (!c || !cloud || !visible) { avt_set_error("avt_visibility: null argument"); return 1; }
     const AvtDims& d = c->dm.d;
-    HIP_OK(hipSetDevice(c->device));
+    AVT_HIP(hipSetDevice(c->device));
     c->frames_valid = c->state_valid = false;
-    HIP_OK(hipMemcpyAsync(c->fb.cloud, cloud, (size_t)3 * d.V * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    AVT_HIP(hipMemcpyAsync(c->fb.cloud, cloud, (size_t)3 * d.V * sizeof(double), hipMemcpyHostToDevice, c->stream));
     { ProfScope ps(c, AVT_K_VISIBILITY); launch_visibility(c, 1, enable); }
     if (check_launch("k_visibility")) return 1;
-    HIP_OK(hipMemcpyAsync(visible, c->fb.visible, (size_t)d.V, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
+    AVT_HIP(hipMemcpyAsync(visible, c->fb.visible, (size_t)d.V, hipMemcpyDeviceToHost, c->stream));
+    AVT_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }
 
 int avt_nn(avt_ctx* c, const double* model_cloud, const unsigned char* visible, const double* data, const int* labels, int N, int* out) {
-    AVT_API_GUARD_BEGIN
-    if (!c || !model_cloud || !visible || !data || !labels || !out) { avt_set_error("avt_nn: null argument"); return 1; }
-    const AvtDims& d = c->dm.d;
-    const int V = d.V;
-    HIP_OK(hipSetDevice(c->device));
-    if (N == 0) return 0;
-    const int offs[2] = {0, N};
-    if (upload_frames(c, 1, data, labels, offs)) return 1;
-    c->frames_valid = c->state_valid = false;    // frame slot 0 is scratch for this call
-    // part-sorted SoA copy of the model cloud
-    std::vector<int> ppos(V);
-    HIP_OK(hipMemcpyAsync(ppos.data(), c->dm.part_pos, (size_t)V * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    std::vector<double> px(V), py(V), pz(V);
-    for (int v = 0; v < V; ++v) { px[ppos[v]] = model_cloud[3 * v]; py[ppos[v]] = model_cloud[3 * v + 1]; pz[ppos[v]] = model_cloud[3 * v + 2]; }
-    HIP_OK(hipMemcpyAsync(c->fb.pcx, px.data(), V * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemcpyAsync(c->fb.pcy, py.data(), V * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemcpyAsync(c->fb.pcz, pz.data(), V * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemcpyAsync(c->fb.visible, visible, (size_t)V, hipMemcpyHostToDevice, c->stream));
-    AvtFrameCtl ctl;
-    std::memset(&ctl, 0, sizeof(ctl));
-    ctl.N = N;
-    HIP_OK(hipMemcpyAsync(c->fb.ctl, &ctl, sizeof(ctl), hipMemcpyHostToDevice, c->stream));
-    { ProfScope ps(c, AVT_K_BUCKET); launch_bucket(c, 1, true); }
-    { ProfScope ps(c, AVT_K_NN); launch_nn(c, 1); }
-    if (check_launch("k_nn")) return 1;
-    HIP_OK(hipMemcpyAsync(out, c->fb.corr, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    return 0;
-    AVT_API_GUARD_END("avt_nn")
+    return avt_guard("avt_nn", [&]() -> int {
+        if (!c || !model_cloud || !visible || !data || !labels || !out) { avt_set_error("avt_nn: null argument"); return 1; }
+        const AvtDims& d = c->dm.d;
+        const int V = d.V;
+        AVT_HIP(hipSetDevice(c->device));
+        if (N == 0) return 0;
+        const int offs[2] = {0, N};
+        if (upload_frames(c, 1, data, labels, offs)) return 1;
+        c->frames_valid = c->state_valid = false;    // frame slot 0 is scratch for this call
+        // part-sorted SoA copy of the model cloud
+        std::vector<int> ppos(V);
+        AVT_HIP(hipMemcpyAsync(ppos.data(), c->dm.part_pos, (size_t)V * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        AVT_HIP(hipStreamSynchronize(c->stream));
+        std::vector<double> px(V), py(V), pz(V);
+        for (int v = 0; v < V; ++v) { px[ppos[v]] = model_cloud[3 * v]; py[ppos[v]] = model_cloud[3 * v + 1]; pz[ppos[v]] = model_cloud[3 * v + 2]; }
+        AVT_HIP(hipMemcpyAsync(c->fb.pcx, px.data(), V * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        AVT_HIP(hipMemcpyAsync(c->fb.pcy, py.data(), V * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        AVT_HIP(hipMemcpyAsync(c->fb.pcz, pz.data(), V * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        AVT_HIP(hipMemcpyAsync(c->fb.visible, visible, (size_t)V, hipMemcpyHostToDevice, c->stream));
+        AvtFrameCtl ctl;
+        std::memset(&ctl, 0, sizeof(ctl));
+        ctl.N = N;
+        AVT_HIP(hipMemcpyAsync(c->fb.ctl, &ctl, sizeof(ctl), hipMemcpyHostToDevice, c->stream));
+        { ProfScope ps(c, AVT_K_BUCKET); launch_bucket(c, 1, true); }
+        { ProfScope ps(c, AVT_K_NN); launch_nn(c, 1); }
+        if (check_launch("k_nn")) return 1;
+        AVT_HIP(hipMemcpyAsync(out, c->fb.corr, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        AVT_HIP(hipStreamSynchronize(c->stream));
+        return 0;
+    });
 }
 
 int avt_synth_render_frames(avt_ctx* c, int nframes, const double* w, const double* p, const double* R, double fx, double fy, double cx,
@@ -896,231 +871,216 @@ int avt_synth_render_frames(avt_ctx* c, int nframes, const double* w, const doub
 
 int avt_synth_render_frames_mode(avt_ctx* c, int nframes, const double* w, const double* p, const double* R, double fx, double fy, double cx,
                                  double cy, int width, int height, int mode, int* points_per_frame) {
-    AVT_API_GUARD_BEGIN
-    if (!c || !w || !p || !R || width <= 0 || height <= 0) { avt_set_error("avt_synth_render_frames: bad argument"); return 1; }
-    if (mode != AVT_RENDER_ZBUFFER && mode != AVT_RENDER_PAINTER) { avt_set_error("avt_synth_render_frames: unknown mode"); return 1; }
-    const bool painter = mode == AVT_RENDER_PAINTER;
-    c->render_img_frames = 0;
-    const AvtDims& d = c->dm.d;
-    if (nframes <= 0 || nframes > c->fb.max_frames) { avt_set_error("avt_synth_render_frames: nframes out of range"); return 1; }
-    HIP_OK(hipSetDevice(c->device));
-    // pose the ground-truth avatars (Avatar::update) for all frames
-    double* dw = c->fb.prep;
-    double* dp = dw + (size_t)nframes * d.K;
-    double* dR = dp + (size_t)nframes * 3;
-    HIP_OK(hipMemcpyAsync(dw, w, (size_t)nframes * d.K * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemcpyAsync(dp, p, (size_t)nframes * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemcpyAsync(dR, R, (size_t)nframes * 9 * d.J * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    launch_lbs(c, nframes, nullptr, dw, dp, dR, 0, -1);
-    // rasterise in chunks of frames (8 bytes of z-buffer key per pixel)
-    const size_t npix = (size_t)width * height;
-    const int chunk = std::max(1, std::min(nframes, (int)((256ull << 20) / (npix * (painter ? 21 : 9) + 64))));
-    const int nb = (int)((npix + 255) / 256);
-    // z-buffer keys, labels and block counts live in the context and only grow (no hipMalloc / hipFree per call)
-    if (c->render_cap_pix < npix * chunk || c->render_cap_blk < (size_t)nb * chunk) {
-        HIP_OK(hipStreamSynchronize(c->stream));
-        if (c->render_zkey) (void)hipFree(c->render_zkey);
-        if (c->render_label) (void)hipFree(c->render_label);
-        if (c->render_block) (void)hipFree(c->render_block);
-        c->render_zkey = nullptr; c->render_label = nullptr; c->render_block = nullptr; c->render_cap_pix = c->render_cap_blk = 0;
-        HIP_OK(hipMalloc((void**)&c->render_zkey, npix * chunk * sizeof(unsigned long long)));
-        HIP_OK(hipMalloc((void**)&c->render_label, npix * chunk));
-        HIP_OK(hipMalloc((void**)&c->render_block, (size_t)nb * chunk * sizeof(int)));
-        c->render_cap_pix = npix * chunk; c->render_cap_blk = (size_t)nb * chunk;
-    }
-    const size_t nface = (size_t)d.F * chunk;
-    if (painter && (c->render_cap_paint_pix < npix * chunk || c->render_cap_paint_face < nface)) {
-        HIP_OK(hipStreamSynchronize(c->stream));
-        for (void* q : {(void*)c->render_mkey, (void*)c->render_depth, (void*)c->render_fkey, (void*)c->render_frank, (void*)c->render_fedge})
-            if (q) (void)hipFree(q);
-        c->render_mkey = nullptr; c->render_depth = nullptr; c->render_fkey = nullptr; c->render_frank = nullptr; c->render_fedge = nullptr;
-        c->render_cap_paint_pix = c->render_cap_paint_face = 0;
-        HIP_OK(hipMalloc((void**)&c->render_mkey, npix * chunk * sizeof(unsigned long long)));
-        HIP_OK(hipMalloc((void**)&c->render_depth, npix * chunk * sizeof(float)));
-        HIP_OK(hipMalloc((void**)&c->render_fkey, nface * sizeof(float)));
-        HIP_OK(hipMalloc((void**)&c->render_frank, nface * sizeof(int)));
-        HIP_OK(hipMalloc((void**)&c->render_fedge, nface));
-        c->render_cap_paint_pix = npix * chunk; c->render_cap_paint_face = nface;
-    }
-    int rc = 0;
-    for (int f0 = 0; f0 < nframes && !rc; f0 += chunk) {
-        c->fb.f0 = f0;
-        const int nf = std::min(chunk, nframes - f0);
-        if (painter)
-            rc = avt_paint_enqueue(c, nf, c->dm.part_of_vertex, c->render_zkey, c->render_mkey, c->render_fkey, c->render_frank, c->render_fedge,
-                                   c->render_depth, c->render_label, c->render_block, fx, fy, cx, cy, width, height);
-        else
-            rc = avt_render_enqueue(c, nf, c->dm.part_of_vertex, c->render_zkey, c->render_label, c->render_block, fx, fy, cx, cy, width, height);
-    }
-    c->fb.f0 = 0;
-    if (rc) { avt_set_error("avt_synth_render_frames: render launch failed"); return 1; }
-    std::vector<AvtFrameCtl> ctl(nframes);
-    HIP_OK(hipMemcpyAsync(ctl.data(), c->fb.ctl, ctl.size() * sizeof(AvtFrameCtl), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    c->frames_valid = c->state_valid = false;
-    c->have_moments = c->have_records = false;
-    c->results_fresh = false;
-    c->nframes = nframes;
-    c->frame_N.assign(nframes, 0);
-    c->frame_off.assign(nframes + 1, 0);
-    int mx = 0;
-    for (int f = 0; f < nframes; ++f) {
-        if (ctl[f].T > c->fb.max_points) { avt_set_error("avt_synth_render_frames: a rendered frame has more points than max_points_per_frame"); return 1; }
-        c->frame_N[f] = ctl[f].N;
-        c->frame_off[f + 1] = c->frame_off[f] + ctl[f].N;
-        mx = std::max(mx, ctl[f].N);
-        if (points_per_frame) points_per_frame[f] = ctl[f].N;
-    }
-    c->launch_maxN = std::max(mx, std::min(c->fb.max_points, ((mx + 2047) / 2048) * 2048));
-    // the render kernels wrote N into the working control blocks; the start copies follow (avt_state_reset)
-    HIP_OK(hipMemcpy2DAsync(&c->fb.ctl_start->N, sizeof(AvtFrameCtl), c->frame_N.data(), sizeof(int), sizeof(int), (size_t)nframes, hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    c->frames_valid = true;
-    if (painter && nframes <= chunk) { c->render_img_frames = nframes; c->render_img_w = width; c->render_img_h = height; }
-    return 0;
-    AVT_API_GUARD_END("avt_synth_render_frames")
+    return avt_guard("avt_synth_render_frames", [&]() -> int {
+        if (!c || !w || !p || !R || width <= 0 || height <= 0) { avt_set_error("avt_synth_render_frames: bad argument"); return 1; }
+        if (mode != AVT_RENDER_ZBUFFER && mode != AVT_RENDER_PAINTER) { avt_set_error("avt_synth_render_frames: unknown mode"); return 1; }
+        const bool painter = mode == AVT_RENDER_PAINTER;
+        c->render_img_frames = 0;
+        const AvtDims& d = c->dm.d;
+        if (nframes <= 0 || nframes > c->fb.max_frames) { avt_set_error("avt_synth_render_frames: nframes out of range"); return 1; }
+        AVT_HIP(hipSetDevice(c->device));
+        // pose the ground-truth avatars (Avatar::update) for all frames
+        double* dw = c->fb.prep;
+        double* dp = dw + (size_t)nframes * d.K;
+        double* dR = dp + (size_t)nframes * 3;
+        AVT_HIP(hipMemcpyAsync(dw, w, (size_t)nframes * d.K * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        AVT_HIP(hipMemcpyAsync(dp, p, (size_t)nframes * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        AVT_HIP(hipMemcpyAsync(dR, R, (size_t)nframes * 9 * d.J * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        launch_lbs(c, nframes, nullptr, dw, dp, dR, 0, -1);
+        // rasterise in chunks of frames (8 bytes of z-buffer key per pixel)
+        const size_t npix = (size_t)width * height;
+        const int chunk = std::max(1, std::min(nframes, (int)((256ull << 20) / (npix * (painter ? 21 : 9) + 64))));
+        const int nb = (int)((npix + 255) / 256);
+        // z-buffer keys, labels and block counts live in the context and only grow (no hipMalloc / hipFree per call)
+        auto scratch = [&](auto& buf, size_t n) -> int {
+            if (n <= buf.cap) return 0;
+            AVT_HIP(hipStreamSynchronize(c->stream));     // what is queued on the old block drains before it goes
+            return buf.reserve(n);
+        };
+        const size_t pix = npix * chunk, nface = (size_t)d.F * chunk;
+        if (scratch(c->render_zkey, pix) || scratch(c->render_label, pix) || scratch(c->render_block, (size_t)nb * chunk)) return 1;
+        if (painter && (scratch(c->render_mkey, pix) || scratch(c->render_depth, pix) || scratch(c->render_fkey, nface) || scratch(c->render_frank, nface) ||
+                        scratch(c->render_fedge, nface)))
+            return 1;
+        int rc = 0;
+        for (int f0 = 0; f0 < nframes && !rc; f0 += chunk) {
+            c->fb.f0 = f0;
+            const int nf = std::min(chunk, nframes - f0);
+            if (painter)
+                rc = avt_paint_enqueue(c, nf, c->dm.part_of_vertex, c->render_zkey, c->render_mkey, c->render_fkey, c->render_frank, c->render_fedge,
+                                       c->render_depth, c->render_label, c->render_block, fx, fy, cx, cy, width, height);
+            else
+                rc = avt_render_enqueue(c, nf, c->dm.part_of_vertex, c->render_zkey, c->render_label, c->render_block, fx, fy, cx, cy, width, height);
+        }
+        c->fb.f0 = 0;
+        if (rc) { avt_set_error("avt_synth_render_frames: render launch failed"); return 1; }
+        std::vector<AvtFrameCtl> ctl(nframes);
+        AVT_HIP(hipMemcpyAsync(ctl.data(), c->fb.ctl, ctl.size() * sizeof(AvtFrameCtl), hipMemcpyDeviceToHost, c->stream));
+        AVT_HIP(hipStreamSynchronize(c->stream));
+        c->frames_valid = c->state_valid = false;
+        c->have_moments = c->have_records = false;
+        c->results_fresh = false;
+        c->nframes = nframes;
+        c->frame_N.assign(nframes, 0);
+        c->frame_off.assign(nframes + 1, 0);
+        int mx = 0;
+        for (int f = 0; f < nframes; ++f) {
+            if (ctl[f].T > c->fb.max_points) { avt_set_error("avt_synth_render_frames: a rendered frame has more points than max_points_per_frame"); return 1; }
+            c->frame_N[f] = ctl[f].N;
+            c->frame_off[f + 1] = c->frame_off[f] + ctl[f].N;
+            mx = std::max(mx, ctl[f].N);
+            if (points_per_frame) points_per_frame[f] = ctl[f].N;
+        }
+        c->launch_maxN = std::max(mx, std::min(c->fb.max_points, ((mx + 2047) / 2048) * 2048));
+        // the render kernels wrote N into the working control blocks; the start copies follow (avt_state_reset)
+        AVT_HIP(hipMemcpy2DAsync(&c->fb.ctl_start->N, sizeof(AvtFrameCtl), c->frame_N.data(), sizeof(int), sizeof(int), (size_t)nframes, hipMemcpyHostToDevice, c->stream));
+        AVT_HIP(hipStreamSynchronize(c->stream));
+        c->frames_valid = true;
+        if (painter && nframes <= chunk) { c->render_img_frames = nframes; c->render_img_w = width; c->render_img_h = height; }
+        return 0;
+    });
 }
 
 int avt_synth_render_images(avt_ctx* c, int frame, float* depth, unsigned char* part_mask) {
-    AVT_API_GUARD_BEGIN
-    if (!c) { avt_set_error("avt_synth_render_images: null context"); return 1; }
-    if (c->render_img_frames == 0) {
-        avt_set_error("avt_synth_render_images: no images retained (needs a preceding AVT_RENDER_PAINTER call whose frames fit one scratch chunk)");
-        return 1;
-    }
-    if (frame < 0 || frame >= c->render_img_frames) { avt_set_error("avt_synth_render_images: frame out of range"); return 1; }
-    HIP_OK(hipSetDevice(c->device));
-    const size_t npix = (size_t)c->render_img_w * c->render_img_h;
-    if (depth) HIP_OK(hipMemcpyAsync(depth, c->render_depth + (size_t)frame * npix, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (part_mask) HIP_OK(hipMemcpyAsync(part_mask, c->render_label + (size_t)frame * npix, npix, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    return 0;
-    AVT_API_GUARD_END("avt_synth_render_images")
+    return avt_guard("avt_synth_render_images", [&]() -> int {
+        if (!c) { avt_set_error("avt_synth_render_images: null context"); return 1; }
+        if (c->render_img_frames == 0) {
+            avt_set_error("avt_synth_render_images: no images retained (needs a preceding AVT_RENDER_PAINTER call whose frames fit one scratch chunk)");
+            return 1;
+        }
+        if (frame < 0 || frame >= c->render_img_frames) { avt_set_error("avt_synth_render_images: frame out of range"); return 1; }
+        AVT_HIP(hipSetDevice(c->device));
+        const size_t npix = (size_t)c->render_img_w * c->render_img_h;
+        if (depth) AVT_HIP(hipMemcpyAsync(depth, c->render_depth + (size_t)frame * npix, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        if (part_mask) AVT_HIP(hipMemcpyAsync(part_mask, c->render_label + (size_t)frame * npix, npix, hipMemcpyDeviceToHost, c->stream));
+        AVT_HIP(hipStreamSynchronize(c->stream));
+        return 0;
+    });
 }
 
 int avt_frames_download(avt_ctx* c, int frame, double* data_3xN, int* labels) {
     if (!c || !c->frames_valid || frame < 0 || frame >= c->nframes) { avt_set_error("avt_frames_download: bad argument"); return 1; }
-    HIP_OK(hipSetDevice(c->device));
+    AVT_HIP(hipSetDevice(c->device));
     const size_t N = c->frame_N[frame];
-    if (data_3xN) HIP_OK(hipMemcpyAsync(data_3xN, c->fb.data_raw + (size_t)frame * c->fb.max_points * 3, N * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (labels) HIP_OK(hipMemcpyAsync(labels, c->fb.labels_raw + (size_t)frame * c->fb.max_points, N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
+    if (data_3xN) AVT_HIP(hipMemcpyAsync(data_3xN, c->fb.data_raw + (size_t)frame * c->fb.max_points * 3, N * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (labels) AVT_HIP(hipMemcpyAsync(labels, c->fb.labels_raw + (size_t)frame * c->fb.max_points, N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    AVT_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }
 
 int avt_frames_upload(avt_ctx* c, int nframes, const double* data, const int* labels, const int* frame_offsets) {
-    AVT_API_GUARD_BEGIN
-    if (!c || !data || !labels || !frame_offsets) { avt_set_error("avt_frames_upload: null argument"); return 1; }
-    HIP_OK(hipSetDevice(c->device));
-    if (upload_frames(c, nframes, data, labels, frame_offsets)) return 1;
-    HIP_OK(hipStreamSynchronize(c->stream));
-    return 0;
-    AVT_API_GUARD_END("avt_frames_upload")
+    return avt_guard("avt_frames_upload", [&]() -> int {
+        if (!c || !data || !labels || !frame_offsets) { avt_set_error("avt_frames_upload: null argument"); return 1; }
+        AVT_HIP(hipSetDevice(c->device));
+        if (upload_frames(c, nframes, data, labels, frame_offsets)) return 1;
+        AVT_HIP(hipStreamSynchronize(c->stream));
+        return 0;
+    });
 }
 
 int avt_state_upload(avt_ctx* c, int nframes, const double* p, const double* q, const double* w) {
-    AVT_API_GUARD_BEGIN
-    if (!c || !p || !q || !w) { avt_set_error("avt_state_upload: null argument"); return 1; }
-    HIP_OK(hipSetDevice(c->device));
-    return upload_state(c, nframes, p, q, w);
-    AVT_API_GUARD_END("avt_state_upload")
+    return avt_guard("avt_state_upload", [&]() -> int {
+        if (!c || !p || !q || !w) { avt_set_error("avt_state_upload: null argument"); return 1; }
+        AVT_HIP(hipSetDevice(c->device));
+        return upload_state(c, nframes, p, q, w);
+    });
 }
 
 int avt_optimize_resident(avt_ctx* c, const avt_options* opt) {
-    AVT_API_GUARD_BEGIN
-    if (!c || !opt) { avt_set_error("avt_optimize_resident: null argument"); return 1; }
-    HIP_OK(hipSetDevice(c->device));
-    const int rc = run_optimize(c, opt);
-    if (rc) c->results_fresh = false;      //  a call that failed left no result records
-    return rc;
-    AVT_API_GUARD_END("avt_optimize_resident")
+    return avt_guard("avt_optimize_resident", [&]() -> int {
+        if (!c || !opt) { avt_set_error("avt_optimize_resident: null argument"); return 1; }
+        AVT_HIP(hipSetDevice(c->device));
+        const int rc = run_optimize(c, opt);
+        if (rc) c->results_fresh = false;      //  a call that failed left no result records
+        return rc;
+    });
 }
 
 int avt_optimize_resident_budgets(avt_ctx* c, const avt_options* opt, const int* icp_budget) {
-    AVT_API_GUARD_BEGIN
-    if (!c || !opt || !icp_budget) { avt_set_error("avt_optimize_resident_budgets: null argument"); return 1; }
-    HIP_OK(hipSetDevice(c->device));
-    if (check_optimize(c, opt)) return 1;
-    const int nf = c->nframes;
-    for (int f = 0; f < nf; ++f)
-        if (icp_budget[f] < 0 || icp_budget[f] > opt->icp_iters) {
-            char msg[160];
-            snprintf(msg, sizeof msg, "avt_optimize_resident_budgets: frame %d has budget %d, outside [0, icp_iters = %d]", f, icp_budget[f], opt->icp_iters);
-            avt_set_error(msg);
-            return 1;
+    return avt_guard("avt_optimize_resident_budgets", [&]() -> int {
+        if (!c || !opt || !icp_budget) { avt_set_error("avt_optimize_resident_budgets: null argument"); return 1; }
+        AVT_HIP(hipSetDevice(c->device));
+        if (check_optimize(c, opt)) return 1;
+        const int nf = c->nframes;
+        for (int f = 0; f < nf; ++f)
+            if (icp_budget[f] < 0 || icp_budget[f] > opt->icp_iters) {
+                char msg[160];
+                snprintf(msg, sizeof msg, "avt_optimize_resident_budgets: frame %d has budget %d, outside [0, icp_iters = %d]", f, icp_budget[f], opt->icp_iters);
+                avt_set_error(msg);
+                return 1;
+            }
+        if (!c->budget_hold && dev_alloc(c, &c->budget_hold, (size_t)c->fb.max_frames * avt_budget_hold_doubles(c->dm.d))) return 1;
+        if (!c->budget) {
+            if (dev_alloc(c, &c->budget, (size_t)c->fb.max_frames)) return 1;
+            c->budget_host.clear();
         }
-    if (!c->budget_hold && dev_alloc(c, &c->budget_hold, (size_t)c->fb.max_frames * avt_budget_hold_doubles(c->dm.d))) return 1;
-    if (!c->budget) {
-        if (dev_alloc(c, &c->budget, (size_t)c->fb.max_frames)) return 1;
-        c->budget_host.clear();
-    }
-    if (c->budget_host.size() < (size_t)nf || !std::equal(icp_budget, icp_budget + nf, c->budget_host.begin())) {
-        for (int f0 = 0; f0 < nf; f0 += AVT_BUDGET_CHUNK) {
-            AvtBudgetChunk a;
-            a.f0 = f0;
-            a.n = std::min(AVT_BUDGET_CHUNK, nf - f0);
-            std::copy(icp_budget + f0, icp_budget + f0 + a.n, a.b);
-            launch_budget_set(c, c->budget, a);
+        if (c->budget_host.size() < (size_t)nf || !std::equal(icp_budget, icp_budget + nf, c->budget_host.begin())) {
+            for (int f0 = 0; f0 < nf; f0 += AVT_BUDGET_CHUNK) {
+                AvtBudgetChunk a;
+                a.f0 = f0;
+                a.n = std::min(AVT_BUDGET_CHUNK, nf - f0);
+                std::copy(icp_budget + f0, icp_budget + f0 + a.n, a.b);
+                launch_budget_set(c, c->budget, a);
+            }
+            if (check_launch("k_budget_set")) { c->budget_host.clear(); return 1; }
+            c->budget_host.assign(icp_budget, icp_budget + nf);
         }
-        if (check_launch("k_budget_set")) { c->budget_host.clear(); return 1; }
-        c->budget_host.assign(icp_budget, icp_budget + nf);
-    }
-    const int rc = run_optimize(c, opt, c->budget);
-    c->results_fresh = false;      // the result records of the closing launch describe the frames before the held ones were put back
-    return rc;
-    AVT_API_GUARD_END("avt_optimize_resident_budgets")
+        const int rc = run_optimize(c, opt, c->budget);
+        c->results_fresh = false;      // the result records of the closing launch describe the frames before the held ones were put back
+        return rc;
+    });
 }
 
 int avt_state_upload_frames(avt_ctx* c, int count, const int* frames, const double* p, const double* q, const double* w) {
-    AVT_API_GUARD_BEGIN
-    if (!c || !frames || !p || !q || !w) { avt_set_error("avt_state_upload_frames: null argument"); return 1; }
-    if (!c->frames_valid || !c->state_valid || c->nframes <= 0) { avt_set_error("avt_state_upload_frames: no resident state to update (avt_state_upload first)"); return 1; }
-    const int nf = c->nframes;
-    if (count <= 0 || count > nf) { avt_set_error("avt_state_upload_frames: count out of range"); return 1; }
-    std::vector<char> seen(nf, 0);
-    for (int i = 0; i < count; ++i) {
-        if (frames[i] < 0 || frames[i] >= nf) { avt_set_error("avt_state_upload_frames: frame id out of range"); return 1; }
-        if (seen[frames[i]]++) { avt_set_error("avt_state_upload_frames: a frame id is repeated"); return 1; }
-    }
-    HIP_OK(hipSetDevice(c->device));
-    const AvtDims& d = c->dm.d;
-    for (int i = 0; i < count; ++i) {
-        AvtStateInstall a;
-        a.frame = frames[i];
-        a.N = c->frame_N[frames[i]];
-        std::copy(p + 3 * i, p + 3 * i + 3, a.x);
-        std::copy(q + (size_t)4 * d.J * i, q + (size_t)4 * d.J * (i + 1), a.x + 3);
-        std::copy(w + (size_t)d.K * i, w + (size_t)d.K * (i + 1), a.x + 3 + 4 * d.J);
-        launch_state_install(c, a);
-    }
-    c->results_fresh = false;
-    return check_launch("k_state_install");
-    AVT_API_GUARD_END("avt_state_upload_frames")
+    return avt_guard("avt_state_upload_frames", [&]() -> int {
+        if (!c || !frames || !p || !q || !w) { avt_set_error("avt_state_upload_frames: null argument"); return 1; }
+        if (!c->frames_valid || !c->state_valid || c->nframes <= 0) { avt_set_error("avt_state_upload_frames: no resident state to update (avt_state_upload first)"); return 1; }
+        const int nf = c->nframes;
+        if (count <= 0 || count > nf) { avt_set_error("avt_state_upload_frames: count out of range"); return 1; }
+        std::vector<char> seen(nf, 0);
+        for (int i = 0; i < count; ++i) {
+            if (frames[i] < 0 || frames[i] >= nf) { avt_set_error("avt_state_upload_frames: frame id out of range"); return 1; }
+            if (seen[frames[i]]++) { avt_set_error("avt_state_upload_frames: a frame id is repeated"); return 1; }
+        }
+        AVT_HIP(hipSetDevice(c->device));
+        const AvtDims& d = c->dm.d;
+        for (int i = 0; i < count; ++i) {
+            AvtStateInstall a;
+            a.frame = frames[i];
+            a.N = c->frame_N[frames[i]];
+            std::copy(p + 3 * i, p + 3 * i + 3, a.x);
+            std::copy(q + (size_t)4 * d.J * i, q + (size_t)4 * d.J * (i + 1), a.x + 3);
+            std::copy(w + (size_t)d.K * i, w + (size_t)d.K * (i + 1), a.x + 3 + 4 * d.J);
+            launch_state_install(c, a);
+        }
+        c->results_fresh = false;
+        return check_launch("k_state_install");
+    });
 }
 
 int avt_state_reset(avt_ctx* c) {
     if (!c || c->nframes <= 0 || !c->state_valid) { avt_set_error("avt_state_reset: no state resident"); return 1; }
-    HIP_OK(hipSetDevice(c->device));
+    AVT_HIP(hipSetDevice(c->device));
     launch_state_reset(c, c->nframes);
     c->results_fresh = false;
     return check_launch("k_state_reset");
 }
 
 int avt_state_download(avt_ctx* c, double* p, double* q, double* w, avt_stats* stats) {
-    AVT_API_GUARD_BEGIN
-    if (!c) { avt_set_error("avt_state_download: null context"); return 1; }
-    HIP_OK(hipSetDevice(c->device));
-    return download_state(c, p, q, w, stats);
-    AVT_API_GUARD_END("avt_state_download")
+    return avt_guard("avt_state_download", [&]() -> int {
+        if (!c) { avt_set_error("avt_state_download: null context"); return 1; }
+        AVT_HIP(hipSetDevice(c->device));
+        return download_state(c, p, q, w, stats);
+    });
 }
 
 int avt_optimize_batch(avt_ctx* c, int nframes, const double* data, const int* labels, const int* frame_offsets, const avt_options* opt,
                        double* p, double* q, double* w, avt_stats* stats) {
-    AVT_API_GUARD_BEGIN
-    if (!c || !data || !labels || !frame_offsets || !opt || !p || !q || !w) { avt_set_error("avt_optimize_batch: null argument"); return 1; }
-    HIP_OK(hipSetDevice(c->device));
-    return optimize_host_to_host(c, nframes, data, labels, frame_offsets, opt, p, q, w, stats);
-    AVT_API_GUARD_END("avt_optimize_batch")
+    return avt_guard("avt_optimize_batch", [&]() -> int {
+        if (!c || !data || !labels || !frame_offsets || !opt || !p || !q || !w) { avt_set_error("avt_optimize_batch: null argument"); return 1; }
+        AVT_HIP(hipSetDevice(c->device));
+        return optimize_host_to_host(c, nframes, data, labels, frame_offsets, opt, p, q, w, stats);
+    });
 }
 
 int avt_optimize(avt_ctx* c, const double* data, const int* labels, int N, const avt_options* opt, double* p, double* q, double* w,
@@ -1131,124 +1091,124 @@ int avt_optimize(avt_ctx* c, const double* data, const int* labels, int N, const
 
 int avt_optimize_posed(avt_ctx* c, const double* data, const int* labels, int N, const avt_options* opt, double* p, double* q, double* w,
                        avt_stats* stats, double* cloud, double* joint_pos, double* joint_trans) {
-    AVT_API_GUARD_BEGIN
-    if (!c || !data || !labels || !opt || !p || !q || !w) { avt_set_error("avt_optimize_posed: null argument"); return 1; }
-    if (opt->icp_iters <= 0 && (cloud || joint_pos || joint_trans)) { avt_set_error("avt_optimize_posed: no ICP iteration, no closing update(): nothing posed to return"); return 1; }
-    HIP_OK(hipSetDevice(c->device));
-    const int offs[2] = {0, N};
-    return optimize_host_to_host(c, 1, data, labels, offs, opt, p, q, w, stats, cloud, joint_pos, joint_trans);
-    AVT_API_GUARD_END("avt_optimize_posed")
+    return avt_guard("avt_optimize_posed", [&]() -> int {
+        if (!c || !data || !labels || !opt || !p || !q || !w) { avt_set_error("avt_optimize_posed: null argument"); return 1; }
+        if (opt->icp_iters <= 0 && (cloud || joint_pos || joint_trans)) { avt_set_error("avt_optimize_posed: no ICP iteration, no closing update(): nothing posed to return"); return 1; }
+        AVT_HIP(hipSetDevice(c->device));
+        const int offs[2] = {0, N};
+        return optimize_host_to_host(c, 1, data, labels, offs, opt, p, q, w, stats, cloud, joint_pos, joint_trans);
+    });
 }
 
 int avt_get_correspondences(avt_ctx* c, int frame, int* out) {
     if (!c || !out || frame < 0 || frame >= c->nframes) { avt_set_error("avt_get_correspondences: bad argument"); return 1; }
-    HIP_OK(hipSetDevice(c->device));
-    HIP_OK(hipMemcpyAsync(out, c->fb.corr + (size_t)frame * c->fb.max_points, (size_t)c->frame_N[frame] * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
+    AVT_HIP(hipSetDevice(c->device));
+    AVT_HIP(hipMemcpyAsync(out, c->fb.corr + (size_t)frame * c->fb.max_points, (size_t)c->frame_N[frame] * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    AVT_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }
 
 int avt_get_cloud(avt_ctx* c, int frame, double* cloud) {
     if (!c || !cloud || frame < 0 || frame >= c->fb.max_frames) { avt_set_error("avt_get_cloud: bad argument"); return 1; }
-    HIP_OK(hipSetDevice(c->device));
-    HIP_OK(hipMemcpyAsync(cloud, c->fb.cloud + (size_t)frame * 3 * c->dm.d.V, (size_t)3 * c->dm.d.V * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
+    AVT_HIP(hipSetDevice(c->device));
+    AVT_HIP(hipMemcpyAsync(cloud, c->fb.cloud + (size_t)frame * 3 * c->dm.d.V, (size_t)3 * c->dm.d.V * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    AVT_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }
 
 int avt_get_posed(avt_ctx* c, int frame, double* cloud, double* joint_pos, double* joint_trans) {
     if (!c || frame < 0 || frame >= c->fb.max_frames) { avt_set_error("avt_get_posed: bad argument"); return 1; }
     const AvtDims& d = c->dm.d;
-    HIP_OK(hipSetDevice(c->device));
-    if (cloud) HIP_OK(hipMemcpyAsync(cloud, c->fb.cloud + (size_t)frame * 3 * d.V, (size_t)3 * d.V * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (joint_pos) HIP_OK(hipMemcpyAsync(joint_pos, c->fb.jointpos + (size_t)frame * 3 * d.J, (size_t)3 * d.J * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (joint_trans) HIP_OK(hipMemcpyAsync(joint_trans, c->fb.jointtrans + (size_t)frame * 12 * d.J, (size_t)12 * d.J * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
+    AVT_HIP(hipSetDevice(c->device));
+    if (cloud) AVT_HIP(hipMemcpyAsync(cloud, c->fb.cloud + (size_t)frame * 3 * d.V, (size_t)3 * d.V * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (joint_pos) AVT_HIP(hipMemcpyAsync(joint_pos, c->fb.jointpos + (size_t)frame * 3 * d.J, (size_t)3 * d.J * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (joint_trans) AVT_HIP(hipMemcpyAsync(joint_trans, c->fb.jointtrans + (size_t)frame * 12 * d.J, (size_t)12 * d.J * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    AVT_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }
 
 int avt_get_normal_equations(avt_ctx* c, int frame, double* H, double* g, double* cost) {
-    AVT_API_GUARD_BEGIN
-    if (!c || frame < 0 || frame >= c->nframes) { avt_set_error("avt_get_normal_equations: bad argument"); return 1; }
-    if (!c->frames_valid || !c->state_valid || c->ran_icp_iters <= 0) { avt_set_error("avt_get_normal_equations: no optimize call has run on the resident frames"); return 1; }
-    const AvtDims& d = c->dm.d;
-    HIP_OK(hipSetDevice(c->device));
-    // optimize() does not build the system of its last trial point (only that point's cost is needed): evaluate the data term
-    // at the CURRENT point here - trial point := current point (SOLVE_INIT), one full evaluation, one reduction - with the
-    // correspondences of the last ICP iteration.  The current point, its cost and the LM state are left untouched.
-    const int G_keep = c->fb.G;
-    c->fb.G = choose_G(c->nframes, 1, c->tun);
-    c->fb.f0 = 0;
-    c->cur_stream = c->stream;
-    // the form of the data term: the one selected (AUTO: the one the last optimize() ran); what that form needs of the resident
-    // correspondences - moments or matched-point records - is made here if the last optimize() ran the other form
-    const bool want_mom = c->dm.d.mom_ok && (c->data_term == AVT_DATA_TERM_MOMENTS || (c->data_term == AVT_DATA_TERM_AUTO && c->last_run_moments));
-    const int use_moments_keep = c->fb.use_moments;      // (restored below: plan_groups / avt_launch_shape read it)
-    c->fb.use_moments = want_mom;
-    launch_solve(c, c->nframes, SOLVE_INIT);
-    if (want_mom) {
-        if (!c->have_moments) { c->fb.const_used = (c->launch_maxN + 2047) / 2048; launch_moments(c, c->nframes); c->have_moments = true; }
-        launch_assemble(c, c->nframes);
-    } else {
-        if (!c->have_records) { c->fb.const_used = (c->launch_maxN + 255) / 256; launch_records(c, c->nframes); c->have_records = true; }
-        launch_eval(c, c->nframes, false);
-        launch_reduce(c, c->nframes);
-    }
-    c->fb.G = G_keep;
-    c->fb.use_moments = use_moments_keep;
-    if (check_launch("avt_get_normal_equations")) return 1;
-    HIP_OK(hipStreamSynchronize(c->stream));
-    AvtFrameCtl ctl;
-    HIP_OK(hipMemcpyAsync(&ctl, c->fb.ctl + frame, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    std::vector<double> buf((size_t)d.HS * d.HS);
-    HIP_OK(hipMemcpyAsync(buf.data(), c->fb.Hraw + ((size_t)frame * 2 + (1 - ctl.cur_slot)) * buf.size(), buf.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    for (int r = 0; r < d.P; ++r) {
-        if (H) for (int q = 0; q < d.P; ++q) H[(size_t)r * d.P + q] = buf[(size_t)r * d.HS + q];
-        if (g) g[r] = buf[(size_t)d.P * d.HS + r];
-    }
-    if (cost) *cost = ctl.cost_cur;
-    return 0;
-    AVT_API_GUARD_END("avt_get_normal_equations")
+    return avt_guard("avt_get_normal_equations", [&]() -> int {
+        if (!c || frame < 0 || frame >= c->nframes) { avt_set_error("avt_get_normal_equations: bad argument"); return 1; }
+        if (!c->frames_valid || !c->state_valid || c->ran_icp_iters <= 0) { avt_set_error("avt_get_normal_equations: no optimize call has run on the resident frames"); return 1; }
+        const AvtDims& d = c->dm.d;
+        AVT_HIP(hipSetDevice(c->device));
+        // optimize() does not build the system of its last trial point (only that point's cost is needed): evaluate the data term
+        // at the CURRENT point here - trial point := current point (SOLVE_INIT), one full evaluation, one reduction - with the
+        // correspondences of the last ICP iteration.  The current point, its cost and the LM state are left untouched.
+        const int G_keep = c->fb.G;
+        c->fb.G = choose_G(c->nframes, 1, c->tun);
+        c->fb.f0 = 0;
+        c->cur_stream = c->stream;
+        // the form of the data term: the one selected (AUTO: the one the last optimize() ran); what that form needs of the resident
+        // correspondences - moments or matched-point records - is made here if the last optimize() ran the other form
+        const bool want_mom = c->dm.d.mom_ok && (c->data_term == AVT_DATA_TERM_MOMENTS || (c->data_term == AVT_DATA_TERM_AUTO && c->last_run_moments));
+        const int use_moments_keep = c->fb.use_moments;      // (restored below: plan_groups / avt_launch_shape read it)
+        c->fb.use_moments = want_mom;
+        launch_solve(c, c->nframes, SOLVE_INIT);
+        if (want_mom) {
+            if (!c->have_moments) { c->fb.const_used = (c->launch_maxN + 2047) / 2048; launch_moments(c, c->nframes); c->have_moments = true; }
+            launch_assemble(c, c->nframes);
+        } else {
+            if (!c->have_records) { c->fb.const_used = (c->launch_maxN + 255) / 256; launch_records(c, c->nframes); c->have_records = true; }
+            launch_eval(c, c->nframes, false);
+            launch_reduce(c, c->nframes);
+        }
+        c->fb.G = G_keep;
+        c->fb.use_moments = use_moments_keep;
+        if (check_launch("avt_get_normal_equations")) return 1;
+        AVT_HIP(hipStreamSynchronize(c->stream));
+        AvtFrameCtl ctl;
+        AVT_HIP(hipMemcpyAsync(&ctl, c->fb.ctl + frame, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
+        AVT_HIP(hipStreamSynchronize(c->stream));
+        std::vector<double> buf((size_t)d.HS * d.HS);
+        AVT_HIP(hipMemcpyAsync(buf.data(), c->fb.Hraw + ((size_t)frame * 2 + (1 - ctl.cur_slot)) * buf.size(), buf.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        AVT_HIP(hipStreamSynchronize(c->stream));
+        for (int r = 0; r < d.P; ++r) {
+            if (H) for (int q = 0; q < d.P; ++q) H[(size_t)r * d.P + q] = buf[(size_t)r * d.HS + q];
+            if (g) g[r] = buf[(size_t)d.P * d.HS + r];
+        }
+        if (cost) *cost = ctl.cost_cur;
+        return 0;
+    });
 }
 
 int avt_debug_mfma_count(avt_ctx* c, int frame, long long* eval_rows, long long* moments, long long* solve) {
-    AVT_API_GUARD_BEGIN
-    if (!c || frame < 0 || frame >= c->nframes) { avt_set_error("avt_debug_mfma_count: bad argument"); return 1; }
-    if (!c->frames_valid || c->ran_icp_iters <= 0) { avt_set_error("avt_debug_mfma_count: no optimize call has run on the resident frames"); return 1; }
-    const AvtDims& d = c->dm.d;
-    HIP_OK(hipSetDevice(c->device));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    if (solve) *solve = avt_solve_mfma_count(d);
-    if (moments) {
-        *moments = -1;
-        if (d.mom_ok) {
-            std::vector<int> cnt(d.V);
-            HIP_OK(hipMemcpyAsync(cnt.data(), c->fb.cnt + (size_t)frame * d.V, cnt.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-            HIP_OK(hipStreamSynchronize(c->stream));
-            *moments = avt_moments_mfma_count(c->model, cnt.data());
+    return avt_guard("avt_debug_mfma_count", [&]() -> int {
+        if (!c || frame < 0 || frame >= c->nframes) { avt_set_error("avt_debug_mfma_count: bad argument"); return 1; }
+        if (!c->frames_valid || c->ran_icp_iters <= 0) { avt_set_error("avt_debug_mfma_count: no optimize call has run on the resident frames"); return 1; }
+        const AvtDims& d = c->dm.d;
+        AVT_HIP(hipSetDevice(c->device));
+        AVT_HIP(hipStreamSynchronize(c->stream));
+        if (solve) *solve = avt_solve_mfma_count(d);
+        if (moments) {
+            *moments = -1;
+            if (d.mom_ok) {
+                std::vector<int> cnt(d.V);
+                AVT_HIP(hipMemcpyAsync(cnt.data(), c->fb.cnt + (size_t)frame * d.V, cnt.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+                AVT_HIP(hipStreamSynchronize(c->stream));
+                *moments = avt_moments_mfma_count(c->model, cnt.data());
+            }
         }
-    }
-    if (eval_rows) {
-        *eval_rows = -1;
-        if (c->have_records && d.NT <= 6) {
-            // k_records leaves one word per batch of 16 matched points: bits 0..23 = the live tile pairs (avt_eval.hip); k_eval runs the
-            // 12 k-steps (48 rows / 4) of every live pair - the split pair's are dealt over the four waves, 12 in total all the same
-            AvtFrameCtl ctl;
-            HIP_OK(hipMemcpyAsync(&ctl, c->fb.ctl + frame, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
-            HIP_OK(hipStreamSynchronize(c->stream));
-            const int nb = (ctl.M + AVT_EVAL_PTS - 1) / AVT_EVAL_PTS;
-            std::vector<int> bm(std::max(nb, 1));
-            HIP_OK(hipMemcpyAsync(bm.data(), c->fb.bmask + (size_t)frame * d.nb_max, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-            HIP_OK(hipStreamSynchronize(c->stream));
-            long long n = 0;
-            for (int b = 0; b < nb; ++b) n += 12ll * __builtin_popcount((unsigned)bm[b] & 0xffffffu);
-            *eval_rows = n;
+        if (eval_rows) {
+            *eval_rows = -1;
+            if (c->have_records && d.NT <= 6) {
+                // k_records leaves one word per batch of 16 matched points: bits 0..23 = the live tile pairs (avt_eval.hip); k_eval runs the
+                // 12 k-steps (48 rows / 4) of every live pair - the split pair's are dealt over the four waves, 12 in total all the same
+                AvtFrameCtl ctl;
+                AVT_HIP(hipMemcpyAsync(&ctl, c->fb.ctl + frame, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
+                AVT_HIP(hipStreamSynchronize(c->stream));
+                const int nb = (ctl.M + AVT_EVAL_PTS - 1) / AVT_EVAL_PTS;
+                std::vector<int> bm(std::max(nb, 1));
+                AVT_HIP(hipMemcpyAsync(bm.data(), c->fb.bmask + (size_t)frame * d.nb_max, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+                AVT_HIP(hipStreamSynchronize(c->stream));
+                long long n = 0;
+                for (int b = 0; b < nb; ++b) n += 12ll * __builtin_popcount((unsigned)bm[b] & 0xffffffu);
+                *eval_rows = n;
+            }
         }
-    }
-    return 0;
-    AVT_API_GUARD_END("avt_debug_mfma_count")
+        return 0;
+    });
 }
 
 int avt_ctx_get_tuning(avt_ctx* c, avt_tuning* out) {
@@ -1258,22 +1218,22 @@ int avt_ctx_get_tuning(avt_ctx* c, avt_tuning* out) {
 }
 
 int avt_ctx_set_tuning(avt_ctx* c, const avt_tuning* t) {
-    AVT_API_GUARD_BEGIN
-    if (!c || !t) { avt_set_error("avt_ctx_set_tuning: null argument"); return 1; }
-    if (validate_tuning(*t)) return 1;
-    HIP_OK(hipSetDevice(c->device));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    {   // the launch sequences captured so far were made with the old knobs
-        std::lock_guard<std::mutex> graph_lock(g_graph_mutex);
-        for (auto& e : c->graphs) (void)hipGraphExecDestroy(e.exec);
-        c->graphs.clear();
-    }
-    c->tun = *t;
-    c->vis_frame_min = avt_visibility_frame_lds(c->dm.d) <= 150 * 1024 ? c->tun.vis_frame_min : 0;
-    c->fb.ride_timeout = c->tun.ride_timeout_us * 100;
-    c->fb.xcd_frames = c->tun.xcd_frames;
-    return 0;
-    AVT_API_GUARD_END("avt_ctx_set_tuning")
+    return avt_guard("avt_ctx_set_tuning", [&]() -> int {
+        if (!c || !t) { avt_set_error("avt_ctx_set_tuning: null argument"); return 1; }
+        if (validate_tuning(*t)) return 1;
+        AVT_HIP(hipSetDevice(c->device));
+        AVT_HIP(hipStreamSynchronize(c->stream));
+        {   // the launch sequences captured so far were made with the old knobs
+            std::lock_guard<std::mutex> graph_lock(g_graph_mutex);
+            for (auto& e : c->graphs) (void)hipGraphExecDestroy(e.exec);
+            c->graphs.clear();
+        }
+        c->tun = *t;
+        c->vis_frame_min = avt_visibility_frame_lds(c->dm.d) <= 150 * 1024 ? c->tun.vis_frame_min : 0;
+        c->fb.ride_timeout = c->tun.ride_timeout_us * 100;
+        c->fb.xcd_frames = c->tun.xcd_frames;
+        return 0;
+    });
 }
 
 int avt_set_data_term(avt_ctx* c, int form) {
@@ -1287,10 +1247,10 @@ int avt_get_data_term(avt_ctx* c) { return c ? c->data_term : -1; }
 
 int avt_debug_trace(avt_ctx* c, int frame, double* out64) {
     if (!c || !out64 || frame < 0 || frame >= c->fb.max_frames) { avt_set_error("avt_debug_trace: bad argument"); return 1; }
-    HIP_OK(hipSetDevice(c->device));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    HIP_OK(hipMemcpyAsync(out64, c->fb.trace + (size_t)frame * 64, 64 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
+    AVT_HIP(hipSetDevice(c->device));
+    AVT_HIP(hipStreamSynchronize(c->stream));
+    AVT_HIP(hipMemcpyAsync(out64, c->fb.trace + (size_t)frame * 64, 64 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    AVT_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }
 
@@ -1322,12 +1282,12 @@ int avt_profile_select(avt_ctx* c, unsigned mask) {
 
 int avt_profile_end(avt_ctx* c, avt_profile* out) {
     if (!c || !out) { avt_set_error("avt_profile_end: null argument"); return 1; }
-    HIP_OK(hipSetDevice(c->device));
-    HIP_OK(hipStreamSynchronize(c->stream));
+    AVT_HIP(hipSetDevice(c->device));
+    AVT_HIP(hipStreamSynchronize(c->stream));
     std::memset(out, 0, sizeof(*out));
     for (auto& rec : c->prof_events) {
         float ms = 0.f;
-        HIP_OK(hipEventElapsedTime(&ms, rec.second.first, rec.second.second));
+        AVT_HIP(hipEventElapsedTime(&ms, rec.second.first, rec.second.second));
         out->ms[rec.first] += ms;
         out->launches[rec.first] += 1;
     }

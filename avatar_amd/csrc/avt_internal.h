@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/avt.h"
+#include "avt_host.h"
 
 #define AVT_ANC_MAX 16        // max deduplicated ancestors per skin point (SMPL needs <= 12)
 #define AVT_TILE 16           // MFMA f64 16x16x4 tile edge
@@ -368,10 +369,9 @@ struct avt_ctx {
     char* host_pin; size_t host_pin_cap;
     bool results_fresh;              // fb.results describes the resident states (the last optimize() packed them and nothing changed them since)
     // persistent scratch of avt_synth_render_frames (z-buffer keys, labels, block counts), grown on demand
-    unsigned long long* render_zkey; unsigned char* render_label; int* render_block; size_t render_cap_pix; size_t render_cap_blk;
+    DevBuf<unsigned long long> render_zkey; DevBuf<unsigned char> render_label; DevBuf<int> render_block;
     // painter's-order mode only: second key image, float depth image, per-face sort key / order position / edge-on flag
-    unsigned long long* render_mkey; float* render_depth; float* render_fkey; int* render_frank; unsigned char* render_fedge;
-    size_t render_cap_paint_pix; size_t render_cap_paint_face;
+    DevBuf<unsigned long long> render_mkey; DevBuf<float> render_depth, render_fkey; DevBuf<int> render_frank; DevBuf<unsigned char> render_fedge;
     int render_img_frames, render_img_w, render_img_h;   // what render_depth / render_label hold (avt_synth_render_images); 0 = nothing
     // avt_optimize_resident_budgets, allocated on its first call: the budget word of every frame, one hold block per frame
     // (avt_budget_hold_doubles), and what budget[] was last set to (a repeated pattern is not uploaded again)

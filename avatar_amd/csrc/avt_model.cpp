@@ -7,7 +7,6 @@
 //     deduplicated ancestor lists and the shape tables S, Sp;
 //   * GaussianMixture::load factorisations (GaussianMixture.cpp:44-76): Cholesky of the precision, consts.
 // and lays everything out SoA for coalesced device access.
-#include <exception>
 #include <algorithm>
 #include <array>
 #include <cmath>
@@ -676,8 +675,6 @@ extern "C" int avt_model_tile_layout(const avt_model* m, int* ntiles, int* tile_
 // ---- exported entry points of the functions above: no C++ exception crosses the C ABI
 extern "C" {
 int avt_model_create(const avt_model_desc* desc, avt_model** out) {
-    try { return avt_model_create_impl(desc, out); }
-    catch (const std::exception& e) { avt_set_error(std::string("avt_model_create: ") + e.what()); return 1; }
-    catch (...) { avt_set_error("avt_model_create: unknown exception"); return 1; }
+    return avt_guard("avt_model_create", [&]() -> int { return avt_model_create_impl(desc, out); });
 }
 }  // extern "C"

@@ -11,7 +11,6 @@
 // this translation unit is built with -ffp-contract=off and uses the same float expressions, and depth ties go to the
 // lowest face index (64-bit atomicMin on (depth bits, face id)) exactly like the host's in-order strict '<' test.
 #include <algorithm>
-#include <exception>
 #include <string>
 #include <vector>
 
@@ -692,32 +691,24 @@ struct avt_renderer {
     int n_images = 0, rendered = 0;                 // resident avatars; AVT_RENDER_* bits of the last run
     std::vector<int> mesh_soa, main_joint;
     std::vector<char> has_joints;
-    int *d_mesh = nullptr, *d_vf_start = nullptr, *d_vf = nullptr, *d_vpart = nullptr;
-    double *d_cloud = nullptr, *d_joints = nullptr, *d_fnorm = nullptr, *d_vnorm = nullptr;
-    float2 *d_proj = nullptr, *d_jproj = nullptr;
-    float *d_fkey = nullptr, *d_lam = nullptr;
-    unsigned char* d_fflag = nullptr;
-    int *d_order = nullptr, *d_rank = nullptr;
-    unsigned *d_dkey = nullptr, *d_mkey = nullptr, *d_lkey = nullptr;
-    int* d_faces = nullptr;
-    float* d_depth = nullptr;
-    unsigned char *d_mask = nullptr, *d_lambert = nullptr;
+    DevBuf<int> d_mesh, d_vf_start, d_vf, d_vpart;
+    DevBuf<double> d_cloud, d_joints, d_fnorm, d_vnorm;
+    DevBuf<float2> d_proj, d_jproj;
+    DevBuf<float> d_fkey, d_lam;
+    DevBuf<unsigned char> d_fflag;
+    DevBuf<int> d_order, d_rank;
+    DevBuf<unsigned> d_dkey, d_mkey, d_lkey;
+    DevBuf<int> d_faces;
+    DevBuf<float> d_depth;
+    DevBuf<unsigned char> d_mask, d_lambert;
 };
 
 namespace {
 
-#define RD_HIP(x)                                                                                       \
-    do {                                                                                                \
-        const hipError_t e_ = (x);                                                                      \
-        if (e_ != hipSuccess) { avt_set_error(std::string(#x) + ": " + hipGetErrorString(e_)); return 1; } \
-    } while (0)
-
+// every buffer is allocated once, at its full size for max_images.  No kernel in this file is known to read the 16 bytes of
+// slack behind each (none uses vector loads); they stay so that the byte counts handed to hipMalloc do not change
 template <class T>
-int rd_alloc(T** p, size_t n) {
-    if (*p) return 0;
-    RD_HIP(hipMalloc((void**)p, n * sizeof(T) + 16));
-    return 0;
-}
+int rd_alloc(DevBuf<T>& b, size_t n) { return b.reserve(n, 16); }
 
 int rd_create(int device, const avt_model* m, int W, int H, float fx, float fy, float cx, float cy, int cap, avt_renderer** out) {
     if (!m || !out || W <= 0 || H <= 0 || cap <= 0 || (long long)W * H >= (1ll << 31) || (long long)W * H * cap >= (1ll << 40)) {
@@ -726,7 +717,7 @@ int rd_create(int device, const avt_model* m, int W, int H, float fx, float fy, 
     }
     const int V = m->d.V, F = m->d.F, J = m->d.J;
     if (F <= 0 || V <= 0 || F >= (1 << 30)) { avt_set_error("avt_renderer_create: the model has no faces"); return 1; }
-    RD_HIP(hipSetDevice(device));
+    AVT_HIP(hipSetDevice(device));
     avt_renderer* r = new avt_renderer();
     r->device = device; r->V = V; r->F = F; r->J = J; r->W = W; r->H = H; r->cap = cap;
     r->fx = fx; r->fy = fy; r->cx = cx; r->cy = cy;
@@ -747,11 +738,11 @@ int rd_create(int device, const avt_model* m, int W, int H, float fx, float fy, 
         return fail();
     }
     const size_t ci = (size_t)cap;
-    if (rd_alloc(&r->d_mesh, (size_t)3 * F) || rd_alloc(&r->d_vf_start, (size_t)V + 1) || rd_alloc(&r->d_vf, (size_t)3 * F) ||
-        rd_alloc(&r->d_vpart, (size_t)V) || rd_alloc(&r->d_cloud, ci * 3 * V) || rd_alloc(&r->d_joints, ci * 3 * (J > 0 ? J : 1)) ||
-        rd_alloc(&r->d_fnorm, ci * 3 * F) || rd_alloc(&r->d_proj, ci * V) || rd_alloc(&r->d_jproj, ci * (J > 0 ? J : 1)) ||
-        rd_alloc(&r->d_fkey, ci * F) || rd_alloc(&r->d_lam, ci * V) || rd_alloc(&r->d_vnorm, ci * 3 * V) || rd_alloc(&r->d_fflag, ci * F) || rd_alloc(&r->d_order, ci * F) ||
-        rd_alloc(&r->d_rank, ci * F))
+    if (rd_alloc(r->d_mesh, (size_t)3 * F) || rd_alloc(r->d_vf_start, (size_t)V + 1) || rd_alloc(r->d_vf, (size_t)3 * F) ||
+        rd_alloc(r->d_vpart, (size_t)V) || rd_alloc(r->d_cloud, ci * 3 * V) || rd_alloc(r->d_joints, ci * 3 * (J > 0 ? J : 1)) ||
+        rd_alloc(r->d_fnorm, ci * 3 * F) || rd_alloc(r->d_proj, ci * V) || rd_alloc(r->d_jproj, ci * (J > 0 ? J : 1)) ||
+        rd_alloc(r->d_fkey, ci * F) || rd_alloc(r->d_lam, ci * V) || rd_alloc(r->d_vnorm, ci * 3 * V) || rd_alloc(r->d_fflag, ci * F) || rd_alloc(r->d_order, ci * F) ||
+        rd_alloc(r->d_rank, ci * F))
         return fail();
     hipError_t e = hipMemcpyAsync(r->d_mesh, r->mesh_soa.data(), (size_t)3 * F * sizeof(int), hipMemcpyHostToDevice, r->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(r->d_vf_start, start.data(), ((size_t)V + 1) * sizeof(int), hipMemcpyHostToDevice, r->stream);
@@ -772,18 +763,18 @@ int rd_set_part_map(avt_renderer* r, int n, const int* map) {
         if (map && n > 0 && (j < 0 || j >= n)) { avt_set_error("avt_renderer_set_part_map: the part map has fewer entries than the model's joints"); return 1; }
         vp[(size_t)v] = (map && n > 0) ? map[j] : j;
     }
-    RD_HIP(hipSetDevice(r->device));
-    RD_HIP(hipMemcpyAsync(r->d_vpart, vp.data(), (size_t)r->V * sizeof(int), hipMemcpyHostToDevice, r->stream));
-    RD_HIP(hipStreamSynchronize(r->stream));
+    AVT_HIP(hipSetDevice(r->device));
+    AVT_HIP(hipMemcpyAsync(r->d_vpart, vp.data(), (size_t)r->V * sizeof(int), hipMemcpyHostToDevice, r->stream));
+    AVT_HIP(hipStreamSynchronize(r->stream));
     return 0;
 }
 
 int rd_upload(avt_renderer* r, int n, const double* clouds, const double* joints) {
     if (!r || !clouds || n <= 0 || n > r->cap) { avt_set_error("avt_renderer_upload: bad arguments (1 <= n_images <= max_images)"); return 1; }
-    RD_HIP(hipSetDevice(r->device));
-    RD_HIP(hipMemcpyAsync(r->d_cloud, clouds, (size_t)n * 3 * r->V * sizeof(double), hipMemcpyHostToDevice, r->stream));
-    if (joints && r->J > 0) RD_HIP(hipMemcpyAsync(r->d_joints, joints, (size_t)n * 3 * r->J * sizeof(double), hipMemcpyHostToDevice, r->stream));
-    RD_HIP(hipStreamSynchronize(r->stream));
+    AVT_HIP(hipSetDevice(r->device));
+    AVT_HIP(hipMemcpyAsync(r->d_cloud, clouds, (size_t)n * 3 * r->V * sizeof(double), hipMemcpyHostToDevice, r->stream));
+    if (joints && r->J > 0) AVT_HIP(hipMemcpyAsync(r->d_joints, joints, (size_t)n * 3 * r->J * sizeof(double), hipMemcpyHostToDevice, r->stream));
+    AVT_HIP(hipStreamSynchronize(r->stream));
     for (int i = 0; i < n; ++i) r->has_joints[(size_t)i] = joints ? 1 : 0;
     r->n_images = n; r->rendered = -1;
     return 0;
@@ -799,22 +790,22 @@ int rd_from_ctx(avt_renderer* r, avt_ctx* c, int n, const int* frames) {
         const int f = frames ? frames[i] : i;
         if (f < 0 || f >= c->fb.max_frames) { avt_set_error("avt_renderer_from_ctx: frame index out of range"); return 1; }
     }
-    RD_HIP(hipSetDevice(r->device));
+    AVT_HIP(hipSetDevice(r->device));
     // after everything queued on the context (its side streams join its main stream), and before anything queued on it later
-    RD_HIP(hipEventRecord(r->ev_in, c->stream));
-    RD_HIP(hipStreamWaitEvent(r->stream, r->ev_in, 0));
+    AVT_HIP(hipEventRecord(r->ev_in, c->stream));
+    AVT_HIP(hipStreamWaitEvent(r->stream, r->ev_in, 0));
     const size_t cb = (size_t)3 * r->V * sizeof(double), jb = (size_t)3 * r->J * sizeof(double);
     for (int i = 0; i < n;) {
         const int f = frames ? frames[i] : i;
         int run = 1;                                                   // consecutive frames go in one copy
         while (i + run < n && (frames ? frames[i + run] : i + run) == f + run) ++run;
-        RD_HIP(hipMemcpyAsync(r->d_cloud + (size_t)i * 3 * r->V, c->fb.cloud + (size_t)f * 3 * r->V, run * cb, hipMemcpyDeviceToDevice, r->stream));
+        AVT_HIP(hipMemcpyAsync(r->d_cloud + (size_t)i * 3 * r->V, c->fb.cloud + (size_t)f * 3 * r->V, run * cb, hipMemcpyDeviceToDevice, r->stream));
         if (r->J > 0)
-            RD_HIP(hipMemcpyAsync(r->d_joints + (size_t)i * 3 * r->J, c->fb.jointpos + (size_t)f * 3 * r->J, run * jb, hipMemcpyDeviceToDevice, r->stream));
+            AVT_HIP(hipMemcpyAsync(r->d_joints + (size_t)i * 3 * r->J, c->fb.jointpos + (size_t)f * 3 * r->J, run * jb, hipMemcpyDeviceToDevice, r->stream));
         i += run;
     }
-    RD_HIP(hipEventRecord(r->ev_out, r->stream));
-    RD_HIP(hipStreamWaitEvent(c->stream, r->ev_out, 0));
+    AVT_HIP(hipEventRecord(r->ev_out, r->stream));
+    AVT_HIP(hipStreamWaitEvent(c->stream, r->ev_out, 0));
     for (int i = 0; i < n; ++i) r->has_joints[(size_t)i] = 1;
     r->n_images = n; r->rendered = -1;
     return 0;
@@ -823,19 +814,19 @@ int rd_from_ctx(avt_renderer* r, avt_ctx* c, int n, const int* frames) {
 int rd_run(avt_renderer* r, int what) {
     if (!r || r->n_images <= 0) { avt_set_error("avt_renderer_run: no avatars resident"); return 1; }
     if (what & ~(AVT_RENDER_DEPTH | AVT_RENDER_PART_MASK | AVT_RENDER_LAMBERT | AVT_RENDER_FACES)) { avt_set_error("avt_renderer_run: unknown output bits"); return 1; }
-    RD_HIP(hipSetDevice(r->device));
+    AVT_HIP(hipSetDevice(r->device));
     const int n = r->n_images, V = r->V, F = r->F, J = r->J, W = r->W, H = r->H;
     const size_t npix = (size_t)W * H, tot = npix * n, ci = (size_t)r->cap * npix;
     RendImgs im{nullptr, nullptr, nullptr, nullptr};
-    if (what & AVT_RENDER_DEPTH) { if (rd_alloc(&r->d_dkey, ci) || rd_alloc(&r->d_depth, ci)) return 1; im.dkey = r->d_dkey; }
-    if (what & AVT_RENDER_PART_MASK) { if (rd_alloc(&r->d_mkey, ci) || rd_alloc(&r->d_mask, ci)) return 1; im.mkey = r->d_mkey; }
-    if (what & AVT_RENDER_LAMBERT) { if (rd_alloc(&r->d_lkey, ci) || rd_alloc(&r->d_lambert, ci)) return 1; im.lkey = r->d_lkey; }
-    if (what & AVT_RENDER_FACES) { if (rd_alloc(&r->d_faces, ci)) return 1; im.faces = r->d_faces; }
+    if (what & AVT_RENDER_DEPTH) { if (rd_alloc(r->d_dkey, ci) || rd_alloc(r->d_depth, ci)) return 1; im.dkey = r->d_dkey; }
+    if (what & AVT_RENDER_PART_MASK) { if (rd_alloc(r->d_mkey, ci) || rd_alloc(r->d_mask, ci)) return 1; im.mkey = r->d_mkey; }
+    if (what & AVT_RENDER_LAMBERT) { if (rd_alloc(r->d_lkey, ci) || rd_alloc(r->d_lambert, ci)) return 1; im.lkey = r->d_lkey; }
+    if (what & AVT_RENDER_FACES) { if (rd_alloc(r->d_faces, ci)) return 1; im.faces = r->d_faces; }
     hipStream_t s = r->stream;
-    if (im.dkey) RD_HIP(hipMemsetAsync(im.dkey, 0, tot * sizeof(unsigned), s));
-    if (im.mkey) RD_HIP(hipMemsetAsync(im.mkey, 0, tot * sizeof(unsigned), s));
-    if (im.lkey) RD_HIP(hipMemsetAsync(im.lkey, 0, tot * sizeof(unsigned), s));
-    if (im.faces) RD_HIP(hipMemsetAsync(im.faces, 0xFF, tot * sizeof(int), s));            // -1
+    if (im.dkey) AVT_HIP(hipMemsetAsync(im.dkey, 0, tot * sizeof(unsigned), s));
+    if (im.mkey) AVT_HIP(hipMemsetAsync(im.mkey, 0, tot * sizeof(unsigned), s));
+    if (im.lkey) AVT_HIP(hipMemsetAsync(im.lkey, 0, tot * sizeof(unsigned), s));
+    if (im.faces) AVT_HIP(hipMemsetAsync(im.faces, 0xFF, tot * sizeof(int), s));            // -1
     const double fx = r->fx, fy = r->fy, cx = r->cx, cy = r->cy;                           // float intrinsics promoted (AvatarRenderer.cpp:16-19)
     const int vb = (std::max(V, J) + 255) / 256, fb = (F + 255) / 256;
     hipLaunchKernelGGL(k_rend_project, dim3(vb, n), dim3(256), 0, s, r->d_cloud, r->d_joints, r->d_proj, r->d_jproj, V, J, fx, fy, cx, cy);
@@ -867,31 +858,31 @@ int rd_download(avt_renderer* r, int image, float* depth, unsigned char* mask, u
         avt_set_error("avt_renderer_download: an image the last run did not render was asked for");
         return 1;
     }
-    RD_HIP(hipSetDevice(r->device));
+    AVT_HIP(hipSetDevice(r->device));
     const size_t npix = (size_t)r->W * r->H, o = (size_t)image * npix;
-    if (depth) RD_HIP(hipMemcpyAsync(depth, r->d_depth + o, npix * sizeof(float), hipMemcpyDeviceToHost, r->stream));
-    if (mask) RD_HIP(hipMemcpyAsync(mask, r->d_mask + o, npix, hipMemcpyDeviceToHost, r->stream));
-    if (lam) RD_HIP(hipMemcpyAsync(lam, r->d_lambert + o, npix, hipMemcpyDeviceToHost, r->stream));
-    if (faces) RD_HIP(hipMemcpyAsync(faces, r->d_faces + o, npix * sizeof(int), hipMemcpyDeviceToHost, r->stream));
-    RD_HIP(hipStreamSynchronize(r->stream));
+    if (depth) AVT_HIP(hipMemcpyAsync(depth, r->d_depth + o, npix * sizeof(float), hipMemcpyDeviceToHost, r->stream));
+    if (mask) AVT_HIP(hipMemcpyAsync(mask, r->d_mask + o, npix, hipMemcpyDeviceToHost, r->stream));
+    if (lam) AVT_HIP(hipMemcpyAsync(lam, r->d_lambert + o, npix, hipMemcpyDeviceToHost, r->stream));
+    if (faces) AVT_HIP(hipMemcpyAsync(faces, r->d_faces + o, npix * sizeof(int), hipMemcpyDeviceToHost, r->stream));
+    AVT_HIP(hipStreamSynchronize(r->stream));
     return 0;
 }
 
 int rd_projection(avt_renderer* r, int image, float* pts, float* jts, float* keys, int* faces, int* face_pos) {
     if (!r || image < 0 || image >= r->n_images || r->rendered < 0) { avt_set_error("avt_renderer_projection: bad image, or no run since the avatars changed"); return 1; }
     if (jts && !r->has_joints[(size_t)image]) { avt_set_error("avt_renderer_projection: no joints were given for this image"); return 1; }
-    RD_HIP(hipSetDevice(r->device));
+    AVT_HIP(hipSetDevice(r->device));
     const int F = r->F;
     std::vector<int> order((size_t)F);
     std::vector<float> fk((size_t)F);
-    if (pts) RD_HIP(hipMemcpyAsync(pts, r->d_proj + (size_t)image * r->V, (size_t)r->V * sizeof(float2), hipMemcpyDeviceToHost, r->stream));
-    if (jts && r->J > 0) RD_HIP(hipMemcpyAsync(jts, r->d_jproj + (size_t)image * r->J, (size_t)r->J * sizeof(float2), hipMemcpyDeviceToHost, r->stream));
-    if (face_pos) RD_HIP(hipMemcpyAsync(face_pos, r->d_rank + (size_t)image * F, (size_t)F * sizeof(int), hipMemcpyDeviceToHost, r->stream));
+    if (pts) AVT_HIP(hipMemcpyAsync(pts, r->d_proj + (size_t)image * r->V, (size_t)r->V * sizeof(float2), hipMemcpyDeviceToHost, r->stream));
+    if (jts && r->J > 0) AVT_HIP(hipMemcpyAsync(jts, r->d_jproj + (size_t)image * r->J, (size_t)r->J * sizeof(float2), hipMemcpyDeviceToHost, r->stream));
+    if (face_pos) AVT_HIP(hipMemcpyAsync(face_pos, r->d_rank + (size_t)image * F, (size_t)F * sizeof(int), hipMemcpyDeviceToHost, r->stream));
     if (keys || faces) {
-        RD_HIP(hipMemcpyAsync(order.data(), r->d_order + (size_t)image * F, (size_t)F * sizeof(int), hipMemcpyDeviceToHost, r->stream));
-        RD_HIP(hipMemcpyAsync(fk.data(), r->d_fkey + (size_t)image * F, (size_t)F * sizeof(float), hipMemcpyDeviceToHost, r->stream));
+        AVT_HIP(hipMemcpyAsync(order.data(), r->d_order + (size_t)image * F, (size_t)F * sizeof(int), hipMemcpyDeviceToHost, r->stream));
+        AVT_HIP(hipMemcpyAsync(fk.data(), r->d_fkey + (size_t)image * F, (size_t)F * sizeof(float), hipMemcpyDeviceToHost, r->stream));
     }
-    RD_HIP(hipStreamSynchronize(r->stream));
+    AVT_HIP(hipStreamSynchronize(r->stream));
     for (int p = 0; p < F && (keys || faces); ++p) {
         const int f = order[(size_t)p];
         if (f < 0 || f >= F) { avt_set_error("avt_renderer_projection: the painter order is not a permutation"); return AVT_STATUS_DEVICE_FAULT; }
@@ -906,35 +897,27 @@ int rd_shading(avt_renderer* r, int image, double* normals, float* lam) {
         avt_set_error("avt_renderer_vertex_shading: bad image, or the last run did not render the Lambert image");
         return 1;
     }
-    RD_HIP(hipSetDevice(r->device));
+    AVT_HIP(hipSetDevice(r->device));
     const size_t V = (size_t)r->V;
-    if (normals) RD_HIP(hipMemcpyAsync(normals, r->d_vnorm + (size_t)image * 3 * V, 3 * V * sizeof(double), hipMemcpyDeviceToHost, r->stream));
-    if (lam) RD_HIP(hipMemcpyAsync(lam, r->d_lam + (size_t)image * V, V * sizeof(float), hipMemcpyDeviceToHost, r->stream));
-    RD_HIP(hipStreamSynchronize(r->stream));
+    if (normals) AVT_HIP(hipMemcpyAsync(normals, r->d_vnorm + (size_t)image * 3 * V, 3 * V * sizeof(double), hipMemcpyDeviceToHost, r->stream));
+    if (lam) AVT_HIP(hipMemcpyAsync(lam, r->d_lam + (size_t)image * V, V * sizeof(float), hipMemcpyDeviceToHost, r->stream));
+    AVT_HIP(hipStreamSynchronize(r->stream));
     return 0;
 }
 
 }  // namespace
 
-#define RD_ENTRY(name, call)                                                                       \
-    try { return call; }                                                                           \
-    catch (const std::exception& e) { avt_set_error(std::string(name ": ") + e.what()); return 1; } \
-    catch (...) { avt_set_error(name ": unknown exception"); return 1; }
-
 extern "C" {
 int avt_renderer_create(int device, const avt_model* m, int width, int height, float fx, float fy, float cx, float cy, int max_images,
                         avt_renderer** out) {
-    RD_ENTRY("avt_renderer_create", rd_create(device, m, width, height, fx, fy, cx, cy, max_images, out))
+    return avt_guard("avt_renderer_create", [&]() -> int { return rd_create(device, m, width, height, fx, fy, cx, cy, max_images, out); });
 }
 
 void avt_renderer_destroy(avt_renderer* r) {
     if (!r) return;
     (void)hipSetDevice(r->device);
     if (r->stream) (void)hipStreamSynchronize(r->stream);
-    for (void* p : {(void*)r->d_mesh, (void*)r->d_vf_start, (void*)r->d_vf, (void*)r->d_vpart, (void*)r->d_cloud, (void*)r->d_joints, (void*)r->d_fnorm,
-                    (void*)r->d_proj, (void*)r->d_jproj, (void*)r->d_fkey, (void*)r->d_lam, (void*)r->d_vnorm, (void*)r->d_fflag, (void*)r->d_order, (void*)r->d_rank,
-                    (void*)r->d_dkey, (void*)r->d_mkey, (void*)r->d_lkey, (void*)r->d_faces, (void*)r->d_depth, (void*)r->d_mask, (void*)r->d_lambert})
-        if (p) (void)hipFree(p);
+    // the buffers go with `delete`, after the events and the stream: the stream has just been drained, so nothing is queued on them either way
     if (r->ev_in) (void)hipEventDestroy(r->ev_in);
     if (r->ev_out) (void)hipEventDestroy(r->ev_out);
     if (r->stream) (void)hipStreamDestroy(r->stream);
@@ -942,23 +925,23 @@ void avt_renderer_destroy(avt_renderer* r) {
 }
 
 int avt_renderer_set_part_map(avt_renderer* r, int n_joints, const int* part_map) {
-    RD_ENTRY("avt_renderer_set_part_map", rd_set_part_map(r, n_joints, part_map))
+    return avt_guard("avt_renderer_set_part_map", [&]() -> int { return rd_set_part_map(r, n_joints, part_map); });
 }
 int avt_renderer_upload(avt_renderer* r, int n_images, const double* clouds, const double* joints) {
-    RD_ENTRY("avt_renderer_upload", rd_upload(r, n_images, clouds, joints))
+    return avt_guard("avt_renderer_upload", [&]() -> int { return rd_upload(r, n_images, clouds, joints); });
 }
 int avt_renderer_from_ctx(avt_renderer* r, avt_ctx* c, int n_images, const int* frames) {
-    RD_ENTRY("avt_renderer_from_ctx", rd_from_ctx(r, c, n_images, frames))
+    return avt_guard("avt_renderer_from_ctx", [&]() -> int { return rd_from_ctx(r, c, n_images, frames); });
 }
-int avt_renderer_run(avt_renderer* r, int what) { RD_ENTRY("avt_renderer_run", rd_run(r, what)) }
+int avt_renderer_run(avt_renderer* r, int what) { return avt_guard("avt_renderer_run", [&]() -> int { return rd_run(r, what); }); }
 int avt_renderer_download(avt_renderer* r, int image, float* depth, unsigned char* part_mask, unsigned char* lambert, int* faces) {
-    RD_ENTRY("avt_renderer_download", rd_download(r, image, depth, part_mask, lambert, faces))
+    return avt_guard("avt_renderer_download", [&]() -> int { return rd_download(r, image, depth, part_mask, lambert, faces); });
 }
 int avt_renderer_projection(avt_renderer* r, int image, float* points_2xV, float* joints_2xJ, float* face_keys, int* faces_3xF, int* face_pos) {
-    RD_ENTRY("avt_renderer_projection", rd_projection(r, image, points_2xV, joints_2xJ, face_keys, faces_3xF, face_pos))
+    return avt_guard("avt_renderer_projection", [&]() -> int { return rd_projection(r, image, points_2xV, joints_2xJ, face_keys, faces_3xF, face_pos); });
 }
 int avt_renderer_vertex_shading(avt_renderer* r, int image, double* normals_3xV, float* lambert_v) {
-    RD_ENTRY("avt_renderer_vertex_shading", rd_shading(r, image, normals_3xV, lambert_v))
+    return avt_guard("avt_renderer_vertex_shading", [&]() -> int { return rd_shading(r, image, normals_3xV, lambert_v); });
 }
 int avt_renderer_sync(avt_renderer* r) {
     if (!r) { avt_set_error("avt_renderer_sync: null handle"); return 1; }
@@ -981,9 +964,9 @@ int avt_renderer_images_for(avt_renderer* r, hipStream_t s, const float** depth,
         avt_set_error("renderer: the last run rendered no depth and part mask (avt_renderer_run(r, AVT_RENDER_DEPTH | AVT_RENDER_PART_MASK))");
         return 1;
     }
-    RD_HIP(hipSetDevice(r->device));
-    RD_HIP(hipEventRecord(r->ev_out, r->stream));
-    RD_HIP(hipStreamWaitEvent(s, r->ev_out, 0));
+    AVT_HIP(hipSetDevice(r->device));
+    AVT_HIP(hipEventRecord(r->ev_out, r->stream));
+    AVT_HIP(hipStreamWaitEvent(s, r->ev_out, 0));
     *depth = r->d_depth; *mask = r->d_mask; *n = r->n_images; *width = r->W; *height = r->H;
     return 0;
 }

@@ -3,7 +3,6 @@
 // (RTree::postProcess, RTree.cpp:3422-3449), which the reference also runs on the host.
 #include "avt_rtree.h"
 
-#include <exception>
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
@@ -14,8 +13,6 @@
 #include "avt_internal.h"
 
 namespace {
-
-#define RT_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { avt_set_error(std::string(#x) + ": " + hipGetErrorString(e_)); return 1; } } while (0)
 
 template <class T> bool get(std::istream& is, T& v) { is.read(reinterpret_cast<char*>(&v), sizeof(T)); return (bool)is; }
 template <class T> void put(std::ostream& os, T v) { os.write(reinterpret_cast<char*>(&v), sizeof(T)); }
@@ -62,29 +59,23 @@ std::vector<RtNodeDev> pack_nodes(const avt_rtree* rt) {
 
 int upload_tree(avt_rtree* rt) {
     if (rt->device < 0) return 0;   // host-only tree: file formats and post-processing work, inference refuses
-    RT_HIP(hipSetDevice(rt->device));
+    AVT_HIP(hipSetDevice(rt->device));
     const int n = (int)(rt->links.size() / 3);
     const std::vector<RtNodeDev> dev = pack_nodes(rt);
-    RT_HIP(hipStreamCreateWithFlags(&rt->stream, hipStreamNonBlocking));
-    RT_HIP(hipMalloc((void**)&rt->d_nodes, sizeof(RtNodeDev) * n));
-    RT_HIP(hipMemcpyAsync(rt->d_nodes, dev.data(), sizeof(RtNodeDev) * n, hipMemcpyHostToDevice, rt->stream));
-    RT_HIP(hipMalloc((void**)&rt->d_leaf, sizeof(float) * std::max<size_t>(1, rt->leaf_data.size())));
-    RT_HIP(hipMemcpyAsync(rt->d_leaf, rt->leaf_data.data(), sizeof(float) * rt->leaf_data.size(), hipMemcpyHostToDevice, rt->stream));
-    RT_HIP(hipStreamSynchronize(rt->stream));     // `dev` goes out of scope; the legacy stream is never used (a host thread may be capturing)
+    AVT_HIP(hipStreamCreateWithFlags(&rt->stream, hipStreamNonBlocking));
+    if (rt->d_nodes.reserve(n)) return 1;
+    AVT_HIP(hipMemcpyAsync(rt->d_nodes, dev.data(), sizeof(RtNodeDev) * n, hipMemcpyHostToDevice, rt->stream));
+    if (rt->d_leaf.reserve(std::max<size_t>(1, rt->leaf_data.size()))) return 1;   // a forest without leaves still has a table to point at
+    AVT_HIP(hipMemcpyAsync(rt->d_leaf, rt->leaf_data.data(), sizeof(float) * rt->leaf_data.size(), hipMemcpyHostToDevice, rt->stream));
+    AVT_HIP(hipStreamSynchronize(rt->stream));     // `dev` goes out of scope; the legacy stream is never used (a host thread may be capturing)
     return 0;
 }
 
 int reserve_images(avt_rtree* rt, size_t pixels) {
     if (rt->device < 0) { avt_set_error("rtree: created host-only (device < 0): inference needs a GPU"); return 1; }
-    if (pixels <= rt->cap_pixels) return 0;
-    RT_HIP(hipSetDevice(rt->device));
-    if (rt->d_depth) (void)hipFree(rt->d_depth);
-    if (rt->d_labels) (void)hipFree(rt->d_labels);
-    rt->d_depth = nullptr; rt->d_labels = nullptr; rt->cap_pixels = 0;
-    RT_HIP(hipMalloc((void**)&rt->d_depth, pixels * sizeof(float)));
-    RT_HIP(hipMalloc((void**)&rt->d_labels, pixels));
-    rt->cap_pixels = pixels;
-    return 0;
+    if (pixels <= rt->d_depth.cap && pixels <= rt->d_labels.cap) return 0;   // each on its own: a failed allocation leaves that buffer empty
+    AVT_HIP(hipSetDevice(rt->device));
+    return rt->d_depth.reserve(pixels) || rt->d_labels.reserve(pixels);
 }
 
 bool parse_part_map(std::istream& is, std::vector<int>& result, int& type) {   // RTree::readPartMap, RTree.cpp:3465-3509
@@ -168,12 +159,12 @@ struct Filler {
 int avt_rtree_refresh_leaves(avt_rtree* rt) {
     best_match_table(rt);
     if (rt->device < 0 || !rt->d_nodes) return 0;
-    RT_HIP(hipSetDevice(rt->device));
+    AVT_HIP(hipSetDevice(rt->device));
     const int n = (int)(rt->links.size() / 3);
     const std::vector<RtNodeDev> dev = pack_nodes(rt);
-    RT_HIP(hipMemcpyAsync(rt->d_nodes, dev.data(), sizeof(RtNodeDev) * n, hipMemcpyHostToDevice, rt->stream));
-    RT_HIP(hipMemcpyAsync(rt->d_leaf, rt->leaf_data.data(), sizeof(float) * rt->leaf_data.size(), hipMemcpyHostToDevice, rt->stream));
-    RT_HIP(hipStreamSynchronize(rt->stream));
+    AVT_HIP(hipMemcpyAsync(rt->d_nodes, dev.data(), sizeof(RtNodeDev) * n, hipMemcpyHostToDevice, rt->stream));
+    AVT_HIP(hipMemcpyAsync(rt->d_leaf, rt->leaf_data.data(), sizeof(float) * rt->leaf_data.size(), hipMemcpyHostToDevice, rt->stream));
+    AVT_HIP(hipStreamSynchronize(rt->stream));
     return 0;
 }
 
@@ -305,11 +296,8 @@ static int avt_rtree_export_impl(const avt_rtree* rt, const char* path) {
 
 void avt_rtree_destroy(avt_rtree* rt) {
     if (!rt) return;
-    if (rt->d_nodes) (void)hipFree(rt->d_nodes);
-    if (rt->d_leaf) (void)hipFree(rt->d_leaf);
-    if (rt->d_depth) (void)hipFree(rt->d_depth);
-    if (rt->d_labels) (void)hipFree(rt->d_labels);
-    if (rt->d_tcount) (void)hipFree(rt->d_tcount);
+    // the buffers go with `delete`, after the stream: it is drained first, so nothing is queued on them either way
+    if (rt->stream) (void)hipStreamSynchronize(rt->stream);
     if (rt->stream) (void)hipStreamDestroy(rt->stream);
     delete rt;
 }
@@ -338,8 +326,8 @@ static int avt_rtree_images_upload_impl(avt_rtree* rt, int n_images, int rows, i
     if (!rt || !depth || n_images <= 0 || rows <= 0 || cols <= 0) { avt_set_error("avt_rtree_images_upload: bad arguments"); return 1; }
     const size_t pixels = (size_t)n_images * rows * cols;
     if (reserve_images(rt, pixels)) return 1;
-    RT_HIP(hipSetDevice(rt->device));
-    RT_HIP(hipMemcpyAsync(rt->d_depth, depth, pixels * sizeof(float), hipMemcpyHostToDevice, rt->stream));
+    AVT_HIP(hipSetDevice(rt->device));
+    AVT_HIP(hipMemcpyAsync(rt->d_depth, depth, pixels * sizeof(float), hipMemcpyHostToDevice, rt->stream));
     rt->n_images = n_images; rt->rows = rows; rt->cols = cols;
     return 0;
 }
@@ -347,7 +335,7 @@ static int avt_rtree_images_upload_impl(avt_rtree* rt, int n_images, int rows, i
 int avt_rtree_predict_best_resident(avt_rtree* rt, int interval, int tlx, int tly, int brx, int bry, int fill) {
     if (!rt || rt->n_images <= 0) { avt_set_error("avt_rtree_predict_best_resident: no images resident"); return 1; }
     if (roi_ok(rt->rows, rt->cols, interval, tlx, tly, brx, bry)) return 1;
-    RT_HIP(hipSetDevice(rt->device));
+    AVT_HIP(hipSetDevice(rt->device));
     if (avt_rtree_launch_predict(rt, rt->n_images, rt->rows, rt->cols, interval, tlx, tly, brx, bry, fill)) { avt_set_error("rtree: kernel launch failed"); return 1; }
     return 0;
 }
@@ -355,14 +343,14 @@ int avt_rtree_predict_best_resident(avt_rtree* rt, int interval, int tlx, int tl
 int avt_rtree_labels_download(avt_rtree* rt, int image, unsigned char* out) {
     if (!rt || !out || image < 0 || image >= rt->n_images) { avt_set_error("avt_rtree_labels_download: bad arguments"); return 1; }
     const size_t px = (size_t)rt->rows * rt->cols;
-    RT_HIP(hipMemcpyAsync(out, rt->d_labels + px * image, px, hipMemcpyDeviceToHost, rt->stream));
-    RT_HIP(hipStreamSynchronize(rt->stream));
+    AVT_HIP(hipMemcpyAsync(out, rt->d_labels + px * image, px, hipMemcpyDeviceToHost, rt->stream));
+    AVT_HIP(hipStreamSynchronize(rt->stream));
     return 0;
 }
 
 int avt_rtree_sync(avt_rtree* rt) {
     if (!rt) { avt_set_error("avt_rtree_sync: null tree"); return 1; }
-    RT_HIP(hipStreamSynchronize(rt->stream));
+    AVT_HIP(hipStreamSynchronize(rt->stream));
     return 0;
 }
 
@@ -379,13 +367,12 @@ static int avt_rtree_predict_impl(avt_rtree* rt, const float* depth, int rows, i
     if (!rt || !depth || !dist_out || rows <= 0 || cols <= 0) { avt_set_error("avt_rtree_predict: bad arguments"); return 1; }
     if (avt_rtree_images_upload(rt, 1, rows, cols, depth)) return 1;
     const size_t n = (size_t)rt->num_parts * rows * cols;
-    float* d_out = nullptr;
-    RT_HIP(hipMalloc((void**)&d_out, n * sizeof(float)));
+    DevBuf<float> d_out;
+    if (d_out.reserve(n)) return 1;
     int rc = avt_rtree_launch_predict_dist(rt, rows, cols, d_out);
     if (rc) avt_set_error("rtree: kernel launch failed");
     if (!rc && hipMemcpyAsync(dist_out, d_out, n * sizeof(float), hipMemcpyDeviceToHost, rt->stream) != hipSuccess) { avt_set_error("rtree: download failed"); rc = 1; }
-    if (hipStreamSynchronize(rt->stream) != hipSuccess && !rc) { avt_set_error("rtree: stream failed"); rc = 1; }
-    (void)hipFree(d_out);
+    if (hipStreamSynchronize(rt->stream) != hipSuccess && !rc) { avt_set_error("rtree: stream failed"); rc = 1; }   // on every path, before d_out goes
     return rc;
 }
 
@@ -456,46 +443,32 @@ static int avt_rtree_post_process_impl(const avt_rtree* rt, unsigned char* image
 // ---- exported entry points of the functions above: no C++ exception crosses the C ABI
 extern "C" {
 int avt_rtree_create(const avt_rtree_desc* d, int device, avt_rtree** out) {
-    try { return avt_rtree_create_impl(d, device, out); }
-    catch (const std::exception& e) { avt_set_error(std::string("avt_rtree_create: ") + e.what()); return 1; }
-    catch (...) { avt_set_error("avt_rtree_create: unknown exception"); return 1; }
+    return avt_guard("avt_rtree_create", [&]() -> int { return avt_rtree_create_impl(d, device, out); });
 }
 
 int avt_rtree_load(const char* path, int device, avt_rtree** out) {
-    try { return avt_rtree_load_impl(path, device, out); }
-    catch (const std::exception& e) { avt_set_error(std::string("avt_rtree_load: ") + e.what()); return 1; }
-    catch (...) { avt_set_error("avt_rtree_load: unknown exception"); return 1; }
+    return avt_guard("avt_rtree_load", [&]() -> int { return avt_rtree_load_impl(path, device, out); });
 }
 
 int avt_rtree_export(const avt_rtree* rt, const char* path) {
-    try { return avt_rtree_export_impl(rt, path); }
-    catch (const std::exception& e) { avt_set_error(std::string("avt_rtree_export: ") + e.what()); return 1; }
-    catch (...) { avt_set_error("avt_rtree_export: unknown exception"); return 1; }
+    return avt_guard("avt_rtree_export", [&]() -> int { return avt_rtree_export_impl(rt, path); });
 }
 
 int avt_rtree_images_upload(avt_rtree* rt, int n_images, int rows, int cols, const float* depth) {
-    try { return avt_rtree_images_upload_impl(rt, n_images, rows, cols, depth); }
-    catch (const std::exception& e) { avt_set_error(std::string("avt_rtree_images_upload: ") + e.what()); return 1; }
-    catch (...) { avt_set_error("avt_rtree_images_upload: unknown exception"); return 1; }
+    return avt_guard("avt_rtree_images_upload", [&]() -> int { return avt_rtree_images_upload_impl(rt, n_images, rows, cols, depth); });
 }
 
 int avt_rtree_predict_best(avt_rtree* rt, const float* depth, int rows, int cols, int interval, int tlx, int tly, int brx, int bry, int fill,
                            unsigned char* labels_out) {
-    try { return avt_rtree_predict_best_impl(rt, depth, rows, cols, interval, tlx, tly, brx, bry, fill, labels_out); }
-    catch (const std::exception& e) { avt_set_error(std::string("avt_rtree_predict_best: ") + e.what()); return 1; }
-    catch (...) { avt_set_error("avt_rtree_predict_best: unknown exception"); return 1; }
+    return avt_guard("avt_rtree_predict_best", [&]() -> int { return avt_rtree_predict_best_impl(rt, depth, rows, cols, interval, tlx, tly, brx, bry, fill, labels_out); });
 }
 
 int avt_rtree_predict(avt_rtree* rt, const float* depth, int rows, int cols, float* dist_out) {
-    try { return avt_rtree_predict_impl(rt, depth, rows, cols, dist_out); }
-    catch (const std::exception& e) { avt_set_error(std::string("avt_rtree_predict: ") + e.what()); return 1; }
-    catch (...) { avt_set_error("avt_rtree_predict: unknown exception"); return 1; }
+    return avt_guard("avt_rtree_predict", [&]() -> int { return avt_rtree_predict_impl(rt, depth, rows, cols, dist_out); });
 }
 
 int avt_rtree_post_process(const avt_rtree* rt, unsigned char* image, int rows, int cols, double* com_pre, int com_pre_valid, int interval, int tlx,
                            int tly, int brx, int bry, double dist_to_pre_weight) {
-    try { return avt_rtree_post_process_impl(rt, image, rows, cols, com_pre, com_pre_valid, interval, tlx, tly, brx, bry, dist_to_pre_weight); }
-    catch (const std::exception& e) { avt_set_error(std::string("avt_rtree_post_process: ") + e.what()); return 1; }
-    catch (...) { avt_set_error("avt_rtree_post_process: unknown exception"); return 1; }
+    return avt_guard("avt_rtree_post_process", [&]() -> int { return avt_rtree_post_process_impl(rt, image, rows, cols, com_pre, com_pre_valid, interval, tlx, tly, brx, bry, dist_to_pre_weight); });
 }
 }  // extern "C"

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/avt_rtree.h"
+#include "avt_host.h"
 
 // one tree node as the kernel reads it: two 16-byte loads
 struct RtNodeDev {
@@ -27,13 +28,12 @@ struct avt_rtree {
     int part_map_type = 0;
     // device
     hipStream_t stream = nullptr;
-    RtNodeDev* d_nodes = nullptr;
-    float* d_leaf = nullptr;         // [n_leafs][num_parts] distributions
-    float* d_depth = nullptr;
-    unsigned char* d_labels = nullptr;
-    size_t cap_pixels = 0;           // capacity of d_depth / d_labels in pixels
+    DevBuf<RtNodeDev> d_nodes;
+    DevBuf<float> d_leaf;            // [n_leafs][num_parts] distributions
+    DevBuf<float> d_depth;           // the resident images and their labels: one capacity, in pixels
+    DevBuf<unsigned char> d_labels;
     int n_images = 0, rows = 0, cols = 0;
-    unsigned long long* d_tcount = nullptr;   // trainTransfer's (leaf, part) counts since the last avt_rtree_transfer_finish
+    DevBuf<unsigned long long> d_tcount;      // trainTransfer's (leaf, part) counts since the last avt_rtree_transfer_finish
 };
 
 int avt_rtree_launch_predict_dist(avt_rtree* rt, int rows, int cols, float* d_out);

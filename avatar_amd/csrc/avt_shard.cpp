@@ -33,15 +33,6 @@
 int avt_internal_install_frames(avt_ctx* c, int nframes, const int* counts, const double* data, const int* labels, int device_src);
 void launch_pack_results(avt_ctx* c, int nframes, double* out, int stride);
 
-#define HIP_OK(expr)                                                                          \
-    do {                                                                                      \
-        hipError_t _e = (expr);                                                               \
-        if (_e != hipSuccess) {                                                               \
-            avt_set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                 \
-            return 1;                                                                         \
-        }                                                                                     \
-    } while (0)
-
 // ---------------------------------------------------------------------------------------------------------------------
 // partition
 // ---------------------------------------------------------------------------------------------------------------------
@@ -567,10 +558,9 @@ struct avt_shard {
     hipStream_t stream = nullptr;          // exchanges that happen before a context exists (model broadcast)
     std::string backend;
     // result gather: per-rank send block and the gathered block, device
-    double* d_send = nullptr; double* d_recv = nullptr; size_t gather_cap = 0;   // doubles per rank block
+    DevBuf<double> d_send, d_recv;         // one rank block / `world` of them, in doubles
     const double* gathered = nullptr;      // where the last gather left every rank's block (d_recv; one rank: the context's own result records)
-    void* d_stage = nullptr; size_t stage_cap = 0;                              // scatter / broadcast staging, bytes
-    void* d_stage2 = nullptr; size_t stage2_cap = 0;
+    DevBuf<char> d_stage, d_stage2;        // scatter / broadcast staging, bytes
     hipStream_t gather_stream = nullptr;   // the stream the last all-gather was enqueued on
     bool self_exchange = false;            // avt_shard_set_self_exchange: a rank's own blocks go through the transport as well (dry runs)
 };
@@ -586,14 +576,9 @@ struct avt_shard {
 
 namespace {
 
-int grow(void** p, size_t* cap, size_t bytes) {
-    if (*cap >= bytes && *p) return 0;
-    if (*p) HIP_OK(hipFree(*p));
-    *p = nullptr; *cap = 0;
-    HIP_OK(hipMalloc(p, std::max<size_t>(bytes, 256)));
-    *cap = std::max<size_t>(bytes, 256);
-    return 0;
-}
+// a staging block of at least `bytes` (discarded when it grows); never under 256, so that the control words of successive
+// calls (64, 8 (world + 1) .. bytes) share one allocation
+int grow(DevBuf<char>& b, size_t bytes) { return b.reserve(std::max<size_t>(bytes, 256)); }
 
 int gather_stride(const avt_ctx* c) { return c->dm.d.xsize + AVT_SHARD_STAT_DOUBLES; }
 
@@ -612,146 +597,152 @@ extern "C" int avt_shard_unique_id(char id[AVT_SHARD_ID_BYTES]) {
 }
 
 extern "C" int avt_shard_create(int device, int rank, int world, const char id[AVT_SHARD_ID_BYTES], avt_shard** out) {
-    if (!id || !out || world <= 0 || rank < 0 || rank >= world) { avt_set_error("avt_shard_create: bad argument"); return 1; }
-    RcclApi* a = rccl_api();
-    if (!a) return 1;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { avt_set_error("avt_shard_create: device index out of range"); return 2; }
-    HIP_OK(hipSetDevice(device));
-    avt_shard* s = new avt_shard();
-    s->api = a; s->device = device; s->rank = rank; s->world = world;
-    ncclUniqueId u;
-    std::memcpy(u.internal, id, AVT_SHARD_ID_BYTES);
-    const ncclResult_t r = a->CommInitRank(&s->comm, world, u, rank);
-    if (r != ncclSuccess) {
-        avt_set_error(std::string("ncclCommInitRank: ") + a->GetErrorString(r));
-        delete s;
-        return 1;
-    }
-    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) {
-        avt_set_error("avt_shard_create: hipStreamCreate failed");
-        a->CommDestroy(s->comm);
-        delete s;
-        return 1;
-    }
-    char buf[512];
-    snprintf(buf, sizeof buf, "rccl %d.%d.%d, %s", a->version / 10000, (a->version / 100) % 100, a->version % 100, a->path.c_str());
-    s->backend = buf;
-    *out = s;
-    return 0;
+    return avt_guard("avt_shard_create", [&]() -> int {
+        if (!id || !out || world <= 0 || rank < 0 || rank >= world) { avt_set_error("avt_shard_create: bad argument"); return 1; }
+        RcclApi* a = rccl_api();
+        if (!a) return 1;
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { avt_set_error("avt_shard_create: device index out of range"); return 2; }
+        AVT_HIP(hipSetDevice(device));
+        avt_shard* s = new avt_shard();
+        s->api = a; s->device = device; s->rank = rank; s->world = world;
+        ncclUniqueId u;
+        std::memcpy(u.internal, id, AVT_SHARD_ID_BYTES);
+        const ncclResult_t r = a->CommInitRank(&s->comm, world, u, rank);
+        if (r != ncclSuccess) {
+            avt_set_error(std::string("ncclCommInitRank: ") + a->GetErrorString(r));
+            delete s;
+            return 1;
+        }
+        if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) {
+            avt_set_error("avt_shard_create: hipStreamCreate failed");
+            a->CommDestroy(s->comm);
+            delete s;
+            return 1;
+        }
+        char buf[512];
+        snprintf(buf, sizeof buf, "rccl %d.%d.%d, %s", a->version / 10000, (a->version / 100) % 100, a->version % 100, a->path.c_str());
+        s->backend = buf;
+        *out = s;
+        return 0;
+    });
 }
 
 extern "C" int avt_shard_create_loopback(int device, int rank, int world, const char* group, avt_shard** out) {
-    if (!group || !out || world <= 0 || rank < 0 || rank >= world) { avt_set_error("avt_shard_create_loopback: bad argument"); return 1; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { avt_set_error("avt_shard_create_loopback: device index out of range"); return 2; }
-    HIP_OK(hipSetDevice(device));
-    LoopGroup* g = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(loop_registry_mutex);
-        auto it = loop_registry.find(group);
-        if (it != loop_registry.end() && it->second->broken) {      // a group that timed out stays broken for its members; a fresh create under the same name starts clean
-            loop_registry.erase(it);
-            it = loop_registry.end();
+    return avt_guard("avt_shard_create_loopback", [&]() -> int {
+        if (!group || !out || world <= 0 || rank < 0 || rank >= world) { avt_set_error("avt_shard_create_loopback: bad argument"); return 1; }
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { avt_set_error("avt_shard_create_loopback: device index out of range"); return 2; }
+        AVT_HIP(hipSetDevice(device));
+        LoopGroup* g = nullptr;
+        {
+            std::lock_guard<std::mutex> lk(loop_registry_mutex);
+            auto it = loop_registry.find(group);
+            if (it != loop_registry.end() && it->second->broken) {      // a group that timed out stays broken for its members; a fresh create under the same name starts clean
+                loop_registry.erase(it);
+                it = loop_registry.end();
+            }
+            if (it == loop_registry.end()) {
+                g = new LoopGroup();
+                g->name = group; g->world = world; g->present.assign(world, 0); g->slot.assign(world, nullptr); g->mail.resize((size_t)world * world); g->outstanding.assign(world, 0);
+                if (const char* e = getenv("AVT_SHARD_LOOPBACK_TIMEOUT_S")) g->timeout_s = std::max(0.1, atof(e));
+                loop_registry[group] = g;
+            } else {
+                g = it->second;
+                if (g->world != world || g->joined >= world) { avt_set_error("avt_shard_create_loopback: group exists with another world size, or is full"); return 1; }
+                if (g->present[rank]) { avt_set_error("avt_shard_create_loopback: this rank is already a member of the group"); return 1; }
+            }
+            ++g->joined; ++g->refs; g->present[rank] = 1;
         }
-        if (it == loop_registry.end()) {
-            g = new LoopGroup();
-            g->name = group; g->world = world; g->present.assign(world, 0); g->slot.assign(world, nullptr); g->mail.resize((size_t)world * world); g->outstanding.assign(world, 0);
-            if (const char* e = getenv("AVT_SHARD_LOOPBACK_TIMEOUT_S")) g->timeout_s = std::max(0.1, atof(e));
-            loop_registry[group] = g;
-        } else {
-            g = it->second;
-            if (g->world != world || g->joined >= world) { avt_set_error("avt_shard_create_loopback: group exists with another world size, or is full"); return 1; }
-            if (g->present[rank]) { avt_set_error("avt_shard_create_loopback: this rank is already a member of the group"); return 1; }
+        avt_shard* s = new avt_shard();
+        s->api = loop_api(); s->device = device; s->rank = rank; s->world = world;
+        s->comm = (ncclComm_t) new LoopComm{g, rank};
+        if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) {
+            avt_set_error("avt_shard_create_loopback: hipStreamCreate failed");
+            s->api->CommDestroy(s->comm);
+            delete s;
+            return 1;
         }
-        ++g->joined; ++g->refs; g->present[rank] = 1;
-    }
-    avt_shard* s = new avt_shard();
-    s->api = loop_api(); s->device = device; s->rank = rank; s->world = world;
-    s->comm = (ncclComm_t) new LoopComm{g, rank};
-    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) {
-        avt_set_error("avt_shard_create_loopback: hipStreamCreate failed");
-        s->api->CommDestroy(s->comm);
-        delete s;
-        return 1;
-    }
-    s->backend = std::string("loop-back (threads of one process), group ") + group;
-    *out = s;
-    return 0;
+        s->backend = std::string("loop-back (threads of one process), group ") + group;
+        *out = s;
+        return 0;
+    });
 }
 
 extern "C" int avt_shard_create_shm(int device, int rank, int world, const char id[AVT_SHARD_ID_BYTES], avt_shard** out) {
-    if (!id || !out || world <= 0 || world > 64 || rank < 0 || rank >= world) { avt_set_error("avt_shard_create_shm: bad argument"); return 1; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { avt_set_error("avt_shard_create_shm: device index out of range"); return 2; }
-    HIP_OK(hipSetDevice(device));
-    unsigned long long h = 1469598103934665603ull;      // FNV-1a of the rendezvous bytes names the segment
-    for (int i = 0; i < AVT_SHARD_ID_BYTES; ++i) { h ^= (unsigned char)id[i]; h *= 1099511628211ull; }
-    char name[64];
-    snprintf(name, sizeof name, "/avt_shard_%016llx", h);
-    double timeout_s = 60.0;
-    if (const char* e = getenv("AVT_SHARD_LOOPBACK_TIMEOUT_S")) timeout_s = std::max(0.1, atof(e));
-    const size_t bytes = shm_bytes(world);
-    const auto t0 = std::chrono::steady_clock::now();
-    auto late = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > timeout_s; };
-    int fd = -1;
-    if (rank == 0) {
-        fd = shm_open(name, O_CREAT | O_EXCL | O_RDWR, 0600);
-        if (fd < 0 || ftruncate(fd, (off_t)bytes) != 0) {
-            avt_set_error(std::string("avt_shard_create_shm: cannot create the segment ") + name + ": " + strerror(errno));
-            if (fd >= 0) { close(fd); shm_unlink(name); }
-            return 1;
+    return avt_guard("avt_shard_create_shm", [&]() -> int {
+        if (!id || !out || world <= 0 || world > 64 || rank < 0 || rank >= world) { avt_set_error("avt_shard_create_shm: bad argument"); return 1; }
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { avt_set_error("avt_shard_create_shm: device index out of range"); return 2; }
+        AVT_HIP(hipSetDevice(device));
+        unsigned long long h = 1469598103934665603ull;      // FNV-1a of the rendezvous bytes names the segment
+        for (int i = 0; i < AVT_SHARD_ID_BYTES; ++i) { h ^= (unsigned char)id[i]; h *= 1099511628211ull; }
+        char name[64];
+        snprintf(name, sizeof name, "/avt_shard_%016llx", h);
+        double timeout_s = 60.0;
+        if (const char* e = getenv("AVT_SHARD_LOOPBACK_TIMEOUT_S")) timeout_s = std::max(0.1, atof(e));
+        const size_t bytes = shm_bytes(world);
+        const auto t0 = std::chrono::steady_clock::now();
+        auto late = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > timeout_s; };
+        int fd = -1;
+        if (rank == 0) {
+            fd = shm_open(name, O_CREAT | O_EXCL | O_RDWR, 0600);
+            if (fd < 0 || ftruncate(fd, (off_t)bytes) != 0) {
+                avt_set_error(std::string("avt_shard_create_shm: cannot create the segment ") + name + ": " + strerror(errno));
+                if (fd >= 0) { close(fd); shm_unlink(name); }
+                return 1;
+            }
+        } else {
+            struct stat sb;
+            while (true) {      // rank 0 creates and sizes it
+                fd = shm_open(name, O_RDWR, 0600);
+                if (fd >= 0 && fstat(fd, &sb) == 0 && (size_t)sb.st_size >= bytes) break;
+                if (fd >= 0) { close(fd); fd = -1; }
+                if (late()) { avt_set_error(std::string("avt_shard_create_shm: rank 0 never created the segment ") + name); return 1; }
+                std::this_thread::sleep_for(std::chrono::milliseconds(2));
+            }
         }
-    } else {
-        struct stat sb;
-        while (true) {      // rank 0 creates and sizes it
-            fd = shm_open(name, O_RDWR, 0600);
-            if (fd >= 0 && fstat(fd, &sb) == 0 && (size_t)sb.st_size >= bytes) break;
-            if (fd >= 0) { close(fd); fd = -1; }
-            if (late()) { avt_set_error(std::string("avt_shard_create_shm: rank 0 never created the segment ") + name); return 1; }
-            std::this_thread::sleep_for(std::chrono::milliseconds(2));
+        void* base = mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
+        close(fd);
+        if (base == MAP_FAILED) { avt_set_error(std::string("avt_shard_create_shm: mmap: ") + strerror(errno)); if (rank == 0) shm_unlink(name); return 1; }
+        ShmComm* sc = new ShmComm();
+        sc->base = base; sc->map_bytes = bytes; sc->rank = rank; sc->world = world; sc->timeout_s = timeout_s;
+        sc->sent.assign(world, 0); sc->taken.assign(world, 0);
+        ShmHeader* hd = sc->hdr();
+        if (rank == 0) {      // (a fresh segment is zero-filled: counters start at 0)
+            hd->world = world; hd->chunk = SHM_CHUNK;
+            hd->magic.store(SHM_MAGIC, std::memory_order_release);
+        } else {
+            while (hd->magic.load(std::memory_order_acquire) != SHM_MAGIC) {
+                if (late()) { avt_set_error("avt_shard_create_shm: the segment was never initialised"); shm_CommDestroy((ncclComm_t)sc); return 1; }
+                std::this_thread::sleep_for(std::chrono::milliseconds(1));
+            }
+            if (hd->world != world || hd->chunk != SHM_CHUNK) { avt_set_error("avt_shard_create_shm: the segment belongs to a group of another shape"); shm_CommDestroy((ncclComm_t)sc); return 1; }
         }
-    }
-    void* base = mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
-    close(fd);
-    if (base == MAP_FAILED) { avt_set_error(std::string("avt_shard_create_shm: mmap: ") + strerror(errno)); if (rank == 0) shm_unlink(name); return 1; }
-    ShmComm* sc = new ShmComm();
-    sc->base = base; sc->map_bytes = bytes; sc->rank = rank; sc->world = world; sc->timeout_s = timeout_s;
-    sc->sent.assign(world, 0); sc->taken.assign(world, 0);
-    ShmHeader* hd = sc->hdr();
-    if (rank == 0) {      // (a fresh segment is zero-filled: counters start at 0)
-        hd->world = world; hd->chunk = SHM_CHUNK;
-        hd->magic.store(SHM_MAGIC, std::memory_order_release);
-    } else {
-        while (hd->magic.load(std::memory_order_acquire) != SHM_MAGIC) {
-            if (late()) { avt_set_error("avt_shard_create_shm: the segment was never initialised"); shm_CommDestroy((ncclComm_t)sc); return 1; }
+        hd->attached.fetch_add(1, std::memory_order_acq_rel);
+        while (hd->attached.load(std::memory_order_acquire) < world) {      // creation is collective, like ncclCommInitRank
+            if (late()) {
+                avt_set_error("avt_shard_create_shm: not every rank attached in time");
+                if (rank == 0) shm_unlink(name);
+                shm_CommDestroy((ncclComm_t)sc);
+                return 1;
+            }
             std::this_thread::sleep_for(std::chrono::milliseconds(1));
         }
-        if (hd->world != world || hd->chunk != SHM_CHUNK) { avt_set_error("avt_shard_create_shm: the segment belongs to a group of another shape"); shm_CommDestroy((ncclComm_t)sc); return 1; }
-    }
-    hd->attached.fetch_add(1, std::memory_order_acq_rel);
-    while (hd->attached.load(std::memory_order_acquire) < world) {      // creation is collective, like ncclCommInitRank
-        if (late()) {
-            avt_set_error("avt_shard_create_shm: not every rank attached in time");
-            if (rank == 0) shm_unlink(name);
-            shm_CommDestroy((ncclComm_t)sc);
+        if (rank == 0) shm_unlink(name);      // everybody holds a mapping: the name can go, the memory lives until the last unmap
+        avt_shard* s = new avt_shard();
+        s->api = shm_api(); s->device = device; s->rank = rank; s->world = world;
+        s->comm = (ncclComm_t)sc;
+        if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) {
+            avt_set_error("avt_shard_create_shm: hipStreamCreate failed");
+            s->api->CommDestroy(s->comm);
+            delete s;
             return 1;
         }
-        std::this_thread::sleep_for(std::chrono::milliseconds(1));
-    }
-    if (rank == 0) shm_unlink(name);      // everybody holds a mapping: the name can go, the memory lives until the last unmap
-    avt_shard* s = new avt_shard();
-    s->api = shm_api(); s->device = device; s->rank = rank; s->world = world;
-    s->comm = (ncclComm_t)sc;
-    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) {
-        avt_set_error("avt_shard_create_shm: hipStreamCreate failed");
-        s->api->CommDestroy(s->comm);
-        delete s;
-        return 1;
-    }
-    s->backend = "shared memory (processes of one node, staged through the host)";
-    *out = s;
-    return 0;
+        s->backend = "shared memory (processes of one node, staged through the host)";
+        *out = s;
+        return 0;
+    });
 }
 
 extern "C" void avt_shard_destroy(avt_shard* s) {
@@ -759,8 +750,7 @@ extern "C" void avt_shard_destroy(avt_shard* s) {
     (void)hipSetDevice(s->device);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
     if (s->comm) s->api->CommDestroy(s->comm);
-    for (void* p : {(void*)s->d_send, (void*)s->d_recv, s->d_stage, s->d_stage2})
-        if (p) (void)hipFree(p);
+    // the blocks go with `delete`, after the stream: hipFree waits for the device, so nothing is queued on them either way
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
 }
@@ -769,219 +759,220 @@ extern "C" int avt_shard_rank(const avt_shard* s) { return s ? s->rank : -1; }
 extern "C" int avt_shard_world(const avt_shard* s) { return s ? s->world : 0; }
 extern "C" const char* avt_shard_backend(const avt_shard* s) { return s ? s->backend.c_str() : ""; }
 
-extern "C" int avt_shard_broadcast_model(avt_shard* s, int root, const avt_model_desc* desc, avt_model** out) try {
-    if (!s || !out || root < 0 || root >= s->world) { avt_set_error("avt_shard_broadcast_model: bad argument"); return 1; }
-    HIP_OK(hipSetDevice(s->device));
-    // 1. size of the packed block (8 bytes), 2. the block itself; both as device-buffer broadcasts
-    unsigned long long nbytes = 0;
-    std::vector<char> host;
-    if (s->rank == root) {
-        size_t n = 0;
-        if (avt_model_pack_size(desc, &n)) return 1;
-        host.resize(n);
-        if (avt_model_pack(desc, host.data(), n)) return 1;
-        nbytes = n;
-    }
-    if (grow(&s->d_stage2, &s->stage2_cap, 64)) return 1;
-    HIP_OK(hipMemcpyAsync(s->d_stage2, &nbytes, 8, hipMemcpyHostToDevice, s->stream));
-    NCCL_OK(s, s->api->Broadcast(s->d_stage2, s->d_stage2, 8, ncclChar, root, s->comm, s->stream));
-    HIP_OK(hipMemcpyAsync(&nbytes, s->d_stage2, 8, hipMemcpyDeviceToHost, s->stream));
-    HIP_OK(hipStreamSynchronize(s->stream));
-    if (nbytes < sizeof(PackHeader) || nbytes > (1ull << 32)) { avt_set_error("avt_shard_broadcast_model: implausible model size received"); return 1; }
-    if (grow(&s->d_stage, &s->stage_cap, nbytes)) return 1;
-    if (s->rank == root) HIP_OK(hipMemcpyAsync(s->d_stage, host.data(), nbytes, hipMemcpyHostToDevice, s->stream));
-    NCCL_OK(s, s->api->Broadcast(s->d_stage, s->d_stage, nbytes, ncclChar, root, s->comm, s->stream));
-    host.resize(nbytes);
-    HIP_OK(hipMemcpyAsync(host.data(), s->d_stage, nbytes, hipMemcpyDeviceToHost, s->stream));
-    HIP_OK(hipStreamSynchronize(s->stream));
-    return avt_model_unpack(host.data(), host.size(), out);
-} catch (const std::exception& e) { avt_set_error(std::string("avt_shard_broadcast_model: ") + e.what()); return 1; }
+extern "C" int avt_shard_broadcast_model(avt_shard* s, int root, const avt_model_desc* desc, avt_model** out) {
+    return avt_guard("avt_shard_broadcast_model", [&]() -> int {
+        if (!s || !out || root < 0 || root >= s->world) { avt_set_error("avt_shard_broadcast_model: bad argument"); return 1; }
+        AVT_HIP(hipSetDevice(s->device));
+        // 1. size of the packed block (8 bytes), 2. the block itself; both as device-buffer broadcasts
+        unsigned long long nbytes = 0;
+        std::vector<char> host;
+        if (s->rank == root) {
+            size_t n = 0;
+            if (avt_model_pack_size(desc, &n)) return 1;
+            host.resize(n);
+            if (avt_model_pack(desc, host.data(), n)) return 1;
+            nbytes = n;
+        }
+        if (grow(s->d_stage2, 64)) return 1;
+        AVT_HIP(hipMemcpyAsync(s->d_stage2, &nbytes, 8, hipMemcpyHostToDevice, s->stream));
+        NCCL_OK(s, s->api->Broadcast(s->d_stage2, s->d_stage2, 8, ncclChar, root, s->comm, s->stream));
+        AVT_HIP(hipMemcpyAsync(&nbytes, s->d_stage2, 8, hipMemcpyDeviceToHost, s->stream));
+        AVT_HIP(hipStreamSynchronize(s->stream));
+        if (nbytes < sizeof(PackHeader) || nbytes > (1ull << 32)) { avt_set_error("avt_shard_broadcast_model: implausible model size received"); return 1; }
+        if (grow(s->d_stage, nbytes)) return 1;
+        if (s->rank == root) AVT_HIP(hipMemcpyAsync(s->d_stage, host.data(), nbytes, hipMemcpyHostToDevice, s->stream));
+        NCCL_OK(s, s->api->Broadcast(s->d_stage, s->d_stage, nbytes, ncclChar, root, s->comm, s->stream));
+        host.resize(nbytes);
+        AVT_HIP(hipMemcpyAsync(host.data(), s->d_stage, nbytes, hipMemcpyDeviceToHost, s->stream));
+        AVT_HIP(hipStreamSynchronize(s->stream));
+        return avt_model_unpack(host.data(), host.size(), out);
+    });
+}
 
 extern "C" int avt_shard_scatter_frames(avt_shard* s, avt_ctx* c, int root, int B, const double* data, const int* labels,
-                                        const int* offs, const double* p, const double* q, const double* w) try {
-    if (!s || !c || root < 0 || root >= s->world || B <= 0) { avt_set_error("avt_shard_scatter_frames: bad argument"); return 1; }
-    const bool is_root = s->rank == root;
-    const AvtDims& d = c->dm.d;
-    const int W = s->world, xs = d.xsize, J = d.J, K = d.K;
-    const int nloc = avt_shard_local_count(B, s->rank, W);
-    HIP_OK(hipSetDevice(s->device));
-    hipStream_t st = c->stream;
-    // A rank that leaves before a collective its peers enter blocks them for ever.  Everything that can be wrong on ONE rank
-    // only - the root's arguments, a context too small for this rank's share - is therefore carried INTO the exchange and all
-    // ranks leave together: the root marks a bad batch in the table it broadcasts, and every rank contributes an ok / not-ok
-    // word to a one-double all-gather before any cloud moves.
-    std::string my_error;
-    // ---- 1. frame table and start states: one small broadcast.  block = [B point counts as doubles | B x xsize states]
-    const size_t tab_n = (size_t)B * (1 + xs);
-    std::vector<double> tab(tab_n, 0.0);
-    if (is_root) {
-        if (!data || !labels || !offs || !p || !q || !w) my_error = "avt_shard_scatter_frames: root needs all host arrays";
-        for (int f = 0; f < B && my_error.empty(); ++f) {
-            const int n = offs[f + 1] - offs[f];
-            if (n < 0) { my_error = "avt_shard_scatter_frames: frame_offsets not monotone"; break; }
-            tab[f] = (double)n;
-            double* x = &tab[(size_t)B + (size_t)f * xs];
-            std::copy(p + 3 * (size_t)f, p + 3 * (size_t)f + 3, x);
-            std::copy(q + (size_t)4 * J * f, q + (size_t)4 * J * (f + 1), x + 3);
-            std::copy(w + (size_t)K * f, w + (size_t)K * (f + 1), x + 3 + 4 * J);
+                                        const int* offs, const double* p, const double* q, const double* w) {
+    return avt_guard("avt_shard_scatter_frames", [&]() -> int {
+        if (!s || !c || root < 0 || root >= s->world || B <= 0) { avt_set_error("avt_shard_scatter_frames: bad argument"); return 1; }
+        const bool is_root = s->rank == root;
+        const AvtDims& d = c->dm.d;
+        const int W = s->world, xs = d.xsize, J = d.J, K = d.K;
+        const int nloc = avt_shard_local_count(B, s->rank, W);
+        AVT_HIP(hipSetDevice(s->device));
+        hipStream_t st = c->stream;
+        // A rank that leaves before a collective its peers enter blocks them for ever.  Everything that can be wrong on ONE rank
+        // only - the root's arguments, a context too small for this rank's share - is therefore carried INTO the exchange and all
+        // ranks leave together: the root marks a bad batch in the table it broadcasts, and every rank contributes an ok / not-ok
+        // word to a one-double all-gather before any cloud moves.
+        std::string my_error;
+        // ---- 1. frame table and start states: one small broadcast.  block = [B point counts as doubles | B x xsize states]
+        const size_t tab_n = (size_t)B * (1 + xs);
+        std::vector<double> tab(tab_n, 0.0);
+        if (is_root) {
+            if (!data || !labels || !offs || !p || !q || !w) my_error = "avt_shard_scatter_frames: root needs all host arrays";
+            for (int f = 0; f < B && my_error.empty(); ++f) {
+                const int n = offs[f + 1] - offs[f];
+                if (n < 0) { my_error = "avt_shard_scatter_frames: frame_offsets not monotone"; break; }
+                tab[f] = (double)n;
+                double* x = &tab[(size_t)B + (size_t)f * xs];
+                std::copy(p + 3 * (size_t)f, p + 3 * (size_t)f + 3, x);
+                std::copy(q + (size_t)4 * J * f, q + (size_t)4 * J * (f + 1), x + 3);
+                std::copy(w + (size_t)K * f, w + (size_t)K * (f + 1), x + 3 + 4 * J);
+            }
+            if (!my_error.empty()) tab[0] = -1.0;          // a point count cannot be negative: "the root's batch is unusable"
         }
-        if (!my_error.empty()) tab[0] = -1.0;          // a point count cannot be negative: "the root's batch is unusable"
-    }
-    if (grow(&s->d_stage2, &s->stage2_cap, std::max<size_t>(tab_n, (size_t)W + 1) * 8)) return 1;   // (allocation failure: nothing a peer could wait for has begun)
-    if (is_root) HIP_OK(hipMemcpyAsync(s->d_stage2, tab.data(), tab_n * 8, hipMemcpyHostToDevice, st));
-    NCCL_OK(s, s->api->Broadcast(s->d_stage2, s->d_stage2, tab_n, ncclDouble, root, s->comm, st));
-    HIP_OK(hipMemcpyAsync(tab.data(), s->d_stage2, tab_n * 8, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    std::vector<int> cnt(B, 0);
-    std::vector<long long> rank_pts(W, 0);
-    const bool root_bad = tab[0] < 0.0;
-    if (root_bad && my_error.empty()) my_error = "avt_shard_scatter_frames: the root rank rejected the batch";
-    if (my_error.empty() && nloc > c->fb.max_frames) my_error = "avt_shard_scatter_frames: this rank's share exceeds the context's max_frames";
-    for (int f = 0; f < B && !root_bad; ++f) {
-        cnt[f] = (int)tab[f];
-        // every rank checks ITS frames against ITS context (contexts may differ in size)
-        if (f % W == s->rank && my_error.empty() && (cnt[f] < 0 || cnt[f] > c->fb.max_points))
-            my_error = "avt_shard_scatter_frames: a frame has more points than max_points_per_frame";
-        rank_pts[f % W] += std::max(cnt[f], 0);
-    }
-    {   // agreement: one double per rank (0 = fine), everybody sees everybody's
-        std::vector<double> flags((size_t)W + 1, 0.0);
-        flags[W] = my_error.empty() ? 0.0 : 1.0;
-        double* dflag = (double*)s->d_stage2;
-        HIP_OK(hipMemcpyAsync(dflag + W, &flags[W], 8, hipMemcpyHostToDevice, st));
-        NCCL_OK(s, s->api->AllGather(dflag + W, dflag, 1, ncclDouble, s->comm, st));
-        HIP_OK(hipMemcpyAsync(flags.data(), dflag, (size_t)W * 8, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        int bad_rank = -1;
-        for (int r = 0; r < W; ++r) if (flags[r] != 0.0 && bad_rank < 0) bad_rank = r;
-        if (bad_rank >= 0) {
+        if (grow(s->d_stage2, std::max<size_t>(tab_n, (size_t)W + 1) * 8)) return 1;   // (allocation failure: nothing a peer could wait for has begun)
+        if (is_root) AVT_HIP(hipMemcpyAsync(s->d_stage2, tab.data(), tab_n * 8, hipMemcpyHostToDevice, st));
+        NCCL_OK(s, s->api->Broadcast(s->d_stage2, s->d_stage2, tab_n, ncclDouble, root, s->comm, st));
+        AVT_HIP(hipMemcpyAsync(tab.data(), s->d_stage2, tab_n * 8, hipMemcpyDeviceToHost, st));
+        AVT_HIP(hipStreamSynchronize(st));
+        std::vector<int> cnt(B, 0);
+        std::vector<long long> rank_pts(W, 0);
+        const bool root_bad = tab[0] < 0.0;
+        if (root_bad && my_error.empty()) my_error = "avt_shard_scatter_frames: the root rank rejected the batch";
+        if (my_error.empty() && nloc > c->fb.max_frames) my_error = "avt_shard_scatter_frames: this rank's share exceeds the context's max_frames";
+        for (int f = 0; f < B && !root_bad; ++f) {
+            cnt[f] = (int)tab[f];
+            // every rank checks ITS frames against ITS context (contexts may differ in size)
+            if (f % W == s->rank && my_error.empty() && (cnt[f] < 0 || cnt[f] > c->fb.max_points))
+                my_error = "avt_shard_scatter_frames: a frame has more points than max_points_per_frame";
+            rank_pts[f % W] += std::max(cnt[f], 0);
+        }
+        {   // agreement: one double per rank (0 = fine), everybody sees everybody's
+            std::vector<double> flags((size_t)W + 1, 0.0);
+            flags[W] = my_error.empty() ? 0.0 : 1.0;
+            double* dflag = (double*)s->d_stage2.p;
+            AVT_HIP(hipMemcpyAsync(dflag + W, &flags[W], 8, hipMemcpyHostToDevice, st));
+            NCCL_OK(s, s->api->AllGather(dflag + W, dflag, 1, ncclDouble, s->comm, st));
+            AVT_HIP(hipMemcpyAsync(flags.data(), dflag, (size_t)W * 8, hipMemcpyDeviceToHost, st));
+            AVT_HIP(hipStreamSynchronize(st));
+            int bad_rank = -1;
+            for (int r = 0; r < W; ++r) if (flags[r] != 0.0 && bad_rank < 0) bad_rank = r;
+            if (bad_rank >= 0) {
+                c->nframes = 0; c->frames_valid = c->state_valid = false;
+                avt_set_error(!my_error.empty() ? my_error : "avt_shard_scatter_frames: rank " + std::to_string(bad_rank) + " rejected the batch; nothing was exchanged");
+                return 1;
+            }
+        }
+        // ---- 2. clouds: the root permutes the batch so that every rank's frames are contiguous (rank-major, then local
+        // order), uploads it once and sends each rank its block: [3 n doubles | n ints] -> two sends per peer, one group
+        std::vector<long long> rank_off(W + 1, 0);
+        for (int r = 0; r < W; ++r) rank_off[r + 1] = rank_off[r] + rank_pts[r];
+        const long long total = rank_off[W], mine = rank_pts[s->rank];
+        double* d_data = nullptr; int* d_lab = nullptr;
+        if (is_root) {
+            std::vector<double> hd((size_t)total * 3);
+            std::vector<int> hl((size_t)total);
+            std::vector<long long> cur(rank_off.begin(), rank_off.end() - 1);
+            for (int f = 0; f < B; ++f) {
+                const int r = f % W, n = cnt[f];
+                std::memcpy(&hd[(size_t)cur[r] * 3], data + (size_t)offs[f] * 3, (size_t)n * 24);
+                std::memcpy(&hl[(size_t)cur[r]], labels + offs[f], (size_t)n * 4);
+                cur[r] += n;
+            }
+            if (grow(s->d_stage, (size_t)total * 28 + 64)) return 1;
+            d_data = (double*)s->d_stage.p; d_lab = (int*)((char*)s->d_stage + (size_t)total * 24);
+            if (total) {
+                AVT_HIP(hipMemcpyAsync(d_data, hd.data(), (size_t)total * 24, hipMemcpyHostToDevice, st));
+                AVT_HIP(hipMemcpyAsync(d_lab, hl.data(), (size_t)total * 4, hipMemcpyHostToDevice, st));
+            }
+            AVT_HIP(hipStreamSynchronize(st));   // the host vectors go out of scope below
+        } else {
+            if (grow(s->d_stage, (size_t)mine * 28 + 64)) return 1;
+            d_data = (double*)s->d_stage.p; d_lab = (int*)((char*)s->d_stage + (size_t)mine * 24);
+        }
+        const bool self_loop = s->self_exchange;   // dry runs (avt_shard_set_self_exchange): push the root's own block through RCCL too
+        double* my_data = d_data; int* my_lab = d_lab;
+        if (is_root) { my_data = d_data + rank_off[s->rank] * 3; my_lab = d_lab + rank_off[s->rank]; }
+        double* loop_data = nullptr; int* loop_lab = nullptr;
+        if (is_root && self_loop && mine) {
+            if (grow(s->d_stage2, std::max<size_t>((size_t)mine * 28 + 64, tab_n * 8))) return 1;
+            loop_data = (double*)s->d_stage2.p; loop_lab = (int*)((char*)s->d_stage2 + (size_t)mine * 24);
+        }
+        NCCL_OK(s, s->api->GroupStart());
+        if (is_root) {
+            for (int r = 0; r < W; ++r) {
+                if (rank_pts[r] == 0 || (r == s->rank && !self_loop)) continue;
+                NCCL_OK(s, s->api->Send(d_data + rank_off[r] * 3, (size_t)rank_pts[r] * 3, ncclDouble, r, s->comm, st));
+                NCCL_OK(s, s->api->Send(d_lab + rank_off[r], (size_t)rank_pts[r], ncclInt32, r, s->comm, st));
+            }
+            if (self_loop && mine) {
+                NCCL_OK(s, s->api->Recv(loop_data, (size_t)mine * 3, ncclDouble, root, s->comm, st));
+                NCCL_OK(s, s->api->Recv(loop_lab, (size_t)mine, ncclInt32, root, s->comm, st));
+                my_data = loop_data; my_lab = loop_lab;
+            }
+        } else if (mine) {
+            NCCL_OK(s, s->api->Recv(d_data, (size_t)mine * 3, ncclDouble, root, s->comm, st));
+            NCCL_OK(s, s->api->Recv(d_lab, (size_t)mine, ncclInt32, root, s->comm, st));
+        }
+        NCCL_OK(s, s->api->GroupEnd());
+        // ---- 3. install this rank's frames in the context's resident buffers (device-to-device) and its start states
+        std::vector<int> lcnt(nloc);
+        std::vector<double> lp((size_t)nloc * 3), lq((size_t)nloc * 4 * J), lw((size_t)nloc * K);
+        for (int i = 0; i < nloc; ++i) {
+            const int f = avt_shard_global_frame(i, s->rank, W);
+            lcnt[i] = cnt[f];
+            const double* x = &tab[(size_t)B + (size_t)f * xs];
+            std::copy(x, x + 3, &lp[(size_t)i * 3]);
+            std::copy(x + 3, x + 3 + 4 * J, &lq[(size_t)i * 4 * J]);
+            std::copy(x + 3 + 4 * J, x + xs, &lw[(size_t)i * K]);
+        }
+        if (nloc == 0) {       // a rank without frames (B < W): nothing resident, and a later gather must see exactly that
             c->nframes = 0; c->frames_valid = c->state_valid = false;
-            avt_set_error(!my_error.empty() ? my_error : "avt_shard_scatter_frames: rank " + std::to_string(bad_rank) + " rejected the batch; nothing was exchanged");
-            return 1;
+            AVT_HIP(hipStreamSynchronize(st));
+            return 0;
         }
-    }
-    // ---- 2. clouds: the root permutes the batch so that every rank's frames are contiguous (rank-major, then local
-    // order), uploads it once and sends each rank its block: [3 n doubles | n ints] -> two sends per peer, one group
-    std::vector<long long> rank_off(W + 1, 0);
-    for (int r = 0; r < W; ++r) rank_off[r + 1] = rank_off[r] + rank_pts[r];
-    const long long total = rank_off[W], mine = rank_pts[s->rank];
-    double* d_data = nullptr; int* d_lab = nullptr;
-    if (is_root) {
-        std::vector<double> hd((size_t)total * 3);
-        std::vector<int> hl((size_t)total);
-        std::vector<long long> cur(rank_off.begin(), rank_off.end() - 1);
-        for (int f = 0; f < B; ++f) {
-            const int r = f % W, n = cnt[f];
-            std::memcpy(&hd[(size_t)cur[r] * 3], data + (size_t)offs[f] * 3, (size_t)n * 24);
-            std::memcpy(&hl[(size_t)cur[r]], labels + offs[f], (size_t)n * 4);
-            cur[r] += n;
-        }
-        if (grow(&s->d_stage, &s->stage_cap, (size_t)total * 28 + 64)) return 1;
-        d_data = (double*)s->d_stage; d_lab = (int*)((char*)s->d_stage + (size_t)total * 24);
-        if (total) {
-            HIP_OK(hipMemcpyAsync(d_data, hd.data(), (size_t)total * 24, hipMemcpyHostToDevice, st));
-            HIP_OK(hipMemcpyAsync(d_lab, hl.data(), (size_t)total * 4, hipMemcpyHostToDevice, st));
-        }
-        HIP_OK(hipStreamSynchronize(st));   // the host vectors go out of scope below
-    } else {
-        if (grow(&s->d_stage, &s->stage_cap, (size_t)mine * 28 + 64)) return 1;
-        d_data = (double*)s->d_stage; d_lab = (int*)((char*)s->d_stage + (size_t)mine * 24);
-    }
-    const bool self_loop = s->self_exchange;   // dry runs (avt_shard_set_self_exchange): push the root's own block through RCCL too
-    double* my_data = d_data; int* my_lab = d_lab;
-    if (is_root) { my_data = d_data + rank_off[s->rank] * 3; my_lab = d_lab + rank_off[s->rank]; }
-    double* loop_data = nullptr; int* loop_lab = nullptr;
-    if (is_root && self_loop && mine) {
-        if (grow(&s->d_stage2, &s->stage2_cap, std::max<size_t>((size_t)mine * 28 + 64, tab_n * 8))) return 1;
-        loop_data = (double*)s->d_stage2; loop_lab = (int*)((char*)s->d_stage2 + (size_t)mine * 24);
-    }
-    NCCL_OK(s, s->api->GroupStart());
-    if (is_root) {
-        for (int r = 0; r < W; ++r) {
-            if (rank_pts[r] == 0 || (r == s->rank && !self_loop)) continue;
-            NCCL_OK(s, s->api->Send(d_data + rank_off[r] * 3, (size_t)rank_pts[r] * 3, ncclDouble, r, s->comm, st));
-            NCCL_OK(s, s->api->Send(d_lab + rank_off[r], (size_t)rank_pts[r], ncclInt32, r, s->comm, st));
-        }
-        if (self_loop && mine) {
-            NCCL_OK(s, s->api->Recv(loop_data, (size_t)mine * 3, ncclDouble, root, s->comm, st));
-            NCCL_OK(s, s->api->Recv(loop_lab, (size_t)mine, ncclInt32, root, s->comm, st));
-            my_data = loop_data; my_lab = loop_lab;
-        }
-    } else if (mine) {
-        NCCL_OK(s, s->api->Recv(d_data, (size_t)mine * 3, ncclDouble, root, s->comm, st));
-        NCCL_OK(s, s->api->Recv(d_lab, (size_t)mine, ncclInt32, root, s->comm, st));
-    }
-    NCCL_OK(s, s->api->GroupEnd());
-    // ---- 3. install this rank's frames in the context's resident buffers (device-to-device) and its start states
-    std::vector<int> lcnt(nloc);
-    std::vector<double> lp((size_t)nloc * 3), lq((size_t)nloc * 4 * J), lw((size_t)nloc * K);
-    for (int i = 0; i < nloc; ++i) {
-        const int f = avt_shard_global_frame(i, s->rank, W);
-        lcnt[i] = cnt[f];
-        const double* x = &tab[(size_t)B + (size_t)f * xs];
-        std::copy(x, x + 3, &lp[(size_t)i * 3]);
-        std::copy(x + 3, x + 3 + 4 * J, &lq[(size_t)i * 4 * J]);
-        std::copy(x + 3 + 4 * J, x + xs, &lw[(size_t)i * K]);
-    }
-    if (nloc == 0) {       // a rank without frames (B < W): nothing resident, and a later gather must see exactly that
-        c->nframes = 0; c->frames_valid = c->state_valid = false;
-        HIP_OK(hipStreamSynchronize(st));
+        if (avt_internal_install_frames(c, nloc, lcnt.data(), my_data, my_lab, 1)) return 1;
+        if (avt_state_upload(c, nloc, lp.data(), lq.data(), lw.data())) return 1;
+        AVT_HIP(hipStreamSynchronize(st));
         return 0;
-    }
-    if (avt_internal_install_frames(c, nloc, lcnt.data(), my_data, my_lab, 1)) return 1;
-    if (avt_state_upload(c, nloc, lp.data(), lq.data(), lw.data())) return 1;
-    HIP_OK(hipStreamSynchronize(st));
-    return 0;
-} catch (const std::exception& e) { avt_set_error(std::string("avt_shard_scatter_frames: ") + e.what()); return 1; }
+    });
+}
 
 extern "C" int avt_shard_gather_enqueue(avt_shard* s, avt_ctx* c, int B) {
-    if (!s || !c || B <= 0) { avt_set_error("avt_shard_gather_enqueue: bad argument"); return 1; }
-    const int W = s->world, per = (B + W - 1) / W, stride = gather_stride(c);
-    const int nloc = avt_shard_local_count(B, s->rank, W);
-    // (a rank whose context does not hold its share still takes part in the all-gather - its peers are on their way into it - with
-    // its rows marked faulty, and reports the error afterwards; every rank's download then fails on those rows)
-    const bool mismatch = nloc != (c->frames_valid ? c->nframes : 0);
-    HIP_OK(hipSetDevice(s->device));
-    const size_t blk = (size_t)per * stride;
-    if (s->gather_cap < blk) {
-        HIP_OK(hipStreamSynchronize(c->stream));
-        HIP_OK(hipStreamSynchronize(s->stream));
-        if (s->d_send) HIP_OK(hipFree(s->d_send));
-        if (s->d_recv) HIP_OK(hipFree(s->d_recv));
-        s->d_send = s->d_recv = nullptr; s->gather_cap = 0;
-        HIP_OK(hipMalloc((void**)&s->d_send, blk * 8));
-        HIP_OK(hipMalloc((void**)&s->d_recv, blk * 8 * W));
-        HIP_OK(hipMemsetAsync(s->d_send, 0, blk * 8, c->stream));
-        s->gather_cap = blk;
-    }
-    // Packing kernel and all-gather go behind optimize() on the context's stream.  Measured on one MI355X (bench.py, one frame
-    // per step, 0.62 ms): this costs 6 us per step; putting the all-gather on the shard's own stream instead - so that the
-    // exchange of step k overlaps step k+1 - costs 25 us, because the event record / cross-stream wait the hand-over needs
-    // sit in the context stream's critical path (double-buffering the send block and waiting on the host: 24 us).
-    // (avt_shard_set_self_exchange - the dry-run switch that pushes a lone rank's own blocks through the transport - keeps the one-rank all-gather too)
-    const bool direct = W == 1 && !mismatch && !s->self_exchange;
-    if (mismatch) {
-        std::vector<double> rows(blk, 0.0);
-        for (int i = 0; i < per; ++i) rows[(size_t)i * stride + c->dm.d.xsize + 7] = (double)AVT_FAULT_NOT_RESIDENT;
-        HIP_OK(hipMemcpyAsync(s->d_send, rows.data(), blk * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
-    } else if (nloc && !c->results_fresh) {      // (no optimize() in front: the records are made now)
-        launch_pack_results(c, nloc, c->fb.results, stride);
-        c->results_fresh = true;
-    }
-    // The result records (p, q, w, statistics, fault word per resident frame) are written by the k_lbs launch that closes optimize()
-    // (FrameBuffers::results): they ARE the send block.  One rank: they are the gathered block as well - an all-gather over one rank is a
-    // device-to-device copy kernel on the stream, 4.3 us per step for the identity.
-    const double* send = (mismatch || (size_t)per > (size_t)c->fb.max_frames) ? s->d_send : c->fb.results;
-    if (!mismatch && send == s->d_send && nloc) HIP_OK(hipMemcpyAsync(s->d_send, c->fb.results, (size_t)nloc * stride * 8, hipMemcpyDeviceToDevice, c->stream));
-    //  ... as a SNAPSHOT, like every other world size: enqueue -> optimize -> download returns the rows of the call the gather was enqueued
-    // behind, not the later call's (include/avt_shard.h: "into a device buffer owned by the shard"); one rank: a plain device-to-device copy
-    if (!direct) NCCL_OK(s, s->api->AllGather(send, s->d_recv, blk, ncclDouble, s->comm, c->stream));
-    else if (nloc) HIP_OK(hipMemcpyAsync(s->d_recv, send, (size_t)nloc * stride * 8, hipMemcpyDeviceToDevice, c->stream));
-    s->gathered = s->d_recv;
-    s->gather_stream = c->stream;
-    if (mismatch) { avt_set_error("avt_shard_gather_enqueue: resident frames differ from this rank's share of the batch (its rows were gathered as faulty)"); return 1; }
-    return 0;
+    return avt_guard("avt_shard_gather_enqueue", [&]() -> int {
+        if (!s || !c || B <= 0) { avt_set_error("avt_shard_gather_enqueue: bad argument"); return 1; }
+        const int W = s->world, per = (B + W - 1) / W, stride = gather_stride(c);
+        const int nloc = avt_shard_local_count(B, s->rank, W);
+        // (a rank whose context does not hold its share still takes part in the all-gather - its peers are on their way into it - with
+        // its rows marked faulty, and reports the error afterwards; every rank's download then fails on those rows)
+        const bool mismatch = nloc != (c->frames_valid ? c->nframes : 0);
+        AVT_HIP(hipSetDevice(s->device));
+        const size_t blk = (size_t)per * stride;
+        if (s->d_send.cap < blk || s->d_recv.cap < blk * W) {   // each on its own: a failed allocation leaves that block empty
+            AVT_HIP(hipStreamSynchronize(c->stream));
+            AVT_HIP(hipStreamSynchronize(s->stream));
+            if (s->d_send.reserve(blk) || s->d_recv.reserve(blk * W)) return 1;
+            AVT_HIP(hipMemsetAsync(s->d_send, 0, blk * 8, c->stream));
+        }
+        // Packing kernel and all-gather go behind optimize() on the context's stream.  Measured on one MI355X (bench.py, one frame
+        // per step, 0.62 ms): this costs 6 us per step; putting the all-gather on the shard's own stream instead - so that the
+        // exchange of step k overlaps step k+1 - costs 25 us, because the event record / cross-stream wait the hand-over needs
+        // sit in the context stream's critical path (double-buffering the send block and waiting on the host: 24 us).
+        // (avt_shard_set_self_exchange - the dry-run switch that pushes a lone rank's own blocks through the transport - keeps the one-rank all-gather too)
+        const bool direct = W == 1 && !mismatch && !s->self_exchange;
+        if (mismatch) {
+            std::vector<double> rows(blk, 0.0);
+            for (int i = 0; i < per; ++i) rows[(size_t)i * stride + c->dm.d.xsize + 7] = (double)AVT_FAULT_NOT_RESIDENT;
+            AVT_HIP(hipMemcpyAsync(s->d_send, rows.data(), blk * 8, hipMemcpyHostToDevice, c->stream));
+            AVT_HIP(hipStreamSynchronize(c->stream));
+        } else if (nloc && !c->results_fresh) {      // (no optimize() in front: the records are made now)
+            launch_pack_results(c, nloc, c->fb.results, stride);
+            c->results_fresh = true;
+        }
+        // The result records (p, q, w, statistics, fault word per resident frame) are written by the k_lbs launch that closes optimize()
+        // (FrameBuffers::results): they ARE the send block.  One rank: they are the gathered block as well - an all-gather over one rank is a
+        // device-to-device copy kernel on the stream, 4.3 us per step for the identity.
+        const double* send = (mismatch || (size_t)per > (size_t)c->fb.max_frames) ? s->d_send.p : c->fb.results;
+        if (!mismatch && send == s->d_send && nloc) AVT_HIP(hipMemcpyAsync(s->d_send, c->fb.results, (size_t)nloc * stride * 8, hipMemcpyDeviceToDevice, c->stream));
+        //  ... as a SNAPSHOT, like every other world size: enqueue -> optimize -> download returns the rows of the call the gather was enqueued
+        // behind, not the later call's (include/avt_shard.h: "into a device buffer owned by the shard"); one rank: a plain device-to-device copy
+        if (!direct) NCCL_OK(s, s->api->AllGather(send, s->d_recv, blk, ncclDouble, s->comm, c->stream));
+        else if (nloc) AVT_HIP(hipMemcpyAsync(s->d_recv, send, (size_t)nloc * stride * 8, hipMemcpyDeviceToDevice, c->stream));
+        s->gathered = s->d_recv;
+        s->gather_stream = c->stream;
+        if (mismatch) { avt_set_error("avt_shard_gather_enqueue: resident frames differ from this rank's share of the batch (its rows were gathered as faulty)"); return 1; }
+        return 0;
+    });
 }
 
 extern "C" int avt_shard_set_self_exchange(avt_shard* s, int on) {
@@ -992,43 +983,45 @@ extern "C" int avt_shard_set_self_exchange(avt_shard* s, int on) {
 
 extern "C" int avt_shard_gather_wait(avt_shard* s) {
     if (!s) { avt_set_error("avt_shard_gather_wait: null argument"); return 1; }
-    HIP_OK(hipSetDevice(s->device));
-    if (s->gather_stream) HIP_OK(hipStreamSynchronize(s->gather_stream));
+    AVT_HIP(hipSetDevice(s->device));
+    if (s->gather_stream) AVT_HIP(hipStreamSynchronize(s->gather_stream));
     return 0;
 }
 
-extern "C" int avt_shard_gather_download(avt_shard* s, avt_ctx* c, int B, double* p, double* q, double* w, avt_stats* stats) try {
-    if (!s || !c || B <= 0) { avt_set_error("avt_shard_gather_download: bad argument"); return 1; }
-    const AvtDims& d = c->dm.d;
-    const int W = s->world, per = (B + W - 1) / W, stride = gather_stride(c), xs = d.xsize, J = d.J, K = d.K;
-    const size_t blk = (size_t)per * stride;
-    if (s->gather_cap < blk || !s->d_recv || !s->gathered) { avt_set_error("avt_shard_gather_download: nothing was gathered"); return 1; }
-    HIP_OK(hipSetDevice(s->device));
-    std::vector<double> host(blk * W);
-    HIP_OK(hipMemcpyAsync(host.data(), s->gathered, host.size() * 8, hipMemcpyDeviceToHost, c->stream));   // behind the all-gather
-    HIP_OK(hipStreamSynchronize(c->stream));
-    int bad = -1;
-    for (int f = 0; f < B; ++f) {
-        const double* x = &host[(size_t)(f % W) * blk + (size_t)(f / W) * stride];
-        if (x[xs + 7] != 0.0 && bad < 0) bad = f;       // the owning rank's device fault bits travelled with the result (k_pack_results)
-        if (p) std::copy(x, x + 3, p + 3 * (size_t)f);
-        if (q) std::copy(x + 3, x + 3 + 4 * J, q + (size_t)4 * J * f);
-        if (w) std::copy(x + 3 + 4 * J, x + xs, w + (size_t)K * f);
-        if (stats) {
-            const double* t = x + xs;
-            stats[f].initial_cost = t[0]; stats[f].final_cost = t[1]; stats[f].lambda = t[2];
-            stats[f].num_correspondences = (int)t[3]; stats[f].matched_model_points = (int)t[4];
-            stats[f].gn_iterations = (int)t[5]; stats[f].accepted_steps = (int)t[6];
+extern "C" int avt_shard_gather_download(avt_shard* s, avt_ctx* c, int B, double* p, double* q, double* w, avt_stats* stats) {
+    return avt_guard("avt_shard_gather_download", [&]() -> int {
+        if (!s || !c || B <= 0) { avt_set_error("avt_shard_gather_download: bad argument"); return 1; }
+        const AvtDims& d = c->dm.d;
+        const int W = s->world, per = (B + W - 1) / W, stride = gather_stride(c), xs = d.xsize, J = d.J, K = d.K;
+        const size_t blk = (size_t)per * stride;
+        if (s->d_recv.cap < blk * W || !s->gathered) { avt_set_error("avt_shard_gather_download: nothing was gathered"); return 1; }
+        AVT_HIP(hipSetDevice(s->device));
+        std::vector<double> host(blk * W);
+        AVT_HIP(hipMemcpyAsync(host.data(), s->gathered, host.size() * 8, hipMemcpyDeviceToHost, c->stream));   // behind the all-gather
+        AVT_HIP(hipStreamSynchronize(c->stream));
+        int bad = -1;
+        for (int f = 0; f < B; ++f) {
+            const double* x = &host[(size_t)(f % W) * blk + (size_t)(f / W) * stride];
+            if (x[xs + 7] != 0.0 && bad < 0) bad = f;       // the owning rank's device fault bits travelled with the result (k_pack_results)
+            if (p) std::copy(x, x + 3, p + 3 * (size_t)f);
+            if (q) std::copy(x + 3, x + 3 + 4 * J, q + (size_t)4 * J * f);
+            if (w) std::copy(x + 3 + 4 * J, x + xs, w + (size_t)K * f);
+            if (stats) {
+                const double* t = x + xs;
+                stats[f].initial_cost = t[0]; stats[f].final_cost = t[1]; stats[f].lambda = t[2];
+                stats[f].num_correspondences = (int)t[3]; stats[f].matched_model_points = (int)t[4];
+                stats[f].gn_iterations = (int)t[5]; stats[f].accepted_steps = (int)t[6];
+            }
         }
-    }
-    if (bad >= 0) {
-        (void)hipMemsetAsync(c->fb.fault, 0, (size_t)c->fb.max_frames * sizeof(unsigned), c->stream);   // reported once
-        c->results_fresh = false;      //  the result records still carry the word that was just cleared: the next gather packs them again
-        avt_set_error("avt_shard_gather_download: frame " + std::to_string(bad) + " carries a device fault (rank " + std::to_string(bad % W) + "); its result is not valid");
-        return AVT_STATUS_DEVICE_FAULT;
-    }
-    return 0;
-} catch (const std::exception& e) { avt_set_error(std::string("avt_shard_gather_download: ") + e.what()); return 1; }
+        if (bad >= 0) {
+            (void)hipMemsetAsync(c->fb.fault, 0, (size_t)c->fb.max_frames * sizeof(unsigned), c->stream);   // reported once
+            c->results_fresh = false;      //  the result records still carry the word that was just cleared: the next gather packs them again
+            avt_set_error("avt_shard_gather_download: frame " + std::to_string(bad) + " carries a device fault (rank " + std::to_string(bad % W) + "); its result is not valid");
+            return AVT_STATUS_DEVICE_FAULT;
+        }
+        return 0;
+    });
+}
 
 extern "C" int avt_shard_gather_results(avt_shard* s, avt_ctx* c, int B, double* p, double* q, double* w, avt_stats* stats) {
     if (avt_shard_gather_enqueue(s, c, B)) return 1;
@@ -1037,11 +1030,11 @@ extern "C" int avt_shard_gather_results(avt_shard* s, avt_ctx* c, int B, double*
 
 extern "C" int avt_shard_barrier(avt_shard* s, avt_ctx* c) {
     if (!s) { avt_set_error("avt_shard_barrier: null argument"); return 1; }
-    HIP_OK(hipSetDevice(s->device));
+    AVT_HIP(hipSetDevice(s->device));
     hipStream_t st = c ? c->stream : s->stream;
-    if (grow(&s->d_stage2, &s->stage2_cap, (size_t)(s->world + 1) * 8)) return 1;
-    double* b = (double*)s->d_stage2;
+    if (grow(s->d_stage2, (size_t)(s->world + 1) * 8)) return 1;
+    double* b = (double*)s->d_stage2.p;
     NCCL_OK(s, s->api->AllGather(b + s->world, b, 1, ncclDouble, s->comm, st));
-    HIP_OK(hipStreamSynchronize(st));
+    AVT_HIP(hipStreamSynchronize(st));
     return 0;
 }

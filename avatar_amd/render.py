@@ -11,7 +11,7 @@ import sys
 
 import numpy as np
 
-from . import api, capi
+from . import capi
 
 RENDER_SYMBOLS = [
     "avt_renderer_create", "avt_renderer_destroy", "avt_renderer_set_part_map", "avt_renderer_upload", "avt_renderer_from_ctx",
@@ -21,10 +21,6 @@ RENDER_SYMBOLS = [
 DEPTH, PART_MASK, LAMBERT, FACES = 1, 2, 4, 8          # AVT_RENDER_* (include/avt_render.h)
 ALL = DEPTH | PART_MASK | LAMBERT | FACES
 ORDER_SORT, ORDER_RANK = 0, 1
-
-
-def _p(a, t):
-    return None if a is None else a.ctypes.data_as(C.POINTER(t))
 
 
 def _intrin(intrin):
@@ -42,7 +38,7 @@ class Renderer:
         self.V, self.J, self.F = model.numPoints(), model.numJoints(), model.numFaces()
         self.h = C.c_void_p()
         fx, fy, cx, cy = _intrin(intrin)
-        api._check(self._lib.avt_renderer_create(C.c_int(device), model.h, C.c_int(self.width), C.c_int(self.height), C.c_float(fx), C.c_float(fy),
+        capi.check(self._lib.avt_renderer_create(C.c_int(device), model.h, C.c_int(self.width), C.c_int(self.height), C.c_float(fx), C.c_float(fy),
                                                  C.c_float(cx), C.c_float(cy), C.c_int(self.max_images), C.byref(self.h)))
         self.n = 0
 
@@ -54,30 +50,30 @@ class Renderer:
     def set_part_map(self, part_map=None):
         """renderPartMask's part_map (joint -> part); None: the joint id"""
         pm = None if part_map is None or len(part_map) == 0 else np.ascontiguousarray(part_map, np.int32)
-        api._check(self._lib.avt_renderer_set_part_map(self.h, C.c_int(0 if pm is None else len(pm)), _p(pm, C.c_int)))
+        capi.check(self._lib.avt_renderer_set_part_map(self.h, C.c_int(0 if pm is None else len(pm)), capi.ptr(pm, C.c_int)))
 
     def set_ordering(self, ordering):
-        api._check(self._lib.avt_renderer_set_ordering(self.h, C.c_int(ordering)))
+        capi.check(self._lib.avt_renderer_set_ordering(self.h, C.c_int(ordering)))
 
     def upload(self, clouds, joints=None):
         """clouds (n, V, 3) or (V, 3); joints (n, J, 3), (J, 3) or None"""
         c = np.ascontiguousarray(clouds, np.float64).reshape(-1, self.V, 3)
         j = None if joints is None else np.ascontiguousarray(joints, np.float64).reshape(c.shape[0], self.J, 3)
-        api._check(self._lib.avt_renderer_upload(self.h, C.c_int(c.shape[0]), _p(c, C.c_double), _p(j, C.c_double)))
+        capi.check(self._lib.avt_renderer_upload(self.h, C.c_int(c.shape[0]), capi.ptr(c, C.c_double), capi.ptr(j, C.c_double)))
         self.n = c.shape[0]
 
     def from_context(self, ctx, frames=None, n=None):
         """the posed avatars of api.Context `ctx`'s frames (None: frames 0..n-1), copied on the device"""
         fr = None if frames is None else np.ascontiguousarray(frames, np.int32)
         n = len(fr) if fr is not None else int(n)
-        api._check(self._lib.avt_renderer_from_ctx(self.h, ctx.h, C.c_int(n), _p(fr, C.c_int)))
+        capi.check(self._lib.avt_renderer_from_ctx(self.h, ctx.h, C.c_int(n), capi.ptr(fr, C.c_int)))
         self.n = n
 
     def run(self, what=ALL):
-        api._check(self._lib.avt_renderer_run(self.h, C.c_int(what)))
+        capi.check(self._lib.avt_renderer_run(self.h, C.c_int(what)))
 
     def sync(self):
-        api._check(self._lib.avt_renderer_sync(self.h))
+        capi.check(self._lib.avt_renderer_sync(self.h))
 
     def download(self, image, what=ALL):
         """dict of the selected images of `image`: depth (H, W) float32, mask / lambert uint8, faces int32"""
@@ -87,8 +83,8 @@ class Renderer:
         if what & PART_MASK: out["mask"] = np.empty((H, W), np.uint8)
         if what & LAMBERT: out["lambert"] = np.empty((H, W), np.uint8)
         if what & FACES: out["faces"] = np.empty((H, W), np.int32)
-        api._check(self._lib.avt_renderer_download(self.h, C.c_int(image), _p(out.get("depth"), C.c_float), _p(out.get("mask"), C.c_ubyte),
-                                                   _p(out.get("lambert"), C.c_ubyte), _p(out.get("faces"), C.c_int)))
+        capi.check(self._lib.avt_renderer_download(self.h, C.c_int(image), capi.ptr(out.get("depth"), C.c_float), capi.ptr(out.get("mask"), C.c_ubyte),
+                                                   capi.ptr(out.get("lambert"), C.c_ubyte), capi.ptr(out.get("faces"), C.c_int)))
         return out
 
     def projection(self, image, joints=True):
@@ -97,15 +93,15 @@ class Renderer:
         out = dict(points=np.empty((self.V, 2), np.float32), keys=np.empty(self.F, np.float32), ordered=np.empty((self.F, 3), np.int32),
                    pos=np.empty(self.F, np.int32))
         if joints: out["joints"] = np.empty((self.J, 2), np.float32)
-        api._check(self._lib.avt_renderer_projection(self.h, C.c_int(image), _p(out["points"], C.c_float), _p(out.get("joints"), C.c_float),
-                                                     _p(out["keys"], C.c_float), _p(out["ordered"], C.c_int), _p(out["pos"], C.c_int)))
+        capi.check(self._lib.avt_renderer_projection(self.h, C.c_int(image), capi.ptr(out["points"], C.c_float), capi.ptr(out.get("joints"), C.c_float),
+                                                     capi.ptr(out["keys"], C.c_float), capi.ptr(out["ordered"], C.c_int), capi.ptr(out["pos"], C.c_int)))
         return out
 
 
     def vertex_shading(self, image):
         """(vertex normals (V, 3) float64, per-vertex Lambert values (V,) float32) of renderLambert; the last run must include LAMBERT"""
         n, lam = np.empty((self.V, 3)), np.empty(self.V, np.float32)
-        api._check(self._lib.avt_renderer_vertex_shading(self.h, C.c_int(image), _p(n, C.c_double), _p(lam, C.c_float)))
+        capi.check(self._lib.avt_renderer_vertex_shading(self.h, C.c_int(image), capi.ptr(n, C.c_double), capi.ptr(lam, C.c_float)))
         return n, lam
 
 

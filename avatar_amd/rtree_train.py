@@ -48,12 +48,6 @@ class TrainStats(C.Structure):
                     level_evals=list(self.level_evals[:L]), level_ms=list(self.level_ms[:L]))
 
 
-def _check(lib, rc):
-    if rc != 0:
-        lib.avt_last_error.restype = C.c_char_p
-        raise RuntimeError((lib.avt_last_error() or b"?").decode())
-
-
 def _images(depth, part_mask):
     d = np.ascontiguousarray(depth, np.float32)
     m = np.ascontiguousarray(part_mask, np.uint8)
@@ -76,7 +70,7 @@ class Trainer:
         self._T = min_samples_per_feature
         p = TrainParams(num_parts, num_points_per_image, num_features, max_probe_offset, min_samples, max_tree_depth, min_samples_per_feature,
                         seed & 0xFFFFFFFFFFFFFFFF)
-        _check(self._lib, self._lib.avt_rtree_trainer_create(C.c_int(device), C.byref(p), C.byref(self._h)))
+        capi.check(self._lib.avt_rtree_trainer_create(C.c_int(device), C.byref(p), C.byref(self._h)))
 
     def __del__(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -85,12 +79,12 @@ class Trainer:
 
     def add_images(self, depth, part_mask):
         d, m = _images(depth, part_mask)
-        _check(self._lib, self._lib.avt_rtree_trainer_add_images(self._h, C.c_int(d.shape[0]), C.c_int(d.shape[1]), C.c_int(d.shape[2]),
-                                                                 d.ctypes.data_as(C.POINTER(C.c_float)), m.ctypes.data_as(C.POINTER(C.c_ubyte))))
+        capi.check(self._lib.avt_rtree_trainer_add_images(self._h, C.c_int(d.shape[0]), C.c_int(d.shape[1]), C.c_int(d.shape[2]),
+                                                          capi.ptr(d, C.c_float), capi.ptr(m, C.c_ubyte)))
 
     def add_rendered(self, renderer):
         """the depth and part-mask images of renderer's (render.Renderer) last run, device to device"""
-        _check(self._lib, self._lib.avt_rtree_trainer_add_rendered(self._h, renderer.h))
+        capi.check(self._lib.avt_rtree_trainer_add_rendered(self._h, renderer.h))
 
     def root_histograms(self, n_features):
         """(n_features, num_parts, T) int32 bucket histograms of the root's first features as the device counts them, and the
@@ -98,13 +92,13 @@ class Trainer:
         T = self._T
         h = np.empty((n_features, self.num_parts, T), np.int32)
         mm = np.empty((n_features, 2), np.float32)
-        _check(self._lib, self._lib.avt_rtree_trainer_root_histograms(self._h, C.c_int(n_features), h.ctypes.data_as(C.POINTER(C.c_int)),
-                                                                      mm.ctypes.data_as(C.POINTER(C.c_float))))
+        capi.check(self._lib.avt_rtree_trainer_root_histograms(self._h, C.c_int(n_features), capi.ptr(h, C.c_int),
+                                                               capi.ptr(mm, C.c_float)))
         return h, mm
 
     def info(self):
         ni, ns = C.c_int(), C.c_longlong()
-        _check(self._lib, self._lib.avt_rtree_trainer_info(self._h, C.byref(ni), C.byref(ns)))
+        capi.check(self._lib.avt_rtree_trainer_info(self._h, C.byref(ni), C.byref(ns)))
         return ni.value, ns.value
 
     def samples(self):
@@ -112,9 +106,8 @@ class Trainer:
         _, n = self.info()
         img, x, y = (np.empty(n, np.int32) for _ in range(3))
         lab = np.empty(n, np.uint8)
-        ip = C.POINTER(C.c_int)
-        _check(self._lib, self._lib.avt_rtree_trainer_samples(self._h, img.ctypes.data_as(ip), x.ctypes.data_as(ip), y.ctypes.data_as(ip),
-                                                              lab.ctypes.data_as(C.POINTER(C.c_ubyte))))
+        capi.check(self._lib.avt_rtree_trainer_samples(self._h, capi.ptr(img, C.c_int), capi.ptr(x, C.c_int), capi.ptr(y, C.c_int),
+                                                       capi.ptr(lab, C.c_ubyte)))
         return img, x, y, lab
 
     def run(self, part_map=None, part_map_type=0):
@@ -123,8 +116,8 @@ class Trainer:
         pm = np.ascontiguousarray(part_map if part_map is not None else np.zeros(0), np.int32)
         h = C.c_void_p()
         st = TrainStats()
-        _check(self._lib, self._lib.avt_rtree_trainer_run(self._h, C.c_int(len(pm)), pm.ctypes.data_as(C.POINTER(C.c_int)), C.c_int(part_map_type),
-                                                          C.byref(h), C.byref(st)))
+        capi.check(self._lib.avt_rtree_trainer_run(self._h, C.c_int(len(pm)), capi.ptr(pm, C.c_int), C.c_int(part_map_type),
+                                                   C.byref(h), C.byref(st)))
         return RTree._from_handle(h, self.device), st.as_dict()
 
 
@@ -133,20 +126,20 @@ def transfer(tree, depth, part_mask):
     leaves never reached (they keep their weights)."""
     d, m = _images(depth, part_mask)
     z = C.c_int()
-    _check(tree._lib, tree._lib.avt_rtree_transfer_images(tree._h, C.c_int(d.shape[0]), C.c_int(d.shape[1]), C.c_int(d.shape[2]),
-                                                          d.ctypes.data_as(C.POINTER(C.c_float)), m.ctypes.data_as(C.POINTER(C.c_ubyte)),
-                                                          C.byref(z)))
+    capi.check(tree._lib.avt_rtree_transfer_images(tree._h, C.c_int(d.shape[0]), C.c_int(d.shape[1]), C.c_int(d.shape[2]),
+                                                   capi.ptr(d, C.c_float), capi.ptr(m, C.c_ubyte),
+                                                   C.byref(z)))
     tree._refresh()
     return z.value
 
 
 def transfer_rendered(tree, renderer):
     """adds the trainTransfer counts of renderer's last depth + part-mask run (device to device); transfer_finish applies them"""
-    _check(tree._lib, tree._lib.avt_rtree_transfer_rendered(tree._h, renderer.h))
+    capi.check(tree._lib.avt_rtree_transfer_rendered(tree._h, renderer.h))
 
 
 def transfer_finish(tree):
     z = C.c_int()
-    _check(tree._lib, tree._lib.avt_rtree_transfer_finish(tree._h, C.byref(z)))
+    capi.check(tree._lib.avt_rtree_transfer_finish(tree._h, C.byref(z)))
     tree._refresh()
     return z.value

@@ -24,22 +24,14 @@ def frames_of_rank(num_frames, rank, world):
     return list(range(rank, num_frames, world))
 
 
-def _check(rc):
-    if rc != 0:
-        from .api import AvtError
-        e = AvtError(capi.load_library().avt_last_error().decode())
-        e.status = rc
-        raise e
-
-
 def pack_model(arrays: capi.ModelArrays) -> bytes:
     """avt_model_pack: the relocatable byte block the model broadcast ships."""
     lib = capi.load_library()
     desc = arrays.desc()
     n = C.c_size_t()
-    _check(lib.avt_model_pack_size(C.byref(desc), C.byref(n)))
+    capi.check(lib.avt_model_pack_size(C.byref(desc), C.byref(n)))
     buf = C.create_string_buffer(n.value)
-    _check(lib.avt_model_pack(C.byref(desc), buf, n))
+    capi.check(lib.avt_model_pack(C.byref(desc), buf, n))
     return buf.raw
 
 
@@ -48,7 +40,7 @@ def unpack_model(block: bytes):
     lib = capi.load_library()
     h = C.c_void_p()
     buf = C.create_string_buffer(block, len(block))
-    _check(lib.avt_model_unpack(buf, C.c_size_t(len(block)), C.byref(h)))
+    capi.check(lib.avt_model_unpack(buf, C.c_size_t(len(block)), C.byref(h)))
     return h
 
 
@@ -60,7 +52,7 @@ def exchange_unique_id(dist, rank, src=0, rccl=True):
     if rank == src:
         if rccl:
             buf = C.create_string_buffer(ID_BYTES)
-            _check(lib.avt_shard_unique_id(buf))
+            capi.check(lib.avt_shard_unique_id(buf))
             box[0] = buf.raw
         else:
             import os
@@ -79,11 +71,11 @@ class Shard:
         self._lib = capi.load_library()
         self.h = C.c_void_p()
         if loopback_group is not None:
-            _check(self._lib.avt_shard_create_loopback(C.c_int(device), C.c_int(rank), C.c_int(world), loopback_group.encode(), C.byref(self.h)))
+            capi.check(self._lib.avt_shard_create_loopback(C.c_int(device), C.c_int(rank), C.c_int(world), loopback_group.encode(), C.byref(self.h)))
         elif shm:
-            _check(self._lib.avt_shard_create_shm(C.c_int(device), C.c_int(rank), C.c_int(world), unique_id, C.byref(self.h)))
+            capi.check(self._lib.avt_shard_create_shm(C.c_int(device), C.c_int(rank), C.c_int(world), unique_id, C.byref(self.h)))
         else:
-            _check(self._lib.avt_shard_create(C.c_int(device), C.c_int(rank), C.c_int(world), unique_id, C.byref(self.h)))
+            capi.check(self._lib.avt_shard_create(C.c_int(device), C.c_int(rank), C.c_int(world), unique_id, C.byref(self.h)))
         self.rank, self.world = rank, world
         self.backend = self._lib.avt_shard_backend(self.h).decode()
 
@@ -105,7 +97,7 @@ class Shard:
         """arrays: capi.ModelArrays on root (ignored elsewhere). Returns an avt_model* built from the broadcast bytes."""
         h = C.c_void_p()
         desc = arrays.desc() if (self.rank == root and arrays is not None) else None
-        _check(self._lib.avt_shard_broadcast_model(self.h, C.c_int(root), C.byref(desc) if desc is not None else None, C.byref(h)))
+        capi.check(self._lib.avt_shard_broadcast_model(self.h, C.c_int(root), C.byref(desc) if desc is not None else None, C.byref(h)))
         return h
 
     def scatter_frames(self, ctx, num_frames, datas=None, labels=None, p=None, q=None, w=None, root=0):
@@ -122,22 +114,22 @@ class Shard:
             args = (dptr(data), iptr(lab), iptr(offs), dptr(p), dptr(q), dptr(w))
         else:
             args = (None,) * 6
-        _check(self._lib.avt_shard_scatter_frames(self.h, ctx.h, C.c_int(root), C.c_int(num_frames), *args))
+        capi.check(self._lib.avt_shard_scatter_frames(self.h, ctx.h, C.c_int(root), C.c_int(num_frames), *args))
         nloc = len(self.local_frames(num_frames))
         ctx._F = nloc
 
     def gather_enqueue(self, ctx, num_frames):
-        _check(self._lib.avt_shard_gather_enqueue(self.h, ctx.h, C.c_int(num_frames)))
+        capi.check(self._lib.avt_shard_gather_enqueue(self.h, ctx.h, C.c_int(num_frames)))
 
     def gather_wait(self):
         """Blocks until the last enqueued all-gather is complete."""
-        _check(self._lib.avt_shard_gather_wait(self.h))
+        capi.check(self._lib.avt_shard_gather_wait(self.h))
 
     def gather_download(self, ctx, num_frames):
         m = ctx.model
         p = np.empty((num_frames, 3)); q = np.empty((num_frames, m.numJoints() * 4)); w = np.empty((num_frames, m.numShapeKeys()))
         st = (Stats * num_frames)()
-        _check(self._lib.avt_shard_gather_download(self.h, ctx.h, C.c_int(num_frames), dptr(p), dptr(q), dptr(w), st))
+        capi.check(self._lib.avt_shard_gather_download(self.h, ctx.h, C.c_int(num_frames), dptr(p), dptr(q), dptr(w), st))
         return p, q.reshape(num_frames, -1, 4), w, list(st)
 
     def gather_results(self, ctx, num_frames):
@@ -146,10 +138,10 @@ class Shard:
 
     def set_self_exchange(self, on=True):
         """Dry runs: a rank's own blocks go through the transport as well (include/avt_shard.h, avt_shard_set_self_exchange)."""
-        _check(self._lib.avt_shard_set_self_exchange(self.h, C.c_int(int(bool(on)))))
+        capi.check(self._lib.avt_shard_set_self_exchange(self.h, C.c_int(int(bool(on)))))
 
     def barrier(self, ctx=None):
-        _check(self._lib.avt_shard_barrier(self.h, ctx.h if ctx is not None else None))
+        capi.check(self._lib.avt_shard_barrier(self.h, ctx.h if ctx is not None else None))
 
 
 def gather_results(local, num_frames, rank, world, dist, device=None):

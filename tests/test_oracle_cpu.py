@@ -317,6 +317,27 @@ def test_abi_library_exports_every_declared_symbol():
         assert hasattr(lib, s), s
 
 
+def test_every_wrapper_raises_avt_error_with_the_status(gmodel):
+    """An argument the library rejects before its first device call: every wrapper module raises capi.AvtError (a RuntimeError)
+    with the status code and the library's message, not a bare RuntimeError without one."""
+    from avatar_amd import bgsub, render, rtree, rtree_train
+    calls = [
+        (lambda: rtree_train.Trainer(num_parts=0),
+         "avt_rtree_trainer_create: bad parameters (1 <= num_parts <= 127, points / features / T >= 1, max_probe_offset > 0.5, "
+         "min_samples >= 0, 1 <= max_tree_depth <= 64, num_parts x T <= 8192)"),
+        (lambda: bgsub.BGSubtractor(np.zeros((4, 70000, 3), np.float32)),
+         "avt_bgsub_create: bad arguments (rows, cols > 0, cols < 65536, n_backgrounds > 0)"),
+        (lambda: rtree.RTree(os.path.join(HERE, "golden", "forest_small.srtr"), device=-1).predictBest(np.ones((8, 8), np.float32)),
+         "rtree: created host-only (device < 0): inference needs a GPU"),
+        (lambda: render.Renderer(gmodel, 0, 10, synth.K4A_INTRIN),
+         "avt_renderer_create: bad arguments (model, width, height, max_images > 0)"),
+    ]
+    for call, message in calls:
+        with pytest.raises(capi.AvtError) as e:
+            call()
+        assert type(e.value) is capi.AvtError and e.value.status == 1 and str(e.value) == message, (e.value, getattr(e.value, "status", None))
+
+
 def test_struct_layouts_match_header():
     assert ctypes.sizeof(capi.Options) == 8 * 2 + 4 * 6 + 8 * 6
     assert ctypes.sizeof(capi.Stats) == 8 * 3 + 4 * 4
