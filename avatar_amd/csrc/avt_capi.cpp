@@ -25,10 +25,10 @@ namespace {
 
 template <class T>
 int dev_alloc(avt_ctx* c, T** p, size_t n) {
-    void* q = nullptr;
-    AVT_HIP(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));   // an empty table still gets a pointer the kernels may be handed
-    c->allocs.push_back(q);
-    *p = (T*)q;
+    DevBuf<char> b;
+    if (b.reserve(std::max<size_t>(n, 1) * sizeof(T))) return 1;   // an empty table still gets a pointer the kernels may be handed
+    *p = (T*)b.p;
+    c->owned.push_back(std::move(b));
     return 0;
 }
 template <class T>
@@ -362,31 +362,42 @@ int run_optimize(avt_ctx* c, const avt_options* o, const int* budget = nullptr) 
     return 0;
 }
 
-// Installs `nframes` frames with `counts[f]` points each; data / labels are packed back to back (frame f starts at the sum
+// The context's record of which frames are resident: `count_of(f)` points in frame f.  The counts are validated first - nothing changes when it
+// fails - then nframes, frame_N, frame_off and launch_maxN are written, and what described the old frames' correspondences and results is dropped.
+// frames_valid / state_valid are the caller's.  (A callable, not an array: the host-to-host call has offsets and must not allocate.)
+template <class CountOf>
+int set_resident_frames(avt_ctx* c, int nframes, CountOf count_of) {
+    if (nframes <= 0 || nframes > c->fb.max_frames) { avt_set_error("frames: nframes out of range for this context"); return 1; }
+    int mx = 0;
+    for (int f = 0; f < nframes; ++f) {
+        const int n = count_of(f);
+        if (n < 0) { avt_set_error("frames: negative point count (frame_offsets must be non-decreasing)"); return 1; }
+        if (n > c->fb.max_points) { avt_set_error("frames: a frame has more points than max_points_per_frame"); return 1; }
+        mx = std::max(mx, n);
+    }
+    c->have_moments = c->have_records = false;      // new frames: the moments / records of the old correspondences describe nothing resident
+    c->results_fresh = false;
+    c->nframes = nframes;
+    c->frame_N.resize(nframes);
+    c->frame_off.assign(nframes + 1, 0);
+    for (int f = 0; f < nframes; ++f) { c->frame_N[f] = count_of(f); c->frame_off[f + 1] = c->frame_off[f] + c->frame_N[f]; }
+    c->launch_maxN = std::max(mx, std::min(c->fb.max_points, ((mx + 2047) / 2048) * 2048));
+    return 0;
+}
+
+// Installs `nframes` frames with `count_of(f)` points each; data / labels are packed back to back (frame f starts at the sum
 // of the previous counts) in host memory or, with device_src, in device memory (the batch split's receive buffer).
 // Everything is validated before any host or device state changes.  The per-frame point count is also written into the
 // device control blocks (working copy and start copy), so that swapping frames under a resident state - the warm-start
 // pattern avt_frames_upload + avt_optimize_resident - runs with the new counts.
-int install_frames(avt_ctx* c, int nframes, const int* counts, const double* data, const int* labels, bool device_src) {
-    if (nframes <= 0 || nframes > c->fb.max_frames) { avt_set_error("frames: nframes out of range for this context"); return 1; }
-    int mx = 0;
-    for (int f = 0; f < nframes; ++f) {
-        if (counts[f] < 0) { avt_set_error("frames: negative point count (frame_offsets must be non-decreasing)"); return 1; }
-        if (counts[f] > c->fb.max_points) { avt_set_error("frames: a frame has more points than max_points_per_frame"); return 1; }
-        mx = std::max(mx, counts[f]);
-    }
+template <class CountOf>
+int install_frames(avt_ctx* c, int nframes, CountOf count_of, const double* data, const int* labels, bool device_src) {
     const bool same_shape = c->frames_valid && nframes == c->nframes;
+    if (set_resident_frames(c, nframes, count_of)) return 1;
     c->frames_valid = false;
-    c->have_moments = c->have_records = false;      // new frames: the moments / records of the old correspondences describe nothing resident
-    c->results_fresh = false;
-    c->nframes = nframes;
-    c->frame_N.assign(counts, counts + nframes);
-    c->frame_off.assign(nframes + 1, 0);
-    for (int f = 0; f < nframes; ++f) c->frame_off[f + 1] = c->frame_off[f] + counts[f];
-    c->launch_maxN = std::max(mx, std::min(c->fb.max_points, ((mx + 2047) / 2048) * 2048));
     const hipMemcpyKind kind = device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     for (int f = 0; f < nframes; ++f) {
-        const size_t N = (size_t)counts[f], o = (size_t)c->frame_off[f];
+        const size_t N = (size_t)c->frame_N[f], o = (size_t)c->frame_off[f];
         if (N == 0) continue;
         AVT_HIP(hipMemcpyAsync(c->fb.data_raw + (size_t)f * c->fb.max_points * 3, data + o * 3, N * 3 * sizeof(double), kind, c->stream));
         AVT_HIP(hipMemcpyAsync(c->fb.labels_raw + (size_t)f * c->fb.max_points, labels + o, N * sizeof(int), kind, c->stream));
@@ -400,10 +411,8 @@ int install_frames(avt_ctx* c, int nframes, const int* counts, const double* dat
 }
 
 int upload_frames(avt_ctx* c, int nframes, const double* data, const int* labels, const int* offs) {
-    if (nframes <= 0 || nframes > c->fb.max_frames) { avt_set_error("frames: nframes out of range for this context"); return 1; }
-    std::vector<int> counts(nframes);
-    for (int f = 0; f < nframes; ++f) counts[f] = offs[f + 1] - offs[f];
-    return install_frames(c, nframes, counts.data(), data + (size_t)offs[0] * 3, labels + offs[0], false);
+    const size_t first = nframes > 0 ? (size_t)offs[0] : 0;      // (a bad nframes is install_frames' to reject: no entry of offs is read for it)
+    return install_frames(c, nframes, [&](int f) { return offs[f + 1] - offs[f]; }, data + first * 3, labels + first, false);
 }
 
 int upload_state(avt_ctx* c, int nframes, const double* p, const double* q, const double* w) {
@@ -412,10 +421,7 @@ int upload_state(avt_ctx* c, int nframes, const double* p, const double* q, cons
     std::vector<double> xs((size_t)nframes * 2 * d.xsize, 0.0);
     std::vector<AvtFrameCtl> ctl(nframes);
     for (int f = 0; f < nframes; ++f) {
-        double* x = &xs[(size_t)f * 2 * d.xsize];
-        std::copy(p + 3 * f, p + 3 * f + 3, x);
-        std::copy(q + (size_t)4 * d.J * f, q + (size_t)4 * d.J * (f + 1), x + 3);
-        std::copy(w + (size_t)d.K * f, w + (size_t)d.K * (f + 1), x + 3 + 4 * d.J);
+        pack_state_row(d, &xs[(size_t)f * 2 * d.xsize], p, q, w, f);
         std::memset(&ctl[f], 0, sizeof(AvtFrameCtl));
         ctl[f].N = c->frame_N[f];
         ctl[f].comp_cur = -1;
@@ -430,6 +436,16 @@ int upload_state(avt_ctx* c, int nframes, const double* p, const double* q, cons
     return 0;
 }
 
+// "report once, then clear": the message of the host-pointer and the staged calls for frames whose fault word is set
+int report_device_fault(avt_ctx* c, int nbad, int first, unsigned bits) {
+    char msg[256];
+    snprintf(msg, sizeof msg, "optimize: %d frame(s) carry a device fault (first: frame %d, bits 0x%x%s); their result is not valid", nbad, first,
+             bits, (bits & AVT_FAULT_RIDE_TIMEOUT) ? ": a solver gave up waiting for the in-launch reduction" : "");
+    if (avt_internal_clear_faults(c)) return 1;
+    avt_set_error(msg);
+    return AVT_STATUS_DEVICE_FAULT;
+}
+
 int download_state(avt_ctx* c, double* p, double* q, double* w, avt_stats* st) {
     const AvtDims& d = c->dm.d;
     const int nf = c->nframes;
@@ -442,21 +458,9 @@ int download_state(avt_ctx* c, double* p, double* q, double* w, avt_stats* st) {
     AVT_HIP(hipStreamSynchronize(c->stream));
     int bad = -1, nbad = 0;
     for (int f = 0; f < nf; ++f) if (fault[f]) { if (bad < 0) bad = f; ++nbad; }
-    if (bad >= 0) {     // reported once, then cleared: the next optimize() starts clean
-        char msg[256];
-        snprintf(msg, sizeof msg, "optimize: %d frame(s) carry a device fault (first: frame %d, bits 0x%x%s); their result is not valid", nbad, bad,
-                 fault[bad], (fault[bad] & AVT_FAULT_RIDE_TIMEOUT) ? ": a solver gave up waiting for the in-launch reduction" : "");
-        AVT_HIP(hipMemsetAsync(c->fb.fault, 0, (size_t)c->fb.max_frames * sizeof(unsigned), c->stream));
-        AVT_HIP(hipStreamSynchronize(c->stream));
-        c->results_fresh = false;      //  the result records carry the word that was just cleared: a later gather packs them again
-        avt_set_error(msg);
-        return AVT_STATUS_DEVICE_FAULT;
-    }
+    if (bad >= 0) return report_device_fault(c, nbad, bad, fault[bad]);
     for (int f = 0; f < nf; ++f) {
-        const double* x = &xs[((size_t)f * 2 + ctl[f].cur_slot) * d.xsize];
-        if (p) std::copy(x, x + 3, p + 3 * f);
-        if (q) std::copy(x + 3, x + 3 + 4 * d.J, q + (size_t)4 * d.J * f);
-        if (w) std::copy(x + 3 + 4 * d.J, x + d.xsize, w + (size_t)d.K * f);
+        unpack_state_row(d, &xs[((size_t)f * 2 + ctl[f].cur_slot) * d.xsize], p, q, w, f);
         if (st) {
             st[f].initial_cost = ctl[f].cost_initial;
             st[f].final_cost = ctl[f].cost_cur;
@@ -473,7 +477,7 @@ int download_state(avt_ctx* c, double* p, double* q, double* w, avt_stats* st) {
 // avt_optimize / avt_optimize_batch on HOST pointers - the reference's call shape, optimize(const CloudType&, const VectorXi&, ..)
 // (AvatarOptimizer.h:17-19) - as one pass with ONE host synchronisation: clouds, labels, start states and control blocks are gathered in
 // the context's pinned staging block and leave as asynchronous copies (no pageable-memory staging inside the runtime, no wait between
-// them), the fit is enqueued behind them, k_pack_results puts (p, q, w), the statistics and the fault word of every frame into one block
+// them), the fit is enqueued behind them, its closing k_lbs launch (k_pack_results where there is none) puts (p, q, w), the statistics and the fault word of every frame into one block
 // and ONE copy brings it back.  (The four-stage path - upload, upload, run, download, a synchronisation each - measured 81 + 26 + 58 us
 // on top of the 0.41 ms fit of one 38 k-point frame, tools/host_call_breakdown.py.)  Leaves the context exactly as the staged calls do:
 // frames and start state resident, avt_state_reset / avt_optimize_resident usable afterwards.
@@ -481,17 +485,11 @@ int download_state(avt_ctx* c, double* p, double* q, double* w, avt_stats* st) {
 int optimize_host_to_host(avt_ctx* c, int nframes, const double* data, const int* labels, const int* offs, const avt_options* o,
                           double* p, double* q, double* w, avt_stats* st, double* posed_cloud = nullptr, double* posed_jpos = nullptr, double* posed_jtrans = nullptr) {
     const AvtDims& d = c->dm.d;
-    if (nframes <= 0 || nframes > c->fb.max_frames) { avt_set_error("frames: nframes out of range for this context"); return 1; }
-    long long total = 0;
-    int mx = 0;
-    for (int f = 0; f < nframes; ++f) {
-        const int n = offs[f + 1] - offs[f];
-        if (n < 0) { avt_set_error("frames: negative point count (frame_offsets must be non-decreasing)"); return 1; }
-        if (n > c->fb.max_points) { avt_set_error("frames: a frame has more points than max_points_per_frame"); return 1; }
-        mx = std::max(mx, n); total += n;
-    }
-    const int xs = d.xsize, stride = xs + 8;
-    const size_t b_data = (size_t)total * 24, b_lab = ((size_t)total * 4 + 15) & ~(size_t)15, b_x = (size_t)nframes * 2 * xs * 8,
+    if (set_resident_frames(c, nframes, [&](int f) { return offs[f + 1] - offs[f]; })) return 1;
+    c->frames_valid = c->state_valid = false;      // until the copies below are enqueued
+    const size_t total = (size_t)c->frame_off[nframes];
+    const int xs = d.xsize, stride = result_stride(d);
+    const size_t b_data = total * 24, b_lab = (total * 4 + 15) & ~(size_t)15, b_x = (size_t)nframes * 2 * xs * 8,
                  b_ctl = (size_t)nframes * sizeof(AvtFrameCtl), b_res = (size_t)nframes * stride * 8;
     const bool want_posed = posed_cloud || posed_jpos || posed_jtrans;
     const size_t b_posed = want_posed ? (size_t)(3 * d.V + 15 * d.J) * 8 : 0;
@@ -509,22 +507,12 @@ int optimize_host_to_host(avt_ctx* c, int nframes, const double* data, const int
     char* pin = c->host_pin;
     double* h_data = (double*)pin; int* h_lab = (int*)(pin + b_data); double* h_x = (double*)(pin + b_data + b_lab);
     AvtFrameCtl* h_ctl = (AvtFrameCtl*)(pin + b_data + b_lab + b_x); double* h_res = (double*)(pin + b_data + b_lab + b_x + b_ctl);
-    // the context's bookkeeping of the resident frames (install_frames)
-    c->frames_valid = c->state_valid = false;
-    c->have_moments = c->have_records = false;
-    c->nframes = nframes;
-    c->frame_N.resize(nframes); c->frame_off.assign(nframes + 1, 0);
-    for (int f = 0; f < nframes; ++f) { c->frame_N[f] = offs[f + 1] - offs[f]; c->frame_off[f + 1] = c->frame_off[f] + c->frame_N[f]; }
-    c->launch_maxN = std::max(mx, std::min(c->fb.max_points, ((mx + 2047) / 2048) * 2048));
     std::memcpy(h_data, data + (size_t)offs[0] * 3, b_data);
-    std::memcpy(h_lab, labels + offs[0], (size_t)total * 4);
+    std::memcpy(h_lab, labels + offs[0], total * 4);
     std::memset(h_x, 0, b_x);
     std::memset((void*)h_ctl, 0, b_ctl);
     for (int f = 0; f < nframes; ++f) {
-        double* x = h_x + (size_t)f * 2 * xs;
-        std::copy(p + 3 * (size_t)f, p + 3 * (size_t)f + 3, x);
-        std::copy(q + (size_t)4 * d.J * f, q + (size_t)4 * d.J * (f + 1), x + 3);
-        std::copy(w + (size_t)d.K * f, w + (size_t)d.K * (f + 1), x + 3 + 4 * d.J);
+        pack_state_row(d, h_x + (size_t)f * 2 * xs, p, q, w, f);
         h_ctl[f].N = c->frame_N[f];
         h_ctl[f].comp_cur = -1;
     }
@@ -544,9 +532,8 @@ int optimize_host_to_host(avt_ctx* c, int nframes, const double* data, const int
         AVT_HIP(hipMemcpyAsync(c->fb.ctl_start, c->fb.ctl, b_ctl, hipMemcpyDeviceToDevice, c->stream));
     }
     c->frames_valid = c->state_valid = true;
-    c->results_fresh = false;
     if (run_optimize(c, o)) { c->results_fresh = false; return 1; }
-    if (!c->results_fresh) { launch_pack_results(c, nframes, c->fb.results, stride); c->results_fresh = true; }      // (a call without ICP iterations has no closing k_lbs launch)
+    if (!c->results_fresh) { launch_pack_results(c, nframes); c->results_fresh = true; }      // (a call without ICP iterations has no closing k_lbs launch)
     AVT_HIP(hipMemcpyAsync(h_res, c->fb.results, b_res, hipMemcpyDeviceToHost, c->stream));
     double* h_posed = (double*)(pin + b_data + b_lab + b_x + b_ctl + b_res);
     if (want_posed) {      // frame 0's posed outputs into the pinned block, behind the fit, in front of the one synchronisation
@@ -557,35 +544,28 @@ int optimize_host_to_host(avt_ctx* c, int nframes, const double* data, const int
     AVT_HIP(hipStreamSynchronize(c->stream));      // the one synchronisation of the call
     int bad = -1, nbad = 0;
     unsigned badbits = 0;
-    for (int f = 0; f < nframes; ++f) {
-        const double* x = h_res + (size_t)f * stride;
-        if (x[xs + 7] != 0.0) { if (bad < 0) { bad = f; badbits = (unsigned)x[xs + 7]; } ++nbad; }
-    }
-    if (bad >= 0) {     // reported once, then cleared (download_state's rule)
-        char msg[256];
-        snprintf(msg, sizeof msg, "optimize: %d frame(s) carry a device fault (first: frame %d, bits 0x%x%s); their result is not valid", nbad, bad,
-                 badbits, (badbits & AVT_FAULT_RIDE_TIMEOUT) ? ": a solver gave up waiting for the in-launch reduction" : "");
-        AVT_HIP(hipMemsetAsync(c->fb.fault, 0, (size_t)c->fb.max_frames * sizeof(unsigned), c->stream));
-        AVT_HIP(hipStreamSynchronize(c->stream));
-        c->results_fresh = false;      //  the records carry the word that was just cleared: a later gather packs them again
-        avt_set_error(msg);
-        return AVT_STATUS_DEVICE_FAULT;
-    }
+    for (int f = 0; f < nframes; ++f)      // a faulty frame anywhere: nothing is handed back
+        if (const unsigned bits = unpack_result_row(d, h_res + (size_t)f * stride, nullptr, nullptr, nullptr, nullptr, f)) { if (bad < 0) { bad = f; badbits = bits; } ++nbad; }
+    if (bad >= 0) return report_device_fault(c, nbad, bad, badbits);
     if (posed_cloud) std::memcpy(posed_cloud, h_posed, (size_t)3 * d.V * 8);
     if (posed_jpos) std::memcpy(posed_jpos, h_posed + 3 * d.V, (size_t)3 * d.J * 8);
     if (posed_jtrans) std::memcpy(posed_jtrans, h_posed + 3 * d.V + 3 * d.J, (size_t)12 * d.J * 8);
-    for (int f = 0; f < nframes; ++f) {
-        const double* x = h_res + (size_t)f * stride;
-        std::copy(x, x + 3, p + 3 * (size_t)f);
-        std::copy(x + 3, x + 3 + 4 * d.J, q + (size_t)4 * d.J * f);
-        std::copy(x + 3 + 4 * d.J, x + xs, w + (size_t)d.K * f);
-        if (st) {
-            const double* t = x + xs;
-            st[f].initial_cost = t[0]; st[f].final_cost = t[1]; st[f].lambda = t[2];
-            st[f].num_correspondences = (int)t[3]; st[f].matched_model_points = (int)t[4];
-            st[f].gn_iterations = (int)t[5]; st[f].accepted_steps = (int)t[6];
-        }
-    }
+    for (int f = 0; f < nframes; ++f) unpack_result_row(d, h_res + (size_t)f * stride, p, q, w, st, f);
+    return 0;
+}
+
+// The parameters of a stand-alone skinning (Avatar::update of `nframes` avatars) staged in the prep buffer, which nothing else uses
+// outside optimize(): w | p | R.  `who`: the entry point, for the message.
+struct StagedPose { double *w, *p, *R; };
+int stage_pose(avt_ctx* c, const char* who, int nframes, const double* w, const double* p, const double* R, StagedPose* s) {
+    const AvtDims& d = c->dm.d;
+    if ((size_t)nframes * (d.K + 3 + 9 * d.J) > (size_t)c->fb.max_frames * 2 * d.prep_size) { avt_set_error(std::string(who) + ": staging overflow"); return 1; }
+    s->w = c->fb.prep;
+    s->p = s->w + (size_t)nframes * d.K;
+    s->R = s->p + (size_t)nframes * 3;
+    AVT_HIP(hipMemcpyAsync(s->w, w, (size_t)nframes * d.K * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    AVT_HIP(hipMemcpyAsync(s->p, p, (size_t)nframes * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    AVT_HIP(hipMemcpyAsync(s->R, R, (size_t)nframes * 9 * d.J * sizeof(double), hipMemcpyHostToDevice, c->stream));
     return 0;
 }
 
@@ -593,7 +573,15 @@ int optimize_host_to_host(avt_ctx* c, int nframes, const double* data, const int
 
 // batch split (avt_shard.cpp): frames received into a device buffer become this context's resident frames
 int avt_internal_install_frames(avt_ctx* c, int nframes, const int* counts, const double* data, const int* labels, int device_src) {
-    return install_frames(c, nframes, counts, data, labels, device_src != 0);
+    return install_frames(c, nframes, [&](int f) { return counts[f]; }, data, labels, device_src != 0);
+}
+
+// a fault is reported once: the next optimize() starts clean, and a later gather packs the result records again
+int avt_internal_clear_faults(avt_ctx* c) {
+    c->results_fresh = false;      //  the records carry the word that is being cleared
+    AVT_HIP(hipMemsetAsync(c->fb.fault, 0, (size_t)c->fb.max_frames * sizeof(unsigned), c->stream));
+    AVT_HIP(hipStreamSynchronize(c->stream));
+    return 0;
 }
 
 extern "C" {
@@ -609,31 +597,13 @@ static int ctx_create_impl(int device, const avt_model* m, int num_parts, const 
     }
     if (device < 0 || device >= ndev) { avt_set_error("avt_ctx_create: device index out of range"); return 1; }
     AVT_HIP(hipSetDevice(device));
-    avt_ctx* c = new avt_ctx();     // value-initialised: every handle starts null, avt_ctx_destroy copes with a partial context
+    avt_ctx* c = new avt_ctx();     // (its member initialisers: every handle starts null, avt_ctx_destroy copes with a partial context)
     *out = c;
     c->device = device;
     c->model = m;
-    c->profiling = false;
-    c->prof_mask = 0xffffffffu;
-    c->event_pool_used = 0;
-    c->nframes = 0;
-    c->ran_icp_iters = 0;
-    c->ran_max_iters = 0;
-    c->launch_maxN = 0;
     c->tun = tuning_from_environment();
     if (validate_tuning(c->tun)) return 1;
-    c->lbs_cleared = false;
-    c->scatter_in_compact = false;
-    c->nn_from_cloud = false;
     { hipDeviceProp_t pr; c->num_cus = hipGetDeviceProperties(&pr, device) == hipSuccess ? pr.multiProcessorCount : 0; }
-    c->vis_frame_min = 0;            // set once the model dimensions are known (below)
-    c->graph_clock = 0;
-    c->params_valid = false;
-    c->frames_valid = c->state_valid = false;
-    c->have_moments = c->have_records = false;
-    c->concurrent_groups = 1;
-    c->host_pin = nullptr; c->host_pin_cap = 0; c->results_fresh = false;
-    c->render_img_frames = c->render_img_w = c->render_img_h = 0;
     AVT_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     AVT_HIP(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
     for (int i = 0; i < AVT_MAX_GROUPS - 1; ++i) {
@@ -681,7 +651,6 @@ static int ctx_create_impl(int device, const avt_model* m, int num_parts, const 
         dev_upload(c, &dm.mom_m1, m->mom_m1) || dev_upload(c, &dm.mom_s2_start, m->mom_s2_start) || dev_upload(c, &dm.mom_s2, m->mom_s2) || dev_upload(c, &dm.mom_s2_jj, m->mom_s2_jj) || dev_upload(c, &dm.mom_z2_jj, m->mom_z2_jj) || dev_upload(c, &dm.mom_tab16, m->mom_tab16))
         return 1;
     FrameBuffers& fb = c->fb;
-    std::memset(&fb, 0, sizeof(fb));
     fb.max_frames = max_frames;
     fb.max_points = max_points;
     fb.G = choose_G(max_frames, 1, c->tun);
@@ -709,7 +678,7 @@ static int ctx_create_impl(int device, const avt_model* m, int num_parts, const 
         dev_alloc(c, &fb.rec, (size_t)max_frames * d.nb_max * 4 * d.rec_quad) || dev_alloc(c, &fb.partial, part_cap * d.NPAIR * 256) || dev_alloc(c, &fb.wmask, part_cap) || dev_alloc(c, &fb.bmask, (size_t)max_frames * d.nb_max) || dev_alloc(c, &fb.erange, (size_t)max_frames * AVT_ERANGE) || dev_alloc(c, &fb.Hraw, (size_t)max_frames * 2 * d.HS * d.HS) ||
         dev_alloc(c, &fb.prior, (size_t)max_frames * 2 * AVT_MAX_COMPS * AVT_PRIOR_STRIDE) ||
         dev_alloc(c, &fb.jointpos, (size_t)max_frames * 3 * J) || dev_alloc(c, &fb.jointtrans, (size_t)max_frames * 12 * J) ||
-        dev_alloc(c, &fb.trace, (size_t)max_frames * 64) || dev_alloc(c, &fb.results, (size_t)max_frames * (d.xsize + 8)))
+        dev_alloc(c, &fb.trace, (size_t)max_frames * 64) || dev_alloc(c, &fb.results, (size_t)max_frames * result_stride(d)))
         return 1;
     {   // the states and control blocks and their start copies are ONE allocation, [x | ctl | x_start | ctl_start]: a context used at its full frame
         // count (the facade's: one frame) uploads state + control block with one copy and keeps the start copy with one more (round 6: they were four)
@@ -717,19 +686,16 @@ static int ctx_create_impl(int device, const avt_model* m, int num_parts, const 
         fb.x = (double*)state_block; fb.ctl = (AvtFrameCtl*)(state_block + bx);
         fb.x_start = (double*)(state_block + bx + bc); fb.ctl_start = (AvtFrameCtl*)(state_block + 2 * bx + bc);
     }
-    fb.use_moments = 0;
     if (d.mom_ok) {      // moment form of the data term (avt_moments.hip): T per (frame, joint pair), D per (frame, joint), scratch of the assembly
         if (dev_alloc(c, &fb.mom_T, (size_t)max_frames * avt_moments_T_doubles(d)) || dev_alloc(c, &fb.mom_D, (size_t)max_frames * J * d.mom_npsi * 3) ||
             dev_alloc(c, &fb.mom_E, (size_t)max_frames * 2) || dev_alloc(c, &fb.mom_rec, (size_t)max_frames * avt_moments_frame_scratch(d)))
             return 1;
         AVT_HIP(hipMemsetAsync(fb.mom_D, 0, (size_t)max_frames * J * d.mom_npsi * 3 * sizeof(double), c->stream));      // joints no vertex is assigned to keep zeros
     }
-    c->data_term = AVT_DATA_TERM_AUTO;
-    // (tun.mom_min_frames = 8, round 5 - ms per step moments / rows, frames per launch [frames per GPU]: 4 [4] 0.701 / 0.648, 6 [6] 0.710 / 0.692, 8 [8] 0.709 / 0.724,
+    // (data_term starts as AUTO; tun.mom_min_frames = 8, round 5 - ms per step moments / rows, frames per launch [frames per GPU]: 4 [4] 0.701 / 0.648, 6 [6] 0.710 / 0.692, 8 [8] 0.709 / 0.724,
     //  12 [12] 0.747 / 0.787, 16 [16] 0.737 / 0.800, 12 [24] 0.777 / 0.877, 16 [32] 0.838 / 0.938, 24 [48] 0.934 / 1.075, 28 [56] 0.985 / 1.186; dense frames 8 [8] 0.757 / 0.777,
     //  16 [16] 0.817 / 0.884; tools/ab_env.sh AVT_MOM_MIN_FRAMES.  Round 4's crossover was 32 frames per launch: the assembly as role workgroups, the decide-only closing
     //  pass and the XCD frame mapping took 15 % off the moment form's GN iteration since)
-    c->last_run_moments = false;
     {
         AvtRunParams* pr = nullptr;
         if (dev_alloc(c, &pr, 1)) return 1;
@@ -748,7 +714,6 @@ static int ctx_create_impl(int device, const avt_model* m, int num_parts, const 
     fb.ride_timeout = c->tun.ride_timeout_us * 100;      // wall_clock64() ticks at 100 MHz; 0 makes every wait that is not already satisfied fail (tests)
     fb.xcd_frames = c->tun.xcd_frames;
     AVT_HIP(hipMemsetAsync(fb.spec, 0, (size_t)max_frames * sizeof(AvtSpecCtl), c->stream));
-    fb.nspec = 0; fb.seq = 0;
     AVT_HIP(hipMemsetAsync(fb.part_cnt, 0, (size_t)max_frames * 2 * (AVT_MAX_PARTS + 1) * sizeof(int), c->stream));   // invariant of launch_bucket
     AVT_HIP(hipStreamSynchronize(c->stream));
     if (c->tun.debug) avt_eval_report_occupancy(dm.d);
@@ -772,9 +737,8 @@ void avt_ctx_destroy(avt_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (void* p : c->allocs) (void)hipFree(p);
     if (c->host_pin) (void)hipHostFree(c->host_pin);
-    // the render scratch (DevBuf members) goes with `delete`, after the events and the streams: the main stream has just been
+    // every device buffer (DevBuf members) goes with `delete`, after the events and the streams: the main stream has just been
     // drained and every side stream joins it, so nothing is queued on those buffers either way
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
     { std::lock_guard<std::mutex> graph_lock(g_graph_mutex); for (auto& g : c->graphs) (void)hipGraphExecDestroy(g.exec); }
@@ -800,15 +764,9 @@ int avt_lbs_update(avt_ctx* c, int nframes, const double* w, const double* p, co
         if (nframes <= 0 || nframes > c->fb.max_frames) { avt_set_error("avt_lbs_update: nframes out of range"); return 1; }
         AVT_HIP(hipSetDevice(c->device));
         c->frames_valid = c->state_valid = false;    // frame slots' posed clouds / skeleton scratch are overwritten
-        // stage the parameters in the (otherwise unused here) prep buffer: w | p | R
-        double* dw = c->fb.prep;
-        double* dp = dw + (size_t)nframes * d.K;
-        double* dR = dp + (size_t)nframes * 3;
-        if ((size_t)nframes * (d.K + 3 + 9 * d.J) > (size_t)c->fb.max_frames * 2 * d.prep_size) { avt_set_error("avt_lbs_update: staging overflow"); return 1; }
-        AVT_HIP(hipMemcpyAsync(dw, w, (size_t)nframes * d.K * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        AVT_HIP(hipMemcpyAsync(dp, p, (size_t)nframes * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        AVT_HIP(hipMemcpyAsync(dR, R, (size_t)nframes * 9 * d.J * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        { ProfScope ps(c, AVT_K_LBS); launch_lbs(c, nframes, nullptr, dw, dp, dR, 0, -1); }
+        StagedPose s;
+        if (stage_pose(c, "avt_lbs_update", nframes, w, p, R, &s)) return 1;
+        { ProfScope ps(c, AVT_K_LBS); launch_lbs(c, nframes, nullptr, s.w, s.p, s.R, 0, -1); }
         if (check_launch("k_lbs")) return 1;
         if (cloud) AVT_HIP(hipMemcpyAsync(cloud, c->fb.cloud, (size_t)nframes * 3 * d.V * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         if (joint_pos) AVT_HIP(hipMemcpyAsync(joint_pos, c->fb.jointpos, (size_t)nframes * 3 * d.J * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -880,13 +838,9 @@ int avt_synth_render_frames_mode(avt_ctx* c, int nframes, const double* w, const
         if (nframes <= 0 || nframes > c->fb.max_frames) { avt_set_error("avt_synth_render_frames: nframes out of range"); return 1; }
         AVT_HIP(hipSetDevice(c->device));
         // pose the ground-truth avatars (Avatar::update) for all frames
-        double* dw = c->fb.prep;
-        double* dp = dw + (size_t)nframes * d.K;
-        double* dR = dp + (size_t)nframes * 3;
-        AVT_HIP(hipMemcpyAsync(dw, w, (size_t)nframes * d.K * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        AVT_HIP(hipMemcpyAsync(dp, p, (size_t)nframes * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        AVT_HIP(hipMemcpyAsync(dR, R, (size_t)nframes * 9 * d.J * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        launch_lbs(c, nframes, nullptr, dw, dp, dR, 0, -1);
+        StagedPose s;
+        if (stage_pose(c, "avt_synth_render_frames", nframes, w, p, R, &s)) return 1;
+        launch_lbs(c, nframes, nullptr, s.w, s.p, s.R, 0, -1);
         // rasterise in chunks of frames (8 bytes of z-buffer key per pixel)
         const size_t npix = (size_t)width * height;
         const int chunk = std::max(1, std::min(nframes, (int)((256ull << 20) / (npix * (painter ? 21 : 9) + 64))));
@@ -917,21 +871,11 @@ int avt_synth_render_frames_mode(avt_ctx* c, int nframes, const double* w, const
         std::vector<AvtFrameCtl> ctl(nframes);
         AVT_HIP(hipMemcpyAsync(ctl.data(), c->fb.ctl, ctl.size() * sizeof(AvtFrameCtl), hipMemcpyDeviceToHost, c->stream));
         AVT_HIP(hipStreamSynchronize(c->stream));
-        c->frames_valid = c->state_valid = false;
-        c->have_moments = c->have_records = false;
-        c->results_fresh = false;
-        c->nframes = nframes;
-        c->frame_N.assign(nframes, 0);
-        c->frame_off.assign(nframes + 1, 0);
-        int mx = 0;
-        for (int f = 0; f < nframes; ++f) {
+        c->frames_valid = c->state_valid = false;      // the rendered frames replace what was resident; they have no start state
+        for (int f = 0; f < nframes; ++f)
             if (ctl[f].T > c->fb.max_points) { avt_set_error("avt_synth_render_frames: a rendered frame has more points than max_points_per_frame"); return 1; }
-            c->frame_N[f] = ctl[f].N;
-            c->frame_off[f + 1] = c->frame_off[f] + ctl[f].N;
-            mx = std::max(mx, ctl[f].N);
-            if (points_per_frame) points_per_frame[f] = ctl[f].N;
-        }
-        c->launch_maxN = std::max(mx, std::min(c->fb.max_points, ((mx + 2047) / 2048) * 2048));
+        if (set_resident_frames(c, nframes, [&](int f) { return ctl[f].N; })) return 1;
+        if (points_per_frame) std::copy(c->frame_N.begin(), c->frame_N.end(), points_per_frame);
         // the render kernels wrote N into the working control blocks; the start copies follow (avt_state_reset)
         AVT_HIP(hipMemcpy2DAsync(&c->fb.ctl_start->N, sizeof(AvtFrameCtl), c->frame_N.data(), sizeof(int), sizeof(int), (size_t)nframes, hipMemcpyHostToDevice, c->stream));
         AVT_HIP(hipStreamSynchronize(c->stream));
@@ -1009,11 +953,7 @@ int avt_optimize_resident_budgets(avt_ctx* c, const avt_options* opt, const int*
                 avt_set_error(msg);
                 return 1;
             }
-        if (!c->budget_hold && dev_alloc(c, &c->budget_hold, (size_t)c->fb.max_frames * avt_budget_hold_doubles(c->dm.d))) return 1;
-        if (!c->budget) {
-            if (dev_alloc(c, &c->budget, (size_t)c->fb.max_frames)) return 1;
-            c->budget_host.clear();
-        }
+        if (c->budget_hold.reserve((size_t)c->fb.max_frames * avt_budget_hold_doubles(c->dm.d)) || c->budget.reserve((size_t)c->fb.max_frames)) return 1;
         if (c->budget_host.size() < (size_t)nf || !std::equal(icp_budget, icp_budget + nf, c->budget_host.begin())) {
             for (int f0 = 0; f0 < nf; f0 += AVT_BUDGET_CHUNK) {
                 AvtBudgetChunk a;
@@ -1048,9 +988,7 @@ int avt_state_upload_frames(avt_ctx* c, int count, const int* frames, const doub
             AvtStateInstall a;
             a.frame = frames[i];
             a.N = c->frame_N[frames[i]];
-            std::copy(p + 3 * i, p + 3 * i + 3, a.x);
-            std::copy(q + (size_t)4 * d.J * i, q + (size_t)4 * d.J * (i + 1), a.x + 3);
-            std::copy(w + (size_t)d.K * i, w + (size_t)d.K * (i + 1), a.x + 3 + 4 * d.J);
+            pack_state_row(d, a.x, p, q, w, i);
             launch_state_install(c, a);
         }
         c->results_fresh = false;

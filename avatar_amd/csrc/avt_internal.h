@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/avt.h"
+#include "../../include/avt_shard.h"
 #include "avt_host.h"
 
 #define AVT_ANC_MAX 16        // max deduplicated ancestors per skin point (SMPL needs <= 12)
@@ -27,7 +28,7 @@
 #define AVT_FIX_SCALE 1099511627776.0  // 2^40 fixed-point scale of the centred correspondence sums
 
 // ---- per-frame state block (doubles), double-buffered: slot 0/1 --------------------------------
-// x = (p[3], q[4J], w[K])
+// x = (p[3], q[4J], w[K]): pack_state_row / unpack_state_row below
 struct AvtDims {
     int V, J, K, F, P;       // P = 3 + 3J + K
     int NT;                  // column tiles of the augmented matrix [J | r]: ceil((P+1)/16)
@@ -80,10 +81,40 @@ __host__ __device__ inline int prep_off_w(const AvtDims& d) { return 19 * d.J + 
 __host__ __device__ inline int prep_off_off(const AvtDims& d) { return 19 * d.J + 3 * d.J * d.K + d.K; }
 __host__ __device__ inline int prep_total(const AvtDims& d) { return ((19 * d.J + 3 * d.J * d.K + d.K + 3) + 7) & ~7; }
 
+// a state row x on the host <-> row f of the ABI's per-frame arrays p[3], q[4J], w[K] (unpacking skips a null array)
+inline void pack_state_row(const AvtDims& d, double* x, const double* p, const double* q, const double* w, size_t f) {
+    std::copy(p + 3 * f, p + 3 * (f + 1), x);
+    std::copy(q + 4 * d.J * f, q + 4 * d.J * (f + 1), x + 3);
+    std::copy(w + d.K * f, w + d.K * (f + 1), x + 3 + 4 * d.J);
+}
+inline void unpack_state_row(const AvtDims& d, const double* x, double* p, double* q, double* w, size_t f) {
+    if (p) std::copy(x, x + 3, p + 3 * f);
+    if (q) std::copy(x + 3, x + 3 + 4 * d.J, q + 4 * d.J * f);
+    if (w) std::copy(x + 3 + 4 * d.J, x + d.xsize, w + d.K * f);
+}
+
+// Result record of a frame (FrameBuffers::results; written on the device by pack_result_row, avt_kernels.hip): the current state x,
+// then AVT_RESULT_TAIL doubles - the seven fields of avt_stats in their order and, at AVT_RESULT_FAULT, the frame's fault word.
+// It is also what the batch split gathers per frame (include/avt_shard.h).
+enum { AVT_RESULT_FAULT = 7, AVT_RESULT_TAIL = 8 };
+static_assert(AVT_RESULT_TAIL == AVT_SHARD_STAT_DOUBLES, "the result record is the row avt_shard_gather_results documents");
+__host__ __device__ inline int result_stride(const AvtDims& d) { return d.xsize + AVT_RESULT_TAIL; }
+// one record into row f of p / q / w / st (null: skipped); returns the fault bits (0: the result is valid)
+inline unsigned unpack_result_row(const AvtDims& d, const double* rec, double* p, double* q, double* w, avt_stats* st, size_t f) {
+    unpack_state_row(d, rec, p, q, w, f);
+    const double* t = rec + d.xsize;
+    if (st) {
+        st[f].initial_cost = t[0]; st[f].final_cost = t[1]; st[f].lambda = t[2];
+        st[f].num_correspondences = (int)t[3]; st[f].matched_model_points = (int)t[4];
+        st[f].gn_iterations = (int)t[5]; st[f].accepted_steps = (int)t[6];
+    }
+    return (unsigned)t[AVT_RESULT_FAULT];
+}
+
 // LDS scratch of k_solve's skeleton pass (avt_lm.hip): offsets in doubles; the host-built work items (DeviceModel::
 // fk_items) address it with 14-bit offsets
 struct PrepLayout {
-    int rot, Rw, o, jp, dv, H, Sp, S, jsr, jsrb, ident, zero, w, x0;
+    int rot, Rw, o, jp, dv, H, Sp, S, jsr, jsrb, ident, zero, w;
     int ndoubles;   // even
     int nitems;     // J*(12+3K)
 };
@@ -103,7 +134,6 @@ __host__ __device__ inline PrepLayout prep_layout(int J, int K, int xsize) {
     L.ident = o; o += 9;
     L.zero = o; o += 3;
     L.w = o; o += K;
-    L.x0 = o;                 // (unused since round 2: both state slots are staged in their own LDS area)
     L.ndoubles = (o + 1) & ~1;
     L.nitems = J * (12 + 3 * K);
     return L;
@@ -301,7 +331,7 @@ struct FrameBuffers {
     double* jointpos;     // [max_frames][3J]
     double* jointtrans;   // [max_frames][12J]
     double* trace;        // [max_frames][64] cost trace (debug)
-    double* results;      // [max_frames][xsize + 8] the result record of every frame - current state (p, q, w), seven statistics, the fault word (k_pack_results' layout) -
+    double* results;      // [max_frames][result_stride] the result record of every frame - current state (p, q, w), seven statistics, the fault word (above) -
                           // written by workgroup 0 of the k_lbs launch that closes optimize(): what the batch split gathers and the host-pointer calls copy back
     const AvtRunParams* params;   // one block per context
     // moment form of the data term (avt_moments.hip): accumulated once per ICP iteration by k_moments
@@ -328,54 +358,55 @@ struct avt_model {
 };
 
 struct avt_ctx {
-    int device;
-    hipStream_t stream;
-    hipStream_t side[AVT_MAX_GROUPS - 1];   // branches of the frame-group pipeline (large batches)
-    hipEvent_t ev_fork, ev_join[AVT_MAX_GROUPS - 1];
-    hipStream_t cur_stream;          // stream the launch wrappers enqueue on
-    const avt_model* model;
-    DeviceModel dm;
-    FrameBuffers fb;
+    // every member starts null / zero / false unless it says otherwise: avt_ctx_destroy copes with a partially built context
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipStream_t side[AVT_MAX_GROUPS - 1] = {};   // branches of the frame-group pipeline (large batches)
+    hipEvent_t ev_fork = nullptr, ev_join[AVT_MAX_GROUPS - 1] = {};
+    hipStream_t cur_stream = nullptr;   // stream the launch wrappers enqueue on
+    const avt_model* model = nullptr;
+    DeviceModel dm = {};
+    FrameBuffers fb = {};
+    std::vector<DevBuf<char>> owned;    // the allocations behind the pointers of dm and fb (dev_alloc, avt_capi.cpp): freed with the context
     std::vector<int> part_map;
-    int nframes;                     // frames currently resident
+    int nframes = 0;                    // frames currently resident
     std::vector<int> frame_N, frame_off;
-    bool profiling;
-    unsigned prof_mask;
+    bool profiling = false;
+    unsigned prof_mask = 0xffffffffu;
     std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> prof_events;
     std::vector<hipEvent_t> event_pool;
-    size_t event_pool_used;
-    std::vector<void*> allocs;
-    int ran_icp_iters, ran_max_iters;
-    int launch_maxN;                 // max points per frame of the resident batch, rounded up to 2048 (grid sizing)
-    int num_cus;                     // compute units of the device (hipDeviceProp_t::multiProcessorCount)
-    bool lbs_cleared;                // the preceding k_lbs reset visibility / correspondence bookkeeping
-    bool nn_from_cloud;              // inside optimize(), frame batches: k_compact gathers the candidates from the cloud (no pcx/pcy/pcz)
-    bool scatter_in_compact;         // launch_visibility left the scatter pass of the bucketing to the k_compact launch that follows
-    int vis_frame_min;               // frames per launch from which visibility runs as one workgroup per frame (0: never; tun.vis_frame_min where the LDS allows)
+    size_t event_pool_used = 0;
+    int ran_icp_iters = 0, ran_max_iters = 0;
+    int launch_maxN = 0;                // max points per frame of the resident batch, rounded up to 2048 (grid sizing)
+    int num_cus = 0;                    // compute units of the device (hipDeviceProp_t::multiProcessorCount)
+    bool lbs_cleared = false;           // the preceding k_lbs reset visibility / correspondence bookkeeping
+    bool nn_from_cloud = false;         // inside optimize(), frame batches: k_compact gathers the candidates from the cloud (no pcx/pcy/pcz)
+    bool scatter_in_compact = false;    // launch_visibility left the scatter pass of the bucketing to the k_compact launch that follows
+    int vis_frame_min = 0;              // frames per launch from which visibility runs as one workgroup per frame (0: never; tun.vis_frame_min where the LDS allows)
     struct GraphEntry { std::string key; hipGraphExec_t exec; unsigned long long last_used; };
-    std::vector<GraphEntry> graphs;  // small LRU cache keyed on the launch SHAPE only (frames, groups, grids, iteration counts)
-    unsigned long long graph_clock;
-    AvtRunParams params_host;        // what fb.params currently holds
-    bool params_valid;
-    bool frames_valid, state_valid;  // resident frames / start state usable by avt_optimize_resident
-    int data_term;                   // AVT_DATA_TERM_* policy (avt_set_data_term)
-    avt_tuning tun;                  // launch-shape / algorithm knobs (include/avt.h): defaults, then the environment ONCE at creation, then avt_ctx_set_tuning
-    bool last_run_moments;           // the form the last optimize() ran
-    std::string mom_reason;          // why this context has no moment form (empty: it has one)
-    bool have_moments, have_records; // what exists for the resident correspondences (avt_get_normal_equations makes the other on demand)
-    int concurrent_groups;           // frame groups the current optimize() call runs side by side (sizes the riding launch shapes)
+    std::vector<GraphEntry> graphs;     // small LRU cache keyed on the launch SHAPE only (frames, groups, grids, iteration counts)
+    unsigned long long graph_clock = 0;
+    AvtRunParams params_host = {};      // what fb.params currently holds
+    bool params_valid = false;
+    bool frames_valid = false, state_valid = false;   // resident frames / start state usable by avt_optimize_resident
+    int data_term = AVT_DATA_TERM_AUTO; // AVT_DATA_TERM_* policy (avt_set_data_term)
+    avt_tuning tun = {};                // launch-shape / algorithm knobs (include/avt.h): defaults, then the environment ONCE at creation, then avt_ctx_set_tuning
+    bool last_run_moments = false;      // the form the last optimize() ran
+    std::string mom_reason;             // why this context has no moment form (empty: it has one)
+    bool have_moments = false, have_records = false;   // what exists for the resident correspondences (avt_get_normal_equations makes the other on demand)
+    int concurrent_groups = 1;          // frame groups the current optimize() call runs side by side (sizes the riding launch shapes)
     // host-to-host calls (avt_optimize / avt_optimize_batch on host pointers): one pinned staging block for everything that crosses PCIe
     // in either direction and one device block for the packed results, grown on demand - the call then needs ONE host synchronisation
-    char* host_pin; size_t host_pin_cap;
-    bool results_fresh;              // fb.results describes the resident states (the last optimize() packed them and nothing changed them since)
+    char* host_pin = nullptr; size_t host_pin_cap = 0;
+    bool results_fresh = false;         // fb.results describes the resident states (the last optimize() packed them and nothing changed them since)
     // persistent scratch of avt_synth_render_frames (z-buffer keys, labels, block counts), grown on demand
     DevBuf<unsigned long long> render_zkey; DevBuf<unsigned char> render_label; DevBuf<int> render_block;
     // painter's-order mode only: second key image, float depth image, per-face sort key / order position / edge-on flag
     DevBuf<unsigned long long> render_mkey; DevBuf<float> render_depth, render_fkey; DevBuf<int> render_frank; DevBuf<unsigned char> render_fedge;
-    int render_img_frames, render_img_w, render_img_h;   // what render_depth / render_label hold (avt_synth_render_images); 0 = nothing
+    int render_img_frames = 0, render_img_w = 0, render_img_h = 0;   // what render_depth / render_label hold (avt_synth_render_images); 0 = nothing
     // avt_optimize_resident_budgets, allocated on its first call: the budget word of every frame, one hold block per frame
     // (avt_budget_hold_doubles), and what budget[] was last set to (a repeated pattern is not uploaded again)
-    int* budget; double* budget_hold;
+    DevBuf<int> budget; DevBuf<double> budget_hold;
     std::vector<int> budget_host;
 };
 
@@ -402,7 +433,9 @@ void launch_records(avt_ctx* c, int nframes);
 void launch_reduce(avt_ctx* c, int nframes);
 bool avt_solve_rides(const avt_ctx* c, int nframes);      // the reduction rides in k_solve's launch: no launch_reduce in front of launch_solve
 void launch_solve(avt_ctx* c, int nframes, int mode, int seq = 0 /* which solve of the ICP iteration (riding shape) */);
-void launch_pack_results(avt_ctx* c, int nframes, double* out, int stride);
+void launch_pack_results(avt_ctx* c, int nframes);               // the result records of the resident frames, when no closing k_lbs launch wrote them
+// a device fault that has been reported is cleared and the result records, which still carry its word, are stale (avt_capi.cpp)
+int avt_internal_clear_faults(avt_ctx* c);
 // per-frame ICP budgets (avt_optimize_resident_budgets) and per-frame state installs (avt_state_upload_frames)
 #define AVT_BUDGET_CHUNK 248
 struct AvtBudgetChunk { int f0, n; int b[AVT_BUDGET_CHUNK]; };        // a kernel argument (1 KB)

@@ -16,17 +16,17 @@ __global__ __launch_bounds__(256) void k_bucket_scatter(DeviceModel dm, FrameBuf
 // the per-vertex loads are SoA and fully coalesced: 3(K+1) shape planes + 4 (weight, joint) pairs in,
 // 3 doubles out => ~336 B/vertex algorithmic traffic.
 // =================================================================================================
-// Result record of a frame (include/avt_shard.h: the current state x = (p, q, w), AVT_SHARD_STAT_DOUBLES statistics): written by the calling workgroup
+// Result record of a frame (avt_internal.h: the current state x = (p, q, w), AVT_RESULT_TAIL statistics): written by the calling workgroup
 __device__ __forceinline__ void pack_result_row(const FrameBuffers& fb, int f, int xsize, int t, int nth) {
     const AvtFrameCtl& ctl = fb.ctl[f];
     const double* x = fb.x + ((size_t)f * 2 + ctl.cur_slot) * xsize;
-    double* o = fb.results + (size_t)f * (xsize + 8);
+    double* o = fb.results + (size_t)f * (xsize + AVT_RESULT_TAIL);
     for (int e = t; e < xsize; e += nth) o[e] = x[e];
     if (t == 0) {
         double* s = o + xsize;
         s[0] = ctl.cost_initial; s[1] = ctl.cost_cur; s[2] = ctl.lambda; s[3] = (double)ctl.T; s[4] = (double)ctl.M;
         s[5] = (double)ctl.gn_iterations; s[6] = (double)ctl.accepted;
-        s[7] = (double)fb.fault[f];      // sticky device fault bits of the frame (0 = its result is valid)
+        s[AVT_RESULT_FAULT] = (double)fb.fault[f];      // sticky device fault bits of the frame (0 = its result is valid)
     }
 }
 
@@ -676,19 +676,11 @@ void launch_finalize(avt_ctx* c, int nframes) {
 }
 
 // =================================================================================================
-// Result record of every resident frame for the batch split's all-gather (include/avt_shard.h): the current state
-// x = (p, q, w) followed by AVT_SHARD_STAT_DOUBLES statistics, `stride` doubles per frame.  grid (nframes), block 128.
+// Result record of every resident frame (pack_result_row), for results asked for without an optimize() in front: the closing k_lbs
+// launch of optimize() writes the same rows itself.  grid (nframes), block 128.
 // =================================================================================================
-__global__ __launch_bounds__(128) void k_pack_results(FrameBuffers fb, double* __restrict__ out, int xsize, int stride) {
-    // (out == fb.results, stride == xsize + 8: the one layout there is; the closing k_lbs launch of optimize() writes the same rows itself - this kernel
-    // remains for results asked for without an optimize() in front, and for a send block that is not fb.results)
-    const int f = blockIdx.x, t = threadIdx.x;
-    (void)stride;
-    FrameBuffers fo = fb;
-    fo.results = out;
-    pack_result_row(fo, f, xsize, t, 128);
-}
+__global__ __launch_bounds__(128) void k_pack_results(FrameBuffers fb, int xsize) { pack_result_row(fb, blockIdx.x, xsize, threadIdx.x, 128); }
 
-void launch_pack_results(avt_ctx* c, int nframes, double* out, int stride) {
-    hipLaunchKernelGGL(k_pack_results, dim3(nframes), dim3(128), 0, c->stream, c->fb, out, c->dm.d.xsize, stride);
+void launch_pack_results(avt_ctx* c, int nframes) {
+    hipLaunchKernelGGL(k_pack_results, dim3(nframes), dim3(128), 0, c->stream, c->fb, c->dm.d.xsize);
 }

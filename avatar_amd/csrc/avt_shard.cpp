@@ -31,7 +31,6 @@
 #include "avt_internal.h"
 
 int avt_internal_install_frames(avt_ctx* c, int nframes, const int* counts, const double* data, const int* labels, int device_src);
-void launch_pack_results(avt_ctx* c, int nframes, double* out, int stride);
 
 // ---------------------------------------------------------------------------------------------------------------------
 // partition
@@ -580,8 +579,6 @@ namespace {
 // calls (64, 8 (world + 1) .. bytes) share one allocation
 int grow(DevBuf<char>& b, size_t bytes) { return b.reserve(std::max<size_t>(bytes, 256)); }
 
-int gather_stride(const avt_ctx* c) { return c->dm.d.xsize + AVT_SHARD_STAT_DOUBLES; }
-
 }  // namespace
 
 extern "C" int avt_shard_unique_id(char id[AVT_SHARD_ID_BYTES]) {
@@ -813,10 +810,7 @@ extern "C" int avt_shard_scatter_frames(avt_shard* s, avt_ctx* c, int root, int 
                 const int n = offs[f + 1] - offs[f];
                 if (n < 0) { my_error = "avt_shard_scatter_frames: frame_offsets not monotone"; break; }
                 tab[f] = (double)n;
-                double* x = &tab[(size_t)B + (size_t)f * xs];
-                std::copy(p + 3 * (size_t)f, p + 3 * (size_t)f + 3, x);
-                std::copy(q + (size_t)4 * J * f, q + (size_t)4 * J * (f + 1), x + 3);
-                std::copy(w + (size_t)K * f, w + (size_t)K * (f + 1), x + 3 + 4 * J);
+                pack_state_row(d, &tab[(size_t)B + (size_t)f * xs], p, q, w, f);
             }
             if (!my_error.empty()) tab[0] = -1.0;          // a point count cannot be negative: "the root's batch is unusable"
         }
@@ -911,10 +905,7 @@ extern "C" int avt_shard_scatter_frames(avt_shard* s, avt_ctx* c, int root, int 
         for (int i = 0; i < nloc; ++i) {
             const int f = avt_shard_global_frame(i, s->rank, W);
             lcnt[i] = cnt[f];
-            const double* x = &tab[(size_t)B + (size_t)f * xs];
-            std::copy(x, x + 3, &lp[(size_t)i * 3]);
-            std::copy(x + 3, x + 3 + 4 * J, &lq[(size_t)i * 4 * J]);
-            std::copy(x + 3 + 4 * J, x + xs, &lw[(size_t)i * K]);
+            unpack_state_row(d, &tab[(size_t)B + (size_t)f * xs], lp.data(), lq.data(), lw.data(), i);
         }
         if (nloc == 0) {       // a rank without frames (B < W): nothing resident, and a later gather must see exactly that
             c->nframes = 0; c->frames_valid = c->state_valid = false;
@@ -931,7 +922,7 @@ extern "C" int avt_shard_scatter_frames(avt_shard* s, avt_ctx* c, int root, int 
 extern "C" int avt_shard_gather_enqueue(avt_shard* s, avt_ctx* c, int B) {
     return avt_guard("avt_shard_gather_enqueue", [&]() -> int {
         if (!s || !c || B <= 0) { avt_set_error("avt_shard_gather_enqueue: bad argument"); return 1; }
-        const int W = s->world, per = (B + W - 1) / W, stride = gather_stride(c);
+        const int W = s->world, per = (B + W - 1) / W, stride = result_stride(c->dm.d);
         const int nloc = avt_shard_local_count(B, s->rank, W);
         // (a rank whose context does not hold its share still takes part in the all-gather - its peers are on their way into it - with
         // its rows marked faulty, and reports the error afterwards; every rank's download then fails on those rows)
@@ -952,11 +943,11 @@ extern "C" int avt_shard_gather_enqueue(avt_shard* s, avt_ctx* c, int B) {
         const bool direct = W == 1 && !mismatch && !s->self_exchange;
         if (mismatch) {
             std::vector<double> rows(blk, 0.0);
-            for (int i = 0; i < per; ++i) rows[(size_t)i * stride + c->dm.d.xsize + 7] = (double)AVT_FAULT_NOT_RESIDENT;
+            for (int i = 0; i < per; ++i) rows[(size_t)i * stride + c->dm.d.xsize + AVT_RESULT_FAULT] = (double)AVT_FAULT_NOT_RESIDENT;
             AVT_HIP(hipMemcpyAsync(s->d_send, rows.data(), blk * 8, hipMemcpyHostToDevice, c->stream));
             AVT_HIP(hipStreamSynchronize(c->stream));
         } else if (nloc && !c->results_fresh) {      // (no optimize() in front: the records are made now)
-            launch_pack_results(c, nloc, c->fb.results, stride);
+            launch_pack_results(c, nloc);
             c->results_fresh = true;
         }
         // The result records (p, q, w, statistics, fault word per resident frame) are written by the k_lbs launch that closes optimize()
@@ -992,7 +983,7 @@ extern "C" int avt_shard_gather_download(avt_shard* s, avt_ctx* c, int B, double
     return avt_guard("avt_shard_gather_download", [&]() -> int {
         if (!s || !c || B <= 0) { avt_set_error("avt_shard_gather_download: bad argument"); return 1; }
         const AvtDims& d = c->dm.d;
-        const int W = s->world, per = (B + W - 1) / W, stride = gather_stride(c), xs = d.xsize, J = d.J, K = d.K;
+        const int W = s->world, per = (B + W - 1) / W, stride = result_stride(d);
         const size_t blk = (size_t)per * stride;
         if (s->d_recv.cap < blk * W || !s->gathered) { avt_set_error("avt_shard_gather_download: nothing was gathered"); return 1; }
         AVT_HIP(hipSetDevice(s->device));
@@ -1000,22 +991,10 @@ extern "C" int avt_shard_gather_download(avt_shard* s, avt_ctx* c, int B, double
         AVT_HIP(hipMemcpyAsync(host.data(), s->gathered, host.size() * 8, hipMemcpyDeviceToHost, c->stream));   // behind the all-gather
         AVT_HIP(hipStreamSynchronize(c->stream));
         int bad = -1;
-        for (int f = 0; f < B; ++f) {
-            const double* x = &host[(size_t)(f % W) * blk + (size_t)(f / W) * stride];
-            if (x[xs + 7] != 0.0 && bad < 0) bad = f;       // the owning rank's device fault bits travelled with the result (k_pack_results)
-            if (p) std::copy(x, x + 3, p + 3 * (size_t)f);
-            if (q) std::copy(x + 3, x + 3 + 4 * J, q + (size_t)4 * J * f);
-            if (w) std::copy(x + 3 + 4 * J, x + xs, w + (size_t)K * f);
-            if (stats) {
-                const double* t = x + xs;
-                stats[f].initial_cost = t[0]; stats[f].final_cost = t[1]; stats[f].lambda = t[2];
-                stats[f].num_correspondences = (int)t[3]; stats[f].matched_model_points = (int)t[4];
-                stats[f].gn_iterations = (int)t[5]; stats[f].accepted_steps = (int)t[6];
-            }
-        }
+        for (int f = 0; f < B; ++f)       // the owning rank's device fault bits travelled with the result
+            if (unpack_result_row(d, &host[(size_t)(f % W) * blk + (size_t)(f / W) * stride], p, q, w, stats, f) && bad < 0) bad = f;
         if (bad >= 0) {
-            (void)hipMemsetAsync(c->fb.fault, 0, (size_t)c->fb.max_frames * sizeof(unsigned), c->stream);   // reported once
-            c->results_fresh = false;      //  the result records still carry the word that was just cleared: the next gather packs them again
+            (void)avt_internal_clear_faults(c);      // reported once
             avt_set_error("avt_shard_gather_download: frame " + std::to_string(bad) + " carries a device fault (rank " + std::to_string(bad % W) + "); its result is not valid");
             return AVT_STATUS_DEVICE_FAULT;
         }

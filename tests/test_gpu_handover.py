@@ -56,6 +56,35 @@ def test_a_solver_that_gives_up_waiting_is_an_error_not_a_different_fit(smpl, gm
     assert np.array_equal(_run(ctx, api, frames, opt), _run(ctx, api, frames, opt))
 
 
+def test_the_staged_calls_report_the_fault_the_host_pointer_call_reports(smpl, gmodel):
+    """The same ride_timeout_us = 0 through avt_frames_upload / avt_state_upload / avt_optimize_resident: avt_state_download is then the
+    call that hands out the result.  It fails with status 3, or returns the bits the host-pointer call returns undisturbed; and the fault
+    is reported once - the download repeated behind a failed one finds the fault words cleared."""
+    from avatar_amd import api
+    pm = synth.identity_part_map()
+    opt = Options.demo(icp_iters=2)
+    faults = 0
+    for F in (1, 2, 3):
+        frames = [synth.make_frame(smpl, s) for s in SEEDS[F]]
+        good = _run(_ctx(api, gmodel, pm, F), api, frames, opt)
+        ctx = _ctx(api, gmodel, pm, F).set_tuning(ride_timeout_us=0)
+        ctx.frames_upload([f["data"] for f in frames], [f["labels"] for f in frames])
+        for _ in range(4):
+            ctx.state_upload(np.array([f["start"][1] for f in frames]), np.array([api.rot_to_quat(f["start"][2]) for f in frames]),
+                             np.array([f["start"][0] for f in frames]))
+            ctx.optimize_resident(opt)
+            try:
+                p, q, w, st = ctx.state_download()
+            except api.AvtError as e:
+                assert e.status == 3 and "fault" in str(e)
+                faults += 1
+                ctx.state_download()
+                continue
+            out = np.concatenate([p.ravel(), q.ravel(), w.ravel(), np.array([x.final_cost for x in st]), np.array([x.accepted_steps for x in st], float)])
+            assert np.array_equal(out, good)
+    assert faults > 0, "the timeout path was never taken: the test does not exercise it"
+
+
 def test_few_frame_shapes_under_compute_pressure_from_another_stream(smpl, gmodel):
     """The one-, two- and three-frame shapes while another stream keeps the whole chip busy (large fp32 matrix products queued
     through torch on a side stream: every CU holds their workgroups, the riding launch's workgroups get CUs as they come free).
