@@ -440,6 +440,16 @@ class Context:
         check(self._lib.avt_debug_mfma_count(self.h, C.c_int(frame), C.byref(a), C.byref(b), C.byref(c)))
         return {k: (None if v.value < 0 else int(v.value)) for k, v in (("eval_rows", a), ("moments", b), ("solve", c))}
 
+    def nn_sums(self, frame=0):
+        """The bookkeeping the nearest-neighbour kernels left for `frame` (avt_debug_nn_sums): cnt int32 (V,) matches per model vertex,
+        fsum int64 (3, V) sums of rint((data - centre) * 2**40) over every vertex's matched data points, centre float64 (3,) the frame's
+        first data point.  Valid after nn() (frame 0) and after an optimize call with at least one ICP iteration - the closing launch of
+        optimize() resets no bookkeeping, so the arrays are those of the last ICP iteration; refused otherwise."""
+        V = self.model.numPoints()
+        cnt = np.empty(V, np.int32); fsum = np.empty((3, V), np.int64); centre = np.empty(3)
+        check(self._lib.avt_debug_nn_sums(self.h, C.c_int(frame), iptr(cnt), fsum.ctypes.data_as(C.POINTER(C.c_longlong)), dptr(centre)))
+        return cnt, fsum, centre
+
     DATA_TERM_ROWS, DATA_TERM_MOMENTS, DATA_TERM_AUTO = 0, 1, 2
 
     def tuning(self):

@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include <memory>
 #include <mutex>
 
 #include "avt_internal.h"
@@ -91,11 +92,11 @@ avt_tuning tuning_from_environment() {
     avt_tuning t;
     std::memset(&t, 0, sizeof t);
     t.use_graph = 1; t.groups = 0; t.g = 0; t.gcap = 128; t.vis_frame_min = 32; t.ride = 1; t.ride_strips = 0; t.ride_sizing_groups = 0;
-    t.asm_parts = 1; t.spec_cost = 1; t.xcd_frames = 1; t.literal_dims = 1; t.nspec = AVT_MAX_SPEC; t.nn_force_part = 0; t.nn_slab = 1; t.mom_min_frames = 8; t.debug = 0; t.ride_timeout_us = 2000000;
+    t.asm_parts = 1; t.spec_cost = 1; t.xcd_frames = 1; t.literal_dims = 1; t.nspec = AVT_MAX_SPEC; t.nn_force_part = 0; t.nn_force_vis = 0; t.nn_slab = 1; t.mom_min_frames = 8; t.debug = 0; t.ride_timeout_us = 2000000;
     struct Knob { const char* name; int* field; };
     const Knob knobs[] = {{"AVT_USE_GRAPH", &t.use_graph}, {"AVT_GROUPS", &t.groups}, {"AVT_G", &t.g}, {"AVT_GCAP", &t.gcap}, {"AVT_VIS_FRAME_MIN", &t.vis_frame_min},
                           {"AVT_RIDE", &t.ride}, {"AVT_RIDE_STRIPS", &t.ride_strips}, {"AVT_RIDE_SIZING_GROUPS", &t.ride_sizing_groups}, {"AVT_NSPEC", &t.nspec},
-                          {"AVT_NN_FORCE_PART", &t.nn_force_part}, {"AVT_NN_SLAB", &t.nn_slab}, {"AVT_MOM_MIN_FRAMES", &t.mom_min_frames}, {"AVT_ASM_PARTS", &t.asm_parts}, {"AVT_LBS_FRAMES", &t.lbs_frames}, {"AVT_SPEC_COST", &t.spec_cost}, {"AVT_XCD_FRAMES", &t.xcd_frames}, {"AVT_LITERAL_DIMS", &t.literal_dims}, {"AVT_DEBUG", &t.debug}};
+                          {"AVT_NN_FORCE_PART", &t.nn_force_part}, {"AVT_NN_FORCE_VIS", &t.nn_force_vis}, {"AVT_NN_SLAB", &t.nn_slab}, {"AVT_MOM_MIN_FRAMES", &t.mom_min_frames}, {"AVT_ASM_PARTS", &t.asm_parts}, {"AVT_LBS_FRAMES", &t.lbs_frames}, {"AVT_SPEC_COST", &t.spec_cost}, {"AVT_XCD_FRAMES", &t.xcd_frames}, {"AVT_LITERAL_DIMS", &t.literal_dims}, {"AVT_DEBUG", &t.debug}};
     // names other parts of the repository own (the batch split, the Python loader, bench.py, instrumented builds)
     const char* others[] = {"AVT_LIB", "AVT_RCCL_LIB", "AVT_SHARD_LOOPBACK_TIMEOUT_S", "AVT_BENCH_SHARE_GPU0", "AVT_TIMING"};
     for (char** e = environ; e && *e; ++e) {
@@ -121,7 +122,7 @@ avt_tuning tuning_from_environment() {
 
 int validate_tuning(const avt_tuning& t) {
     if (t.groups < 0 || t.groups > AVT_MAX_GROUPS || t.g < 0 || t.gcap < 2 || t.vis_frame_min < 0 || t.nspec < 0 || t.nspec > AVT_MAX_SPEC ||
-        (t.ride_strips != 0 && t.ride_strips != 4 && t.ride_strips != 8) || t.mom_min_frames < 1 || t.ride_timeout_us < 0 || (t.lbs_frames != 0 && t.lbs_frames != 1 && t.lbs_frames != 2 && t.lbs_frames != 4) || t.spec_cost < 0 || t.spec_cost > 1 || t.xcd_frames < 0 || t.xcd_frames > 1 || t.literal_dims < 0 || t.literal_dims > 1) {
+        (t.ride_strips != 0 && t.ride_strips != 4 && t.ride_strips != 8) || t.mom_min_frames < 1 || t.ride_timeout_us < 0 || (t.lbs_frames != 0 && t.lbs_frames != 1 && t.lbs_frames != 2 && t.lbs_frames != 4) || t.spec_cost < 0 || t.spec_cost > 1 || t.xcd_frames < 0 || t.xcd_frames > 1 || t.literal_dims < 0 || t.literal_dims > 1 || t.nn_force_vis < 0 || t.nn_force_vis > 1) {
         avt_set_error("avt_tuning: a field is out of range (include/avt.h)");
         return 1;
     }
@@ -799,6 +800,7 @@ int avt_nn(avt_ctx* c, const double* model_cloud, const unsigned char* visible, 
         const int offs[2] = {0, N};
         if (upload_frames(c, 1, data, labels, offs)) return 1;
         c->frames_valid = c->state_valid = false;    // frame slot 0 is scratch for this call
+        c->nn_sums_frame0 = false;
         // part-sorted SoA copy of the model cloud
         std::vector<int> ppos(V);
         AVT_HIP(hipMemcpyAsync(ppos.data(), c->dm.part_pos, (size_t)V * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -809,6 +811,12 @@ int avt_nn(avt_ctx* c, const double* model_cloud, const unsigned char* visible, 
         AVT_HIP(hipMemcpyAsync(c->fb.pcy, py.data(), V * sizeof(double), hipMemcpyHostToDevice, c->stream));
         AVT_HIP(hipMemcpyAsync(c->fb.pcz, pz.data(), V * sizeof(double), hipMemcpyHostToDevice, c->stream));
         AVT_HIP(hipMemcpyAsync(c->fb.visible, visible, (size_t)V, hipMemcpyHostToDevice, c->stream));
+        std::unique_ptr<unsigned char[]> vs;
+        if (c->tun.nn_force_vis) {      // the fused shape reads the flags in part-sorted order (inside optimize(): k_lbs / k_visibility keep them)
+            vs.reset(new unsigned char[V]);
+            for (int v = 0; v < V; ++v) vs[ppos[v]] = visible[v];
+            AVT_HIP(hipMemcpyAsync(c->fb.vis_sorted, vs.get(), (size_t)V, hipMemcpyHostToDevice, c->stream));
+        }
         AvtFrameCtl ctl;
         std::memset(&ctl, 0, sizeof(ctl));
         ctl.N = N;
@@ -818,6 +826,7 @@ int avt_nn(avt_ctx* c, const double* model_cloud, const unsigned char* visible, 
         if (check_launch("k_nn")) return 1;
         AVT_HIP(hipMemcpyAsync(out, c->fb.corr, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         AVT_HIP(hipStreamSynchronize(c->stream));
+        c->nn_sums_frame0 = true;
         return 0;
     });
 }
@@ -1145,6 +1154,27 @@ int avt_debug_mfma_count(avt_ctx* c, int frame, long long* eval_rows, long long*
                 *eval_rows = n;
             }
         }
+        return 0;
+    });
+}
+
+int avt_debug_nn_sums(avt_ctx* c, int frame, int* cnt, long long* fsum, double* centre) {
+    return avt_guard("avt_debug_nn_sums", [&]() -> int {
+        if (!c || frame < 0 || frame >= c->fb.max_frames) { avt_set_error("avt_debug_nn_sums: bad argument"); return 1; }
+        // the closing launch of optimize() resets no bookkeeping (launch_lbs with vis_init = -1), so the counts and sums of the last ICP
+        // iteration are still there; a stand-alone avt_nn leaves them for frame 0
+        const bool after_nn = c->nn_sums_frame0 && !c->frames_valid && frame == 0;
+        const bool after_opt = c->frames_valid && c->ran_icp_iters > 0 && frame < c->nframes;
+        if (!after_nn && !after_opt) { avt_set_error("avt_debug_nn_sums: neither a stand-alone avt_nn (frame 0) nor an optimize call with an ICP iteration has run last"); return 1; }
+        const size_t V = c->dm.d.V;
+        AVT_HIP(hipSetDevice(c->device));
+        AVT_HIP(hipStreamSynchronize(c->stream));
+        if (cnt) AVT_HIP(hipMemcpyAsync(cnt, c->fb.cnt + (size_t)frame * V, V * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        if (fsum) AVT_HIP(hipMemcpyAsync(fsum, c->fb.fsum + (size_t)frame * 3 * V, 3 * V * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+        AvtFrameCtl ctl;
+        AVT_HIP(hipMemcpyAsync(&ctl, c->fb.ctl + frame, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
+        AVT_HIP(hipStreamSynchronize(c->stream));
+        if (centre) for (int k = 0; k < 3; ++k) centre[k] = ctl.centre[k];
         return 0;
     });
 }

@@ -389,6 +389,7 @@ struct avt_ctx {
     AvtRunParams params_host = {};      // what fb.params currently holds
     bool params_valid = false;
     bool frames_valid = false, state_valid = false;   // resident frames / start state usable by avt_optimize_resident
+    bool nn_sums_frame0 = false;        // a stand-alone avt_nn has left its counts and sums in frame slot 0 (avt_debug_nn_sums)
     int data_term = AVT_DATA_TERM_AUTO; // AVT_DATA_TERM_* policy (avt_set_data_term)
     avt_tuning tun = {};                // launch-shape / algorithm knobs (include/avt.h): defaults, then the environment ONCE at creation, then avt_ctx_set_tuning
     bool last_run_moments = false;      // the form the last optimize() ran

@@ -766,7 +766,8 @@ void launch_nn(avt_ctx* c, int nframes) {
     if (maxN <= 0) return;
     // few queries: 4 lanes per query (more workgroups, shorter scans); many: one lane per query, one part per workgroup
     const bool few = avt_nn_few(c, nframes);
-    if (few && c->lbs_cleared) {   // inside optimize() (k_lbs / k_visibility keep the part-sorted visibility flags): compaction fused into the scan
+    // (nn_force_vis: the stand-alone avt_nn uploaded the part-sorted flags itself - tests run the fused shape on inputs of their own)
+    if (few && (c->lbs_cleared || c->tun.nn_force_vis)) {   // inside optimize() (k_lbs / k_visibility keep the part-sorted visibility flags): compaction fused into the scan
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nn_vis<4>), dim3((maxN + 63) / 64, nframes), dim3(256), 0, c->cur_stream, c->dm, c->fb);
         return;
     }

@@ -272,6 +272,13 @@ int avt_debug_trace(avt_ctx* c, int frame, double* out64);
  * Any pointer may be NULL.  bench.py divides these by the measured launch times for the matrix-pipe utilisation it reports. */
 int avt_debug_mfma_count(avt_ctx* c, int frame, long long* eval_rows, long long* moments, long long* solve);
 
+/* diagnostics: the bookkeeping the nearest-neighbour kernels leave for frame `frame`: cnt[V] the matches of every model vertex,
+ * fsum[3][V] the sums of rint((data - centre) * 2^40) over a vertex's matched data points, centre[3] the frame's centring offset (its
+ * first data point).  Synchronises.  Valid after a stand-alone avt_nn (frame 0) and after an optimize call with at least one ICP
+ * iteration: the closing launch of optimize() skins only and resets nothing, so the arrays are those of the last ICP iteration.
+ * Any pointer may be NULL. */
+int avt_debug_nn_sums(avt_ctx* c, int frame, int* cnt, long long* fsum, double* centre);
+
 /* Launch-shape and algorithm knobs of a context.  The defaults are the measured optima (DESIGN.md sections 5 and 7); they exist for
  * experiments and for tests that must force a particular code path.  avt_ctx_create fills the structure from the defaults and then
  * ONCE from the environment (AVT_<FIELD NAME IN UPPER CASE>, e.g. AVT_NSPEC=0; unknown AVT_* names are reported on stderr): nothing in
@@ -303,6 +310,8 @@ typedef struct avt_tuning {
     int literal_dims;        /* 1 (default): a model with SMPL's dimensions (24 joints, 10 shape keys, a 69-dimensional pose prior) runs the copies of
                               * k_solve, k_pairpass and k_prior that are compiled for them (every count a literal: DESIGN section 5, "Round 6, second
                               * half"); 0: the run-time-dimension copies every other model runs - same results to rounding, ~25 % slower per solve */
+    int nn_force_vis;        /* 1: the stand-alone avt_nn runs the fused shape of a single-frame optimize() (k_nn_vis: the compaction inside the scan) instead of
+                              * k_compact + k_nn; nn_force_part wins if both are set */
 } avt_tuning;
 int avt_ctx_get_tuning(avt_ctx* c, avt_tuning* out);
 int avt_ctx_set_tuning(avt_ctx* c, const avt_tuning* t);
