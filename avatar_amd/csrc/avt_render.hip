@@ -7,7 +7,8 @@
 // Behavioural counterpart of AvatarRenderer::renderDepth / renderPartMask (AvatarRenderer.cpp:72-101, :174-202), the
 // projection of AvatarRenderer.cpp:11-24, CameraIntrin::to3D (Calibration.cpp:68-74, float arithmetic) and the y flip of
 // optim.cpp:116-119.  Like the host generator (synth_render.cpp) it resolves visibility with a z-buffer instead of the
-// reference's painter's algorithm; the two generators are bit-identical to each other (tests/test_gpu_render.py):
+// reference's painter's algorithm; the two generators are bit-identical to each other (tests/test_gpu_render.py,
+// tests/test_gpu_raster_edges.py):
 // this translation unit is built with -ffp-contract=off and uses the same float expressions, and depth ties go to the
 // lowest face index (64-bit atomicMin on (depth bits, face id)) exactly like the host's in-order strict '<' test.
 #include <algorithm>
@@ -47,10 +48,11 @@ __global__ __launch_bounds__(256) void k_raster(DeviceModel dm, FrameBuffers fb,
     const float denom = (by - cyy) * (ax - cxx) + (cxx - bx) * (ay - cyy);
     if (denom == 0.0f) return;
     const float inv = 1.0f / denom;
-    const int x0 = max(0, (int)floorf(fminf(ax, fminf(bx, cxx))));
-    const int x1 = min(width - 1, (int)ceilf(fmaxf(ax, fmaxf(bx, cxx))));
-    const int y0 = max(0, (int)floorf(fminf(ay, fminf(by, cyy))));
-    const int y1 = min(height - 1, (int)ceilf(fmaxf(ay, fmaxf(by, cyy))));
+    // clamped in float before the conversion, as in synth_render.cpp (a projected coordinate may lie beyond the range of int)
+    const int x0 = (int)fminf(fmaxf(floorf(fminf(ax, fminf(bx, cxx))), 0.0f), (float)width);
+    const int x1 = (int)fminf(fmaxf(ceilf(fmaxf(ax, fmaxf(bx, cxx))), -1.0f), (float)(width - 1));
+    const int y0 = (int)fminf(fmaxf(floorf(fminf(ay, fminf(by, cyy))), 0.0f), (float)height);
+    const int y1 = (int)fminf(fmaxf(ceilf(fmaxf(ay, fmaxf(by, cyy))), -1.0f), (float)(height - 1));
     const float az = (float)a[2], bz = (float)b[2], cz = (float)c[2];
     unsigned long long* zk = zkey + (size_t)(f - fb.f0) * width * height;
     for (int r = y0; r <= y1; ++r)

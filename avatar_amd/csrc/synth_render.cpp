@@ -68,10 +68,12 @@ static void rasterise(int V, int F, const double* cloud, const int* mesh, const 
         const float denom = (by - cyy) * (ax - cxx) + (cxx - bx) * (ay - cyy);
         if (denom == 0.0f) continue;
         const float inv = 1.0f / denom;
-        const int x0 = std::max(0, (int)std::floor(std::min(ax, std::min(bx, cxx))));
-        const int x1 = std::min(width - 1, (int)std::ceil(std::max(ax, std::max(bx, cxx))));
-        const int y0 = std::max(0, (int)std::floor(std::min(ay, std::min(by, cyy))));
-        const int y1 = std::min(height - 1, (int)std::ceil(std::max(ay, std::max(by, cyy))));
+        // clamped in float before the conversion (a projected coordinate may lie beyond the range of int, or be infinite):
+        // an empty box paints nothing, any other paints up to the image border
+        const int x0 = (int)std::min(std::max(std::floor(std::min(ax, std::min(bx, cxx))), 0.0f), (float)width);
+        const int x1 = (int)std::min(std::max(std::ceil(std::max(ax, std::max(bx, cxx))), -1.0f), (float)(width - 1));
+        const int y0 = (int)std::min(std::max(std::floor(std::min(ay, std::min(by, cyy))), 0.0f), (float)height);
+        const int y1 = (int)std::min(std::max(std::ceil(std::max(ay, std::max(by, cyy))), -1.0f), (float)(height - 1));
         const float az = (float)a[2], bz = (float)b[2], cz = (float)c[2];
         for (int r = y0; r <= y1; ++r) {
             for (int col = x0; col <= x1; ++col) {

@@ -521,18 +521,19 @@ def _render_lib():
     return _synth_lib
 
 
-def render_cloud(model, verts, part_map, res_scale=1):
+def render_cloud(model, verts, part_map, res_scale=1, intrin=None):
     """Depth-render the posed vertices `verts` (V,3) with the K4A intrinsics (x res_scale) and back-project
-    every foreground pixel.  Returns (data (N,3) float64, labels (N,) int32)."""
+    every foreground pixel.  Returns (data (N,3) float64, labels (N,) int32).  intrin: another camera
+    (fx, fy, cx, cy, width, height) in place of K4A_INTRIN; the output then has room for every pixel."""
     import ctypes as C
     lib = _render_lib()
     V = verts.shape[0]
     mesh = np.ascontiguousarray(model["f"], np.int32)
     vp = np.ascontiguousarray(np.asarray(part_map, np.int32)[main_joint(model)])
     cloud = np.ascontiguousarray(verts, np.float64)
-    k = K4A_INTRIN
+    k = K4A_INTRIN if intrin is None else intrin
     W, H = k["width"] * res_scale, k["height"] * res_scale
-    cap = 400000 * res_scale * res_scale
+    cap = 400000 * res_scale * res_scale if intrin is None else W * H
     xyz = np.empty((cap, 3), np.float64); lab = np.empty(cap, np.int32)
     dp = C.POINTER(C.c_double); ip = C.POINTER(C.c_int)
     n = lib.avt_synth_render_cloud(
@@ -544,15 +545,15 @@ def render_cloud(model, verts, part_map, res_scale=1):
     return xyz[:n].copy(), lab[:n].copy()
 
 
-def render_images(model, verts, part_map):
+def render_images(model, verts, part_map, intrin=None):
     """XYZ map (H,W,3) float32 (camera coordinates, y down) + part mask (H,W) uint8 (255 = background) of the posed
-    vertices, the inputs of the reference's tracker loop (demo.cpp:215-250)."""
+    vertices, the inputs of the reference's tracker loop (demo.cpp:215-250).  intrin: another camera in place of K4A_INTRIN."""
     import ctypes as C
     lib = _render_lib()
     mesh = np.ascontiguousarray(model["f"], np.int32)
     vp = np.ascontiguousarray(np.asarray(part_map, np.int32)[main_joint(model)])
     cloud = np.ascontiguousarray(verts, np.float64)
-    k = K4A_INTRIN
+    k = K4A_INTRIN if intrin is None else intrin
     W, H = k["width"], k["height"]
     xyz = np.empty((H, W, 3), np.float32); mask = np.empty((H, W), np.uint8)
     dp = C.POINTER(C.c_double); ip = C.POINTER(C.c_int)
