@@ -132,6 +132,12 @@ class BGSubtractor:
                                                 capi.ptr(depth, C.c_float), C.byref(fr)))
         return Result(mask, depth, fr)
 
+    def info(self, image) -> Result:
+        """The record of image `image` alone (box, capped, fg_count, comps): no image is copied."""
+        fr = Frame()
+        capi.check(self._lib.avt_bgsub_download(self._h, C.c_int(image), None, None, C.byref(fr)))
+        return Result(None, None, fr)
+
     def run_batch(self, images, bg_index=None, prev_boxes=None):
         """upload + run_resident + download of every image: a list of Result."""
         self.upload(images, bg_index, prev_boxes)

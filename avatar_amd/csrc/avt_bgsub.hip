@@ -26,7 +26,7 @@
 #include <vector>
 
 #include "avt_internal.h"
-#include "../../include/avt_bgsub.h"
+#include "avt_bgsub_internal.h"
 
 #define BGS_TILE 32
 #define BGS_HALO (BGS_TILE + 2)
@@ -56,6 +56,11 @@ struct avt_bgsub {
     DevBuf<BgsInfo> d_info;                // cap
     DevBuf<unsigned> d_fault;              // sticky fault word of the handle
     int n_images = 0;
+    bool ran = false;                      // a run_resident followed the last upload: d_depth and the boxes are that run's
+    // hand-over to a reader on another stream (avt_bgsub_internal.h): ev_ready is recorded on `stream` for the reader to wait
+    // on, ev_reader on the reader's stream; while reader_pending, whatever overwrites or frees the result waits for ev_reader
+    hipEvent_t ev_ready = nullptr, ev_reader = nullptr;
+    bool reader_pending = false;
 };
 
 namespace {
@@ -348,6 +353,14 @@ __global__ __launch_bounds__(256) void k_bgs_depth(const float* __restrict__ img
     if (b && (threadIdx.x & 63) == 0) atomicAdd(&in.fg_count, __popcll(b));
 }
 
+// before the stream overwrites what a reader on another stream may still read
+int wait_for_reader(avt_bgsub* bg) {
+    if (!bg->reader_pending) return 0;
+    AVT_HIP(hipStreamWaitEvent(bg->stream, bg->ev_reader, 0));
+    bg->reader_pending = false;
+    return 0;
+}
+
 int reserve(avt_bgsub* bg, int n) {
     // d_info stands for the whole group: it grows last, and it is released when anything below fails, so that a call after
     // a failure allocates again whatever is missing (and, as ever after a failure, every slot starts at cv::Point())
@@ -428,6 +441,8 @@ int upload_impl(avt_bgsub* bg, int n, const float* images, const int* bg_index, 
         if (idx[i] < 0 || idx[i] >= bg->n_bg) { avt_set_error("avt_bgsub_images_upload: background index out of range"); return 1; }
     }
     AVT_HIP(hipSetDevice(bg->device));
+    if (wait_for_reader(bg)) return 1;
+    bg->ran = false;
     if (reserve(bg, n)) return 1;
     const size_t N = (size_t)bg->rows * bg->cols;
     AVT_HIP(hipMemcpyAsync(bg->d_img, images, (size_t)n * N * 3 * sizeof(float), hipMemcpyHostToDevice, bg->stream));
@@ -442,6 +457,7 @@ int upload_impl(avt_bgsub* bg, int n, const float* images, const int* bg_index, 
 int run_resident_impl(avt_bgsub* bg, float nn_rel, float neighb_rel) {
     if (!bg || bg->n_images <= 0) { avt_set_error("avt_bgsub_run_resident: no images resident"); return 1; }
     AVT_HIP(hipSetDevice(bg->device));
+    if (wait_for_reader(bg)) return 1;
     const int rows = bg->rows, cols = bg->cols, n = bg->n_images, npix = rows * cols;
     const float nn = thresh(rows, cols, nn_rel), nb = thresh(rows, cols, neighb_rel);
     const int min_pts = std::max(npix / 1000, 100);                                   // BGSubtractor.cpp:19
@@ -460,6 +476,7 @@ int run_resident_impl(avt_bgsub* bg, float nn_rel, float neighb_rel) {
     hipLaunchKernelGGL(k_bgs_depth, g1, dim3(256), 0, bg->stream, bg->d_img, bg->d_mask, bg->d_info, bg->d_depth, npix, rows, cols);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { avt_set_error(std::string("avt_bgsub_run_resident: launch failed: ") + hipGetErrorString(e)); return 1; }
+    bg->ran = true;
     return 0;
 }
 
@@ -495,6 +512,29 @@ int run_impl(avt_bgsub* bg, int background_index, const float* xyz, float nn_rel
 
 }  // namespace
 
+// ---- avt_bgsub_internal.h
+int avt_bgsub_last_run(avt_bgsub* bg, avt_bgsub_view* out) {
+    if (!bg || !out || bg->n_images <= 0 || !bg->ran) { avt_set_error("avt_bgsub: no run behind the handle (avt_bgsub_run_resident after the last upload)"); return 1; }
+    static_assert(sizeof(BgsInfo) % sizeof(int) == 0 && offsetof(BgsInfo, box) == 0, "the boxes are read as ints at a stride of one BgsInfo");
+    *out = avt_bgsub_view{bg->device, bg->n_images, bg->rows, bg->cols, bg->d_depth, (const int*)(BgsInfo*)bg->d_info, (int)(sizeof(BgsInfo) / sizeof(int))};
+    return 0;
+}
+
+int avt_bgsub_reader_begin(avt_bgsub* bg, hipStream_t reader) {
+    if (!bg->ev_ready) AVT_HIP(hipEventCreateWithFlags(&bg->ev_ready, hipEventDisableTiming));
+    if (!bg->ev_reader) AVT_HIP(hipEventCreateWithFlags(&bg->ev_reader, hipEventDisableTiming));
+    if (wait_for_reader(bg)) return 1;         // one reader event: an earlier reader is ordered in front of this one
+    AVT_HIP(hipEventRecord(bg->ev_ready, bg->stream));
+    AVT_HIP(hipStreamWaitEvent(reader, bg->ev_ready, 0));
+    return 0;
+}
+
+int avt_bgsub_reader_end(avt_bgsub* bg, hipStream_t reader) {
+    AVT_HIP(hipEventRecord(bg->ev_reader, reader));
+    bg->reader_pending = true;
+    return 0;
+}
+
 // ---- exported entry points: no C++ exception crosses the C ABI
 extern "C" {
 int avt_bgsub_create(int device, int n_backgrounds, int rows, int cols, const float* backgrounds, avt_bgsub** out) {
@@ -503,9 +543,12 @@ int avt_bgsub_create(int device, int n_backgrounds, int rows, int cols, const fl
 
 void avt_bgsub_destroy(avt_bgsub* bg) {
     if (!bg) return;
+    if (bg->reader_pending) (void)hipEventSynchronize(bg->ev_reader);    // a reader on another stream is done with the buffers
     if (bg->stream) (void)hipStreamSynchronize(bg->stream);
     // the buffers go with `delete`, after the stream: it has just been drained, so nothing is queued on them either way
     if (bg->stream) (void)hipStreamDestroy(bg->stream);
+    if (bg->ev_ready) (void)hipEventDestroy(bg->ev_ready);
+    if (bg->ev_reader) (void)hipEventDestroy(bg->ev_reader);
     delete bg;
 }
 

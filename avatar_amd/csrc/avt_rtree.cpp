@@ -10,6 +10,7 @@
 #include <limits>
 #include <map>
 
+#include "avt_bgsub_internal.h"
 #include "avt_internal.h"
 
 namespace {
@@ -328,7 +329,7 @@ static int avt_rtree_images_upload_impl(avt_rtree* rt, int n_images, int rows, i
     if (reserve_images(rt, pixels)) return 1;
     AVT_HIP(hipSetDevice(rt->device));
     AVT_HIP(hipMemcpyAsync(rt->d_depth, depth, pixels * sizeof(float), hipMemcpyHostToDevice, rt->stream));
-    rt->n_images = n_images; rt->rows = rows; rt->cols = cols;
+    rt->n_images = rt->n_labels = n_images; rt->rows = rows; rt->cols = cols;
     return 0;
 }
 
@@ -340,8 +341,62 @@ int avt_rtree_predict_best_resident(avt_rtree* rt, int interval, int tlx, int tl
     return 0;
 }
 
+static const char* const kHostOnly = "rtree: created host-only (device < 0): inference needs a GPU";
+
+static int predict_best_resident_boxes_impl(avt_rtree* rt, int interval, const int* boxes, int fill) {
+    if (!rt || !boxes) { avt_set_error("avt_rtree_predict_best_resident_boxes: null argument"); return 1; }
+    if (rt->device < 0) { avt_set_error(kHostOnly); return 1; }
+    if (rt->n_images <= 0) { avt_set_error("avt_rtree_predict_best_resident_boxes: no images resident"); return 1; }
+    const int n = rt->n_images, rows = rt->rows, cols = rt->cols;
+    // everything is checked before anything is queued: after a failure the labels of the previous call are still there
+    std::vector<int> b(boxes, boxes + 4 * (size_t)n);
+    for (int i = 0; i < n; ++i) {
+        int* q = &b[4 * (size_t)i];
+        if (q[2] == -1) { q[2] = cols - 1; q[3] = rows - 1; }
+        if (q[0] > q[2] || q[1] > q[3]) continue;          // an empty box: that image stays 255 (a lost stream does not fail the batch)
+        if (roi_ok(rows, cols, interval, q[0], q[1], q[2], q[3])) return 1;
+    }
+    int tlx = 0, tly = 0, brx = -1, bry = -1;
+    if (roi_ok(rows, cols, interval, tlx, tly, brx, bry)) return 1;     // the interval and the image size, when every box is empty
+    AVT_HIP(hipSetDevice(rt->device));
+    if (rt->d_boxes.reserve(4 * (size_t)n)) return 1;
+    AVT_HIP(hipMemcpyAsync(rt->d_boxes, b.data(), b.size() * sizeof(int), hipMemcpyHostToDevice, rt->stream));
+    AVT_HIP(hipStreamSynchronize(rt->stream));             // `b` is on this stack frame
+    if (avt_rtree_launch_predict_boxes(rt, rt->d_depth, rt->d_boxes, 4, n, rows, cols, interval, fill)) { avt_set_error("rtree: kernel launch failed"); return 1; }
+    return 0;
+}
+
+static int predict_best_from_bgsub_impl(avt_rtree* rt, avt_bgsub* bg, int interval, int fill) {
+    if (!rt) { avt_set_error("avt_rtree_predict_best_from_bgsub: null tree"); return 1; }
+    if (rt->device < 0) { avt_set_error(kHostOnly); return 1; }
+    if (!bg) { avt_set_error("avt_rtree_predict_best_from_bgsub: null background subtractor"); return 1; }
+    avt_bgsub_view v;
+    if (avt_bgsub_last_run(bg, &v)) return 1;
+    if (v.device != rt->device) { avt_set_error("avt_rtree_predict_best_from_bgsub: the tree and the background subtractor are on different devices"); return 1; }
+    int tlx = 0, tly = 0, brx = -1, bry = -1;
+    if (roi_ok(v.rows, v.cols, interval, tlx, tly, brx, bry)) return 1;
+    AVT_HIP(hipSetDevice(rt->device));
+    const size_t pixels = (size_t)v.n_images * v.rows * v.cols;
+    if (rt->d_labels.reserve(pixels)) return 1;
+    // the labels are these images' from here on, and the tree has no resident depth of its own until the next images_upload
+    rt->n_images = 0; rt->n_labels = v.n_images; rt->rows = v.rows; rt->cols = v.cols;
+    // the tree's stream waits for the run; bg's next upload / run / destroy waits for the labelling.  No copy, no host wait.
+    if (avt_bgsub_reader_begin(bg, rt->stream)) return 1;
+    const int rc = avt_rtree_launch_predict_boxes(rt, v.d_depth, v.d_boxes, v.box_stride, v.n_images, v.rows, v.cols, interval, fill);
+    if (avt_bgsub_reader_end(bg, rt->stream)) return 1;    // also after a failed launch: the memset may be queued
+    if (rc) { avt_set_error("rtree: kernel launch failed"); return 1; }
+    return 0;
+}
+
+static int labels_download_all_impl(avt_rtree* rt, unsigned char* out) {
+    if (!rt || !out || rt->n_labels <= 0) { avt_set_error("avt_rtree_labels_download_all: bad arguments or no labelled images"); return 1; }
+    AVT_HIP(hipMemcpyAsync(out, rt->d_labels, (size_t)rt->n_labels * rt->rows * rt->cols, hipMemcpyDeviceToHost, rt->stream));
+    AVT_HIP(hipStreamSynchronize(rt->stream));
+    return 0;
+}
+
 int avt_rtree_labels_download(avt_rtree* rt, int image, unsigned char* out) {
-    if (!rt || !out || image < 0 || image >= rt->n_images) { avt_set_error("avt_rtree_labels_download: bad arguments"); return 1; }
+    if (!rt || !out || image < 0 || image >= rt->n_labels) { avt_set_error("avt_rtree_labels_download: bad arguments"); return 1; }
     const size_t px = (size_t)rt->rows * rt->cols;
     AVT_HIP(hipMemcpyAsync(out, rt->d_labels + px * image, px, hipMemcpyDeviceToHost, rt->stream));
     AVT_HIP(hipStreamSynchronize(rt->stream));
@@ -465,6 +520,18 @@ int avt_rtree_predict_best(avt_rtree* rt, const float* depth, int rows, int cols
 
 int avt_rtree_predict(avt_rtree* rt, const float* depth, int rows, int cols, float* dist_out) {
     return avt_guard("avt_rtree_predict", [&]() -> int { return avt_rtree_predict_impl(rt, depth, rows, cols, dist_out); });
+}
+
+int avt_rtree_predict_best_resident_boxes(avt_rtree* rt, int interval, const int* boxes, int fill) {
+    return avt_guard("avt_rtree_predict_best_resident_boxes", [&]() -> int { return predict_best_resident_boxes_impl(rt, interval, boxes, fill); });
+}
+
+int avt_rtree_predict_best_from_bgsub(avt_rtree* rt, avt_bgsub* bg, int interval, int fill) {
+    return avt_guard("avt_rtree_predict_best_from_bgsub", [&]() -> int { return predict_best_from_bgsub_impl(rt, bg, interval, fill); });
+}
+
+int avt_rtree_labels_download_all(avt_rtree* rt, unsigned char* labels_out) {
+    return avt_guard("avt_rtree_labels_download_all", [&]() -> int { return labels_download_all_impl(rt, labels_out); });
 }
 
 int avt_rtree_post_process(const avt_rtree* rt, unsigned char* image, int rows, int cols, double* com_pre, int com_pre_valid, int interval, int tlx,

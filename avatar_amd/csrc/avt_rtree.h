@@ -32,11 +32,16 @@ struct avt_rtree {
     DevBuf<float> d_leaf;            // [n_leafs][num_parts] distributions
     DevBuf<float> d_depth;           // the resident images and their labels: one capacity, in pixels
     DevBuf<unsigned char> d_labels;
-    int n_images = 0, rows = 0, cols = 0;
+    int n_images = 0, rows = 0, cols = 0;     // n_images: resident depth images of the tree's own (0 after a hand-over from bgsub)
+    int n_labels = 0;                         // images d_labels holds (rows x cols each): what avt_rtree_labels_download serves
+    DevBuf<int> d_boxes;                      // n x 4 regions of interest of avt_rtree_predict_best_resident_boxes
     DevBuf<unsigned long long> d_tcount;      // trainTransfer's (leaf, part) counts since the last avt_rtree_transfer_finish
 };
 
 int avt_rtree_launch_predict_dist(avt_rtree* rt, int rows, int cols, float* d_out);
 int avt_rtree_launch_predict(avt_rtree* rt, int n_images, int rows, int cols, int interval, int tlx, int tly, int brx, int bry, int fill);
+// one box per image from device memory (stride in ints), depth from any device buffer; sizes the grid from the image
+int avt_rtree_launch_predict_boxes(avt_rtree* rt, const float* d_depth, const int* d_boxes, int box_stride, int n_images, int rows, int cols,
+                                   int interval, int fill);
 // after leaf_data changed (trainTransfer): re-derives leafBestMatch and uploads nodes and distributions again (avt_rtree.cpp)
 int avt_rtree_refresh_leaves(avt_rtree* rt);

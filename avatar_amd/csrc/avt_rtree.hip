@@ -41,6 +41,44 @@ __global__ __launch_bounds__(256) void k_rtree_predict(const RtNodeDev* __restri
     }
 }
 
+// k_rtree_predict with one region of interest per image, read from device memory: boxes[img * box_stride + 0..3] =
+// tl.x tl.y br.x br.y, inclusive.  The grid covers the interval grid of the whole image, since the host does not know the
+// boxes; a lane outside its image's grid exits.  A box that does not lie inside the image is not trusted: it labels nothing
+// (background subtraction reports an empty mask as (cols-1, rows-1), (0, 0), and a caller's previous box can be anything).
+// Per labelled pixel the arithmetic is k_rtree_predict's.
+__global__ __launch_bounds__(256) void k_rtree_predict_boxes(const RtNodeDev* __restrict__ nodes, const float* __restrict__ depth,
+                                                             unsigned char* __restrict__ labels, const int* __restrict__ boxes, int box_stride,
+                                                             int rows, int cols, int interval, int fill) {
+    const int img = blockIdx.z;
+    const int* box = boxes + (size_t)img * box_stride;
+    const int tlx = box[0], tly = box[1], brx = box[2], bry = box[3];
+    if (!(0 <= tlx && tlx <= brx && brx < cols && 0 <= tly && tly <= bry && bry < rows)) return;
+    const int grows = (bry - tly) / interval, gcols = (brx - tlx) / interval + 1;      // as avt_rtree_launch_predict sizes them
+    const int gc = blockIdx.x * 16 + (threadIdx.x & 15), gr = blockIdx.y * 16 + (threadIdx.x >> 4);
+    if (gc >= gcols || gr >= grows) return;
+    const int r = tly + interval * (gr + 1), c = tlx + interval * gc;                  // r <= bry < rows, c <= brx < cols
+    const float* d = depth + (size_t)img * rows * cols;
+    unsigned char* out = labels + (size_t)img * rows * cols;
+    const float sample = d[(size_t)r * cols + c];
+    unsigned char lab = 255;
+    if (sample != 0.f) {
+        int nodeid = 0;
+        const float4* nv = (const float4*)nodes;
+        for (;;) {
+            const float4 a = nv[2 * nodeid], b = nv[2 * nodeid + 1];
+            const int lnode = __float_as_int(b.y);
+            if (__float_as_int(b.w)) { lab = (unsigned char)lnode; break; }
+            nodeid = (rt_score_by_feature(d, cols, 0, 0, tlx, tly, brx, bry, c, r, sample, a) < b.x) ? lnode : __float_as_int(b.z);
+        }
+    }
+    if (fill && interval > 1) {
+        for (int rr = r; rr < r + interval && rr <= bry; ++rr)
+            for (int cc = c; cc < c + interval && cc < cols; ++cc) out[(size_t)rr * cols + cc] = lab;
+    } else if (lab != 255) {
+        out[(size_t)r * cols + c] = lab;
+    }
+}
+
 // RTree::predict(depth) (RTree.cpp:3156-3182): every pixel, probes bounded by the image, the whole leaf distribution out
 __global__ __launch_bounds__(256) void k_rtree_predict_dist(const RtNodeDev* __restrict__ nodes, const float* __restrict__ leaf_data,
                                                             const float* __restrict__ depth, float* __restrict__ out, int rows, int cols, int num_parts) {
@@ -79,5 +117,18 @@ int avt_rtree_launch_predict(avt_rtree* rt, int n_images, int rows, int cols, in
     dim3 grid((gcols + 15) / 16, (grows + 15) / 16, n_images);
     hipLaunchKernelGGL(k_rtree_predict, grid, dim3(256), 0, rt->stream, rt->d_nodes, rt->d_depth, rt->d_labels, rows, cols, interval, tlx, tly,
                        brx, bry, gcols, grows, fill);
+    return hipGetLastError() != hipSuccess;
+}
+
+// The grid is the interval grid of the whole image: nothing is read back to size it.  `d_depth` need not be the tree's buffer.
+int avt_rtree_launch_predict_boxes(avt_rtree* rt, const float* d_depth, const int* d_boxes, int box_stride, int n_images, int rows, int cols,
+                                   int interval, int fill) {
+    const size_t npix = (size_t)n_images * rows * cols;
+    if (hipMemsetAsync(rt->d_labels, 255, npix, rt->stream) != hipSuccess) return 1;
+    const int grows = (rows - 1) / interval, gcols = (cols - 1) / interval + 1;
+    if (grows <= 0) return 0;
+    dim3 grid((gcols + 15) / 16, (grows + 15) / 16, n_images);
+    hipLaunchKernelGGL(k_rtree_predict_boxes, grid, dim3(256), 0, rt->stream, rt->d_nodes, d_depth, rt->d_labels, d_boxes, box_stride, rows, cols,
+                       interval, fill);
     return hipGetLastError() != hipSuccess;
 }

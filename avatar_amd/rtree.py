@@ -14,7 +14,8 @@ from . import capi
 RTREE_SYMBOLS = [
     "avt_rtree_create", "avt_rtree_load", "avt_rtree_export", "avt_rtree_destroy", "avt_rtree_info", "avt_rtree_get",
     "avt_rtree_predict_best", "avt_rtree_predict", "avt_rtree_images_upload", "avt_rtree_predict_best_resident", "avt_rtree_labels_download",
-    "avt_rtree_sync", "avt_rtree_post_process",
+    "avt_rtree_sync", "avt_rtree_post_process", "avt_rtree_predict_best_resident_boxes", "avt_rtree_predict_best_from_bgsub",
+    "avt_rtree_labels_download_all",
 ]
 
 
@@ -178,8 +179,30 @@ class RTree:
         capi.check(self._lib.avt_rtree_predict_best_resident(self._h, C.c_int(interval), C.c_int(top_left[0]), C.c_int(top_left[1]),
                                                              C.c_int(bot_right[0]), C.c_int(bot_right[1]), C.c_int(1 if fill_in_gaps else 0)))
 
+    def predict_resident_boxes(self, interval, boxes, fill_in_gaps=True):
+        """The resident images, image i inside boxes[i] = (tl.x, tl.y, br.x, br.y), inclusive (demo.cpp:179-204 per stream):
+        br.x == -1 is the whole image, an empty box (tl > br) leaves its image all 255."""
+        b = np.ascontiguousarray(boxes, np.int32).reshape(-1, 4)
+        n = getattr(self, "_shape", (0,))[0]
+        if n and len(b) != n:
+            raise ValueError(f"RTree.predict_resident_boxes: {len(b)} boxes for {n} resident images")
+        capi.check(self._lib.avt_rtree_predict_best_resident_boxes(self._h, C.c_int(interval), capi.ptr(b, C.c_int), C.c_int(1 if fill_in_gaps else 0)))
+
+    def predict_from_bgsub(self, bg, interval, fill_in_gaps=True):
+        """Labels every image of `bg`'s (bgsub.BGSubtractor) last run_resident inside the box that run found, reading the masked
+        depth and the boxes on the device: no copy of the depth, no host wait.  download_labels / download_all_labels then
+        serve these images; the tree's own resident images are gone until the next upload_images."""
+        capi.check(self._lib.avt_rtree_predict_best_from_bgsub(self._h, bg._h, C.c_int(interval), C.c_int(1 if fill_in_gaps else 0)))
+        self._shape = (bg._n,) + tuple(bg._shape[:2])
+
     def sync(self):
         capi.check(self._lib.avt_rtree_sync(self._h))
+
+    def download_all_labels(self):
+        """(n, rows, cols) uint8: the labels of every image of the last batch call, one copy and one wait."""
+        out = np.empty(self._shape, np.uint8)
+        capi.check(self._lib.avt_rtree_labels_download_all(self._h, capi.ptr(out, C.c_ubyte)))
+        return out
 
     def download_labels(self, image):
         out = np.empty(self._shape[1:], np.uint8)

@@ -205,6 +205,45 @@ class MultiFrameTracker:
                 self.streams[s].framesFitted += 1
         return fitted
 
+    # ---- depth in: the front end of demo.cpp:179-204 for all streams at once ----
+    def attach_front_end(self, bgsub, rtree, rtree_interval=2, dist_to_pre_weight=0.001):
+        """`bgsub`: a bgsub.BGSubtractor holding one background per stream; `rtree`: an rtree.RTree on the same device."""
+        self.bgsub, self.rtree = bgsub, rtree
+        self.rtreeInterval, self.distToPreWeight = rtree_interval, dist_to_pre_weight
+        self.comPre = [None] * self.S                 # demo.cpp:148, per stream
+        self.boxes = [None] * self.S                  # ((tl.x, tl.y), (br.x, br.y)) of every stream's last background subtraction
+        self.labels = None
+
+    def process_depth(self, images):
+        """One step from S XYZ maps (S, H, W, 3): background subtraction of image s against background s (every slot keeps the box
+        of its previous run), the forest on the masked depth inside every image's box, both without leaving the device; one
+        download of all labels and of the S boxes; postProcess per stream on the host (a sequential flood fill, as in the
+        reference); then process() with the caller's XYZ.  A stream whose box is empty, or not inside the image, has an all-255
+        mask: it goes through postProcess on the whole image (every comPre x becomes -1) and is lost in process()."""
+        if getattr(self, "bgsub", None) is None:
+            raise RuntimeError("MultiFrameTracker.process_depth: no front end attached (attach_front_end)")
+        if len(images) != self.S:
+            raise ValueError(f"MultiFrameTracker.process_depth: {len(images)} images for {self.S} streams")
+        self.bgsub.upload(images)
+        self.bgsub.run_resident()
+        self.rtree.predict_from_bgsub(self.bgsub, self.rtreeInterval)
+        labels = self.rtree.download_all_labels()
+        frames = []
+        for s in range(self.S):
+            res = self.bgsub.info(s)
+            tl, br = res.topLeft, res.botRight
+            self.boxes[s] = (tl, br)
+            H, W = labels[s].shape
+            if 0 <= tl[0] <= br[0] < W and 0 <= tl[1] <= br[1] < H:
+                self.comPre[s] = self.rtree.postProcess(labels[s], self.comPre[s], self.rtreeInterval, 1, tl, br, self.distToPreWeight)
+                bbox = (tl[1], tl[0], br[1], br[0])
+            else:
+                self.comPre[s] = self.rtree.postProcess(labels[s], self.comPre[s], self.rtreeInterval, 1, (0, 0), (-1, -1), self.distToPreWeight)
+                bbox = (H - 1, W - 1, 0, 0)           # nothing to subsample
+            frames.append((images[s], labels[s], bbox))
+        self.labels = labels                          # the step's post-processed part masks (S, H, W)
+        return self.process(frames)
+
     def posed(self, stream):
         """(cloud (V,3), jointPos (J,3), jointTrans (J,12)) of the stream's last fit (one download; avt_get_posed)."""
         return self.ctx.posed(stream)

@@ -3,7 +3,10 @@
 // neighbThreshRel, numThreads, background, topLeft, botRight), computed on the GPU with the reference's result bit for bit.
 // cv::Mat is replaced by the row-major images of ark/RTree.h (Image8 for the mask) and ImageXYZ below for the CV_32FC3
 // XYZ maps, cv::Point by ark::Point.  The handle is created on the first run() and again when `background` changes size.
+// Beyond the reference: runBatch() runs many streams' images in one launch sequence, image i against backgrounds[i], and
+// leaves the masked depth and the boxes on the device for RTree::predictBestFromBGSub.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdio>
 #include <cstdlib>
@@ -30,6 +33,9 @@ class BGSubtractor {
 public:
     /** Create background subtractor with given background image */
     explicit BGSubtractor(ImageXYZ background, int device = 0) : background(std::move(background)), device_(device) {}
+    /** One background per stream (the batch form); `background` is the first of them */
+    explicit BGSubtractor(std::vector<ImageXYZ> backgrounds_, int device = 0)
+        : background(backgrounds_.empty() ? ImageXYZ() : backgrounds_[0]), backgrounds(std::move(backgrounds_)), device_(device) {}
     ~BGSubtractor() { avt_bgsub_destroy(h_); }
     BGSubtractor(const BGSubtractor&) = delete;
     BGSubtractor& operator=(const BGSubtractor&) = delete;
@@ -43,6 +49,7 @@ public:
         avt_bgsub_frame f;
         f.top_left[0] = topLeft.x; f.top_left[1] = topLeft.y; f.bot_right[0] = botRight.x; f.bot_right[1] = botRight.y;
         if (avt_bgsub_run(h_, 0, image.data(), nnDistThreshRel, neighbThreshRel, mask.data(), maskedDepth_.data(), &f) != 0) die("run");
+        batch_ = 0;                                   // slot 0 now holds this image: no batch run behind the handle
         topLeft = Point(f.top_left[0], f.top_left[1]);
         botRight = Point(f.bot_right[0], f.bot_right[1]);
         fgCount_ = f.fg_count;
@@ -52,6 +59,54 @@ public:
         }
         return mask;
     }
+
+    /** One image's record of a batch run */
+    struct BatchInfo {
+        Point topLeft, botRight;
+        bool capped = false;
+        int fgCount = 0;
+    };
+
+    /** Batch form: image i against background i of `backgrounds` (or bg_index[i]).  prev_boxes: {tl.x, tl.y, br.x, br.y} per image,
+     *  null: every slot keeps the box of its previous batch run ((0,0),(0,0) at first).  Queues the run; batchInfo / batchMask /
+     *  batchMaskedDepth wait for it and fetch one image's part. */
+    void runBatch(const std::vector<ImageXYZ>& images, const std::vector<int>& bg_index = {}, const std::vector<std::array<int, 4>>* prev_boxes = nullptr) {
+        if (images.empty() || !ensure(images[0]) || (!bg_index.empty() && bg_index.size() != images.size()) ||
+            (prev_boxes && prev_boxes->size() != images.size())) die("runBatch");
+        std::vector<float> all;
+        for (const ImageXYZ& im : images) {
+            if (im.rows != rows_ || im.cols != cols_) die("runBatch");
+            all.insert(all.end(), im.a.begin(), im.a.end());
+        }
+        if (avt_bgsub_images_upload(h_, (int)images.size(), all.data(), bg_index.empty() ? nullptr : bg_index.data(),
+                                    prev_boxes ? (*prev_boxes)[0].data() : nullptr) != 0 ||
+            avt_bgsub_run_resident(h_, nnDistThreshRel, neighbThreshRel) != 0)
+            die("runBatch");
+        batch_ = (int)images.size();
+    }
+    int batchSize() const { return batch_; }
+    BatchInfo batchInfo(int i) {
+        avt_bgsub_frame f;
+        if (avt_bgsub_download(h_, i, nullptr, nullptr, &f) != 0) die("batchInfo");
+        BatchInfo b;
+        b.topLeft = Point(f.top_left[0], f.top_left[1]); b.botRight = Point(f.bot_right[0], f.bot_right[1]);
+        b.capped = f.capped != 0; b.fgCount = f.fg_count;
+        return b;
+    }
+    Image8 batchMask(int i) {
+        Image8 m(rows_, cols_, 255);
+        if (avt_bgsub_download(h_, i, m.data(), nullptr, nullptr) != 0) die("batchMask");
+        return m;
+    }
+    ImageF batchMaskedDepth(int i) {
+        ImageF d(rows_, cols_);
+        if (avt_bgsub_download(h_, i, nullptr, d.data(), nullptr) != 0) die("batchMaskedDepth");
+        return d;
+    }
+    /** The C handle and the image size (RTree::predictBestFromBGSub) */
+    avt_bgsub* handle() const { return h_; }
+    int rows() const { return rows_; }
+    int cols() const { return cols_; }
 
     /** Channel 2 of the last image with 0 inside [topLeft, botRight] where the mask is >= 254 (demo.cpp:183-192) */
     const ImageF& maskedDepth() const { return maskedDepth_; }
@@ -66,6 +121,8 @@ public:
     int numThreads = 1;
     /** The background image */
     ImageXYZ background;
+    /** The batch form's backgrounds, one per stream; empty: `background` alone */
+    std::vector<ImageXYZ> backgrounds;
     /** Current top left and bottom right points of foreground */
     Point topLeft, botRight;
 
@@ -73,14 +130,25 @@ private:
     // (re)creates the handle when the background's size changed, uploads the background when its contents did
     bool ensure(const ImageXYZ& image) {
         if (image.rows != background.rows || image.cols != background.cols || background.empty()) return false;
-        if (!h_ || rows_ != background.rows || cols_ != background.cols) {
+        // background 0 is `background` (the reference's member); the batch form's further backgrounds follow it
+        const int nbg = backgrounds.empty() ? 1 : (int)backgrounds.size();
+        std::vector<float> all(background.a);
+        for (int i = 1; i < nbg; ++i) {
+            if (backgrounds[(size_t)i].rows != background.rows || backgrounds[(size_t)i].cols != background.cols) return false;
+            all.insert(all.end(), backgrounds[(size_t)i].a.begin(), backgrounds[(size_t)i].a.end());
+        }
+        if (!h_ || rows_ != background.rows || cols_ != background.cols || nbg_ != nbg) {
             avt_bgsub_destroy(h_);
             h_ = nullptr;
-            if (avt_bgsub_create(device_, 1, background.rows, background.cols, background.data(), &h_) != 0) return false;
-            rows_ = background.rows; cols_ = background.cols; uploaded_ = background.a;
-        } else if (uploaded_ != background.a) {
-            if (avt_bgsub_set_background(h_, 0, background.data()) != 0) return false;
-            uploaded_ = background.a;
+            batch_ = 0;
+            if (avt_bgsub_create(device_, nbg, background.rows, background.cols, all.data(), &h_) != 0) return false;
+            rows_ = background.rows; cols_ = background.cols; nbg_ = nbg; uploaded_ = all;
+        } else if (uploaded_ != all) {
+            const size_t n = (size_t)rows_ * cols_ * 3;
+            for (int i = 0; i < nbg; ++i)
+                if (!std::equal(all.begin() + i * n, all.begin() + (i + 1) * n, uploaded_.begin() + i * n) &&
+                    avt_bgsub_set_background(h_, i, all.data() + i * n) != 0) return false;
+            uploaded_ = all;
         }
         return true;
     }
@@ -89,9 +157,15 @@ private:
         std::exit(1);
     }
     avt_bgsub* h_ = nullptr;
-    int device_ = 0, rows_ = 0, cols_ = 0, fgCount_ = 0;
+    int device_ = 0, rows_ = 0, cols_ = 0, fgCount_ = 0, nbg_ = 0, batch_ = 0;
     std::vector<float> uploaded_;
     ImageF maskedDepth_;
 };
+
+inline std::vector<Image8> RTree::predictBestFromBGSub(BGSubtractor& bgsub, int interval, bool fill_in_gaps) {
+    if (bgsub.batchSize() <= 0) fatal("predictBestFromBGSub", "the background subtractor has no batch run behind it");
+    if (!ensure() || avt_rtree_predict_best_from_bgsub(h_, bgsub.handle(), interval, fill_in_gaps ? 1 : 0) != 0) die("predictBestFromBGSub");
+    return downloadAll(bgsub.batchSize(), bgsub.rows(), bgsub.cols(), "predictBestFromBGSub");
+}
 
 }  // namespace ark

@@ -6,6 +6,10 @@
 // resident; a lost stream rides as an empty frame); avt_state_upload_frames for the streams that reinitialise (the first step
 // installs all S with avt_state_upload); avt_optimize_resident_budgets with icp_iters = the largest budget of the step; one
 // avt_state_download.  Per-stream p, r, w and stats are always there; posed clouds are fetched on request (posed()).
+//
+// processDepth() puts the front end of demo.cpp:179-204 in front of a step for all streams at once: BGSubtractor::runBatch, then
+// RTree::predictBestFromBGSub on the masked depth where it lies on the device, one download of all labels, postProcess per stream
+// on the host (a sequential flood fill, as in the reference), then process() with the caller's XYZ maps.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -13,6 +17,7 @@
 
 #include "../avt_render.h"
 #include "AvatarOptimizer.h"
+#include "BGSubtractor.h"
 #include "RTree.h"
 #include "TrackerPolicy.h"
 
@@ -113,6 +118,44 @@ class MultiFrameTracker {
             if (fitted[(size_t)s]) { stats[(size_t)s] = st[(size_t)s]; ++streams[(size_t)s].framesFitted; }
     }
 
+    /** The front end of processDepth: a BGSubtractor holding one background per stream and a forest on the same device (both
+     *  outlive the tracker's use of them); the interval of predictBest / postProcess (demo.cpp:198) and postProcess's weight. */
+    void attachFrontEnd(BGSubtractor& bgsub, RTree& rtree, int rtree_interval = 2, double dist_to_pre_weight = 0.001) {
+        frontBG = &bgsub; frontTree = &rtree;
+        rtreeInterval = rtree_interval; distToPreWeight = dist_to_pre_weight;
+        comPre.assign((size_t)S, MatrixNX<2>());
+        boxes.assign((size_t)S, {0, 0, 0, 0});
+        partMasks.clear();
+    }
+
+    /** One step from S XYZ maps: image s against background s (every slot keeps the box of its previous run), labelled inside its
+     *  box without leaving the device, post-processed on the host with stream s's comPre, then process().  A stream whose box is
+     *  empty or not inside the image has an all-255 mask: it goes through postProcess on the whole image (every comPre x becomes
+     *  -1) and is lost in process().  Afterwards partMasks[s] and boxes[s] (tl.x tl.y br.x br.y) hold the step's labels and boxes. */
+    void processDepth(const std::vector<ImageXYZ>& images, std::vector<int>& fitted) {
+        if (!frontBG || !frontTree) { std::fprintf(stderr, "MultiFrameTracker::processDepth: no front end attached\n"); std::exit(1); }
+        if ((int)images.size() != S) { std::fprintf(stderr, "MultiFrameTracker: %d images for %d streams\n", (int)images.size(), S); std::exit(1); }
+        frontBG->runBatch(images);
+        partMasks = frontTree->predictBestFromBGSub(*frontBG, rtreeInterval);
+        std::vector<Frame> frames((size_t)S);
+        for (int s = 0; s < S; ++s) {
+            const BGSubtractor::BatchInfo b = frontBG->batchInfo(s);
+            boxes[(size_t)s] = {b.topLeft.x, b.topLeft.y, b.botRight.x, b.botRight.y};
+            Image8& m = partMasks[(size_t)s];
+            Rect box;
+            if (0 <= b.topLeft.x && b.topLeft.x <= b.botRight.x && b.botRight.x < m.cols && 0 <= b.topLeft.y && b.topLeft.y <= b.botRight.y &&
+                b.botRight.y < m.rows) {
+                frontTree->postProcess(m, comPre[(size_t)s], rtreeInterval, 1, b.topLeft, b.botRight, distToPreWeight);
+                box.top = b.topLeft.y; box.left = b.topLeft.x; box.bottom = b.botRight.y; box.right = b.botRight.x;
+            } else {
+                frontTree->postProcess(m, comPre[(size_t)s], rtreeInterval, 1, Point(0, 0), Point(-1, -1), distToPreWeight);
+                box.top = m.rows - 1; box.left = m.cols - 1; box.bottom = 0; box.right = 0;       // nothing to subsample
+            }
+            frames[(size_t)s] = {images[(size_t)s].data(), m.data(), m.cols, m.rows, box};
+        }
+        process(frames, fitted);
+    }
+
     /** ava.cloud (3 x V), jointPos (3 x J), jointTrans (12 x J) of stream s's last fit; any pointer may be null (avt_get_posed) */
     void posed(int s, double* cloud_3xV, double* joint_pos_3xJ = nullptr, double* joint_trans_12xJ = nullptr) {
         ARK_AVT_CHECK(avt_get_posed(ctx, s, cloud_3xV, joint_pos_3xJ, joint_trans_12xJ));
@@ -160,6 +203,12 @@ class MultiFrameTracker {
     int maxItersPerICP = 10;
     bool enableOcclusion = true;
     std::vector<int> budgets, reinitStreams;       // of the last step (0 = not fitted)
+    // processDepth: per stream the previous centres of mass (demo.cpp:148), the last step's box and post-processed labels
+    std::vector<MatrixNX<2>> comPre;
+    std::vector<std::array<int, 4>> boxes;
+    std::vector<Image8> partMasks;
+    int rtreeInterval = 2;
+    double distToPreWeight = 0.001;
 
    private:
     std::vector<double> p, q, w;
@@ -169,6 +218,8 @@ class MultiFrameTracker {
 
    private:
     avt_ctx* ctx = nullptr;
+    BGSubtractor* frontBG = nullptr;
+    RTree* frontTree = nullptr;
     int device_ = 0;
     avt_renderer* rend = nullptr;                  // render(): created on first use, again when the size or the intrinsics change
     int rendW = 0, rendH = 0;

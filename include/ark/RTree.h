@@ -6,6 +6,7 @@
 // skinned, rendered and sampled on the device; train(images...) feeds it in-memory depth images and part masks;
 // trainTransfer(images...) re-fits the leaves (:3332-3420).  The V2 trainer of train(depth_dir, part_mask_dir, ...) is not built.
 #pragma once
+#include <array>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -41,6 +42,8 @@ struct Image {  // row-major rows x cols, the layout of a continuous single-chan
 };
 using ImageF = Image<float>;      // CV_32F depth, metres, 0 = background
 using Image8 = Image<uint8_t>;    // CV_8U part labels, 255 = none
+
+class BGSubtractor;   // ark/BGSubtractor.h, which defines RTree::predictBestFromBGSub
 
 class RTree {
 public:
@@ -83,6 +86,28 @@ public:
             die("predictBest");
         return result;
     }
+
+    /** predictBest for a batch of same-size images, image i inside boxes[i] = {tl.x, tl.y, br.x, br.y} (the labelling of
+     *  demo.cpp:179-204 for many streams in one launch): br.x == -1 is the whole image, an empty box (tl > br) leaves its image
+     *  all 255.  One upload, one launch sequence, one download. */
+    std::vector<Image8> predictBestBatch(const std::vector<ImageF>& depths, int interval, const std::vector<std::array<int, 4>>& boxes,
+                                         bool fill_in_gaps = true) {
+        if (depths.empty() || depths.size() != boxes.size()) fatal("predictBestBatch", "need one box per depth image, at least one");
+        const int rows = depths[0].rows, cols = depths[0].cols;
+        std::vector<float> d;
+        for (const ImageF& im : depths) {
+            if (im.rows != rows || im.cols != cols) fatal("predictBestBatch", "the images must share one size");
+            d.insert(d.end(), im.a.begin(), im.a.end());
+        }
+        if (!ensure() || avt_rtree_images_upload(h_, (int)depths.size(), rows, cols, d.data()) != 0 ||
+            avt_rtree_predict_best_resident_boxes(h_, interval, boxes[0].data(), fill_in_gaps ? 1 : 0) != 0)
+            die("predictBestBatch");
+        return downloadAll((int)depths.size(), rows, cols, "predictBestBatch");
+    }
+
+    /** The labels of every image of bgsub's last runBatch, each inside the box that run found, read from the masked depth on the
+     *  device (demo.cpp:179-204 without the host in between; avt_rtree_predict_best_from_bgsub).  Defined in ark/BGSubtractor.h. */
+    std::vector<Image8> predictBestFromBGSub(BGSubtractor& bgsub, int interval = 1, bool fill_in_gaps = true);
 
     /** Predict distribution for all of image: numParts planes of CV_32F (RTree.h:59-61) */
     std::vector<ImageF> predict(const ImageF& depth) {
@@ -218,6 +243,13 @@ private:
         if (avt_rtree_create(&d, device_, &h_) != 0) return false;
         pull();
         return true;
+    }
+    std::vector<Image8> downloadAll(int n, int rows, int cols, const char* what) {
+        std::vector<uint8_t> all((size_t)n * rows * cols);
+        if (avt_rtree_labels_download_all(h_, all.data()) != 0) die(what);
+        std::vector<Image8> result((size_t)n, Image8(rows, cols));
+        for (int i = 0; i < n; ++i) result[(size_t)i].a.assign(all.begin() + (size_t)i * rows * cols, all.begin() + (size_t)(i + 1) * rows * cols);
+        return result;
     }
     void pull() {
         int n = 0, nl = 0, pml = 0;

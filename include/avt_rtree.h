@@ -16,6 +16,7 @@ extern "C" {
 #endif
 
 typedef struct avt_rtree avt_rtree;
+struct avt_bgsub;              /* include/avt_bgsub.h */
 
 /* The members of `class RTree` (RTree.h:171-184): nodes, leafData, numParts, partMap (+ its type). */
 typedef struct avt_rtree_desc {
@@ -57,6 +58,23 @@ int avt_rtree_images_upload(avt_rtree* rt, int n_images, int rows, int cols, con
 int avt_rtree_predict_best_resident(avt_rtree* rt, int interval, int tl_x, int tl_y, int br_x, int br_y, int fill_in_gaps);
 int avt_rtree_labels_download(avt_rtree* rt, int image, unsigned char* labels_out);
 int avt_rtree_sync(avt_rtree* rt);
+
+/* The labelling of demo.cpp:179-204 for a batch of streams: every image inside its own box, as predictBest(depth, ..., interval,
+ * bgsub.topLeft, bgsub.botRight) gives it per image.  boxes: n_images x 4 host ints tl.x tl.y br.x br.y, inclusive, copied on
+ * the tree's stream; br.x == -1 is the whole image; an empty box (tl > br in either axis, background subtraction's "no
+ * foreground") leaves that image all 255 and is no error; a box shorter than `interval` rows labels nothing (the first row
+ * touched is tl.y + interval).  A box outside the image or a bad interval fails before anything is queued. */
+int avt_rtree_predict_best_resident_boxes(avt_rtree* rt, int interval, const int* boxes, int fill_in_gaps);
+/* demo.cpp:179-204 without the host in between: labels every image of `bg`'s last avt_bgsub_run_resident, each inside the box
+ * that run left on the device, reading the masked depth where it lies.  No copy of the depth, no host synchronisation: the
+ * tree's stream waits for the run, and bg's next images_upload, run_resident and destroy wait for the labelling.  A box on the
+ * device that does not lie inside the image (an empty mask, a capped run's unusable previous box) labels nothing.  Both handles
+ * must be on one device; `bg` must have a run behind it.  Afterwards avt_rtree_labels_download[_all] serve these images; the
+ * tree has no resident depth of its own until the next avt_rtree_images_upload. */
+int avt_rtree_predict_best_from_bgsub(avt_rtree* rt, struct avt_bgsub* bg, int interval, int fill_in_gaps);
+/* The labels of every image of the last labelling call (demo.cpp:179-204 for all streams): n_images x rows x cols bytes, one
+ * copy and one wait. */
+int avt_rtree_labels_download_all(avt_rtree* rt, unsigned char* labels_out);
 
 /* void RTree::postProcess(image, com_pre, interval, num_threads, top_left, bot_right, dist_to_pre_weight) const
  * (RTree.cpp:3422-3449): largest-component selection per part ('contiguous' part maps) or small-piece removal
