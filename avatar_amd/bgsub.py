@@ -10,10 +10,12 @@ import ctypes as C
 import numpy as np
 
 from . import capi
+from .depth import depth_to_xyz, intrin_array
 
 BGSUB_SYMBOLS = [
     "avt_bgsub_create", "avt_bgsub_destroy", "avt_bgsub_set_background", "avt_bgsub_run", "avt_bgsub_images_upload",
-    "avt_bgsub_run_resident", "avt_bgsub_download", "avt_bgsub_sync",
+    "avt_bgsub_run_resident", "avt_bgsub_download", "avt_bgsub_sync", "avt_bgsub_depth_upload", "avt_bgsub_run_depth",
+    "avt_bgsub_set_background_depth", "avt_bgsub_xyz_download",
 ]
 MAX_COMPS = 254
 DEVICE_FAULT = 3        # AVT_STATUS_DEVICE_FAULT (include/avt.h)
@@ -29,6 +31,13 @@ def _xyz(a, shape):
     a = np.ascontiguousarray(a, np.float32)
     if a.shape[-3:] != shape:
         raise ValueError(f"BGSubtractor: image shape {a.shape} does not match the background's {shape}")
+    return a
+
+
+def _depth(a, shape):
+    a = np.ascontiguousarray(a, np.float32)
+    if a.shape[-2:] != shape[:2]:
+        raise ValueError(f"BGSubtractor: depth image shape {a.shape} does not match the background's {shape[:2]}")
     return a
 
 
@@ -89,18 +98,38 @@ class BGSubtractor:
         capi.check(self._lib.avt_bgsub_set_background(self._h, C.c_int(index), capi.ptr(a, C.c_float)))
         self._bgs[index] = a
 
+    def set_background_depth(self, depth, intrin, index=0):
+        """set_background from a depth image (rows, cols) and its camera: expanded on the device (CameraIntrin::depthToXYZ)."""
+        a = _depth(depth, self._shape)
+        if a.ndim != 2:
+            raise ValueError("BGSubtractor.set_background_depth: one (rows, cols) depth image")
+        k = intrin_array(intrin, 1)
+        capi.check(self._lib.avt_bgsub_set_background_depth(self._h, C.c_int(index), capi.ptr(a, C.c_float), capi.ptr(k, C.c_float)))
+        self._bgs[index] = depth_to_xyz(a, k[0])
+
     def run(self, image, comps_by_size=False, background_index=0):
         """cv::Mat BGSubtractor::run(image, comps_by_size) (BGSubtractor.cpp:159-163): the mask; with comps_by_size
         True returns (mask, [(size, id), ...])."""
         a = _xyz(image, self._shape)
+        return self._run(self._lib.avt_bgsub_run, (capi.ptr(a, C.c_float),), comps_by_size, background_index)
+
+    def run_depth(self, depth, intrin, comps_by_size=False, background_index=0):
+        """run() on a depth image (rows, cols) and its camera (a depth.CameraIntrin or fx, fy, cx, cy): the XYZ map is
+        built on the device, bit for bit depth.depth_to_xyz."""
+        a = _depth(depth, self._shape)
+        if a.ndim != 2:
+            raise ValueError("BGSubtractor.run_depth: one (rows, cols) depth image")
+        k = intrin_array(intrin, 1)
+        return self._run(self._lib.avt_bgsub_run_depth, (capi.ptr(a, C.c_float), capi.ptr(k, C.c_float)), comps_by_size, background_index)
+
+    def _run(self, entry, source, comps_by_size, background_index):
         mask = np.empty(self._shape[:2], np.uint8)
         depth = np.empty(self._shape[:2], np.float32)
         fr = Frame()
         fr.top_left[:] = self.topLeft
         fr.bot_right[:] = self.botRight
-        capi.check(self._lib.avt_bgsub_run(self._h, C.c_int(background_index), capi.ptr(a, C.c_float), C.c_float(self.nnDistThreshRel),
-                                           C.c_float(self.neighbThreshRel), capi.ptr(mask, C.c_ubyte), capi.ptr(depth, C.c_float),
-                                           C.byref(fr)))
+        capi.check(entry(self._h, C.c_int(background_index), *source, C.c_float(self.nnDistThreshRel), C.c_float(self.neighbThreshRel),
+                         capi.ptr(mask, C.c_ubyte), capi.ptr(depth, C.c_float), C.byref(fr)))
         self._n = 1
         res = Result(mask, depth, fr)
         self.topLeft, self.botRight, self.maskedDepth, self.fgCount, self.capped = res.topLeft, res.botRight, depth, res.fg_count, res.capped
@@ -117,6 +146,26 @@ class BGSubtractor:
         capi.check(self._lib.avt_bgsub_images_upload(self._h, C.c_int(n), capi.ptr(a, C.c_float), capi.ptr(bi, C.c_int),
                                                      capi.ptr(pb, C.c_int)))
         self._n = n
+
+    def upload_depth(self, depth, intrin, bg_index=None, prev_boxes=None):
+        """upload() from depth images (n, rows, cols) and `intrin`, one camera for all of them or (n, 4) fx fy cx cy: a
+        third of the bytes cross the bus, the XYZ maps are built on the device."""
+        a = _depth(depth, self._shape)
+        if a.ndim != 3:
+            raise ValueError("BGSubtractor.upload_depth: depth images must be (n, rows, cols)")
+        n = a.shape[0]
+        k = intrin_array(intrin, n)
+        bi = None if bg_index is None else np.ascontiguousarray(bg_index, np.int32)
+        pb = None if prev_boxes is None else np.ascontiguousarray(prev_boxes, np.int32).reshape(n, 4)
+        capi.check(self._lib.avt_bgsub_depth_upload(self._h, C.c_int(n), capi.ptr(a, C.c_float), capi.ptr(k, C.c_float),
+                                                    capi.ptr(bi, C.c_int), capi.ptr(pb, C.c_int)))
+        self._n = n
+
+    def xyz(self, image):
+        """The resident XYZ map (rows, cols, 3) of image `image`, after either kind of upload."""
+        out = np.empty(self._shape, np.float32)
+        capi.check(self._lib.avt_bgsub_xyz_download(self._h, C.c_int(image), capi.ptr(out, C.c_float)))
+        return out
 
     def run_resident(self):
         capi.check(self._lib.avt_bgsub_run_resident(self._h, C.c_float(self.nnDistThreshRel), C.c_float(self.neighbThreshRel)))

@@ -2,6 +2,9 @@
 // as a near-background test plus a union-find connected-component labelling whose roots are the smallest raster index
 // of every component, so the partition, the roots and hence the ids are the reference's whatever the scheduling.
 //
+// Depth images in (avt_bgsub_depth_upload and its kin): k_bgs_backproject expands n x N uploaded depth floats into the
+// resident XYZ images with CameraIntrin::depthToXYZ's float expression (Calibration.cpp:82-95); the rest runs unchanged.
+//
 // Launch sequence per run (every kernel batched over the images on a grid dimension):
 //   k_bgs_local    32x32 tile per 256-thread workgroup: the 3x3 near-background test against an LDS copy of the
 //                  background tile and its one-pixel halo (:30-76), then union-find over the tile's 4-neighbour edges
@@ -49,10 +52,13 @@ struct avt_bgsub {
     DevBuf<float> d_bg;                    // n_bg x N x 3
     DevBuf<float> d_img;                   // cap x N x 3, cap = d_info.cap images (reserve() grows d_info last)
     DevBuf<int> d_bgidx;                   // cap
-    DevBuf<int> d_label;                   // cap x N: parent / root index, -1 not a candidate
+    DevBuf<int> d_label;                   // cap x N: parent / root index, -1 not a candidate.  Dead once a run has ended (nothing reads it
+                                           // after k_bgs_mask): avt_bgsub_set_background_depth stages its depth image in slot 0 of it
     DevBuf<int> d_count;                   // cap x N: size at a root; after k_bgs_ids -1 - code at a kept root
     DevBuf<unsigned char> d_mask;          // cap x N
-    DevBuf<float> d_depth;                 // cap x N
+    DevBuf<float> d_depth;                 // cap x N: a run's masked depth; between a depth upload and its k_bgs_backproject the staged depth
+    DevBuf<float> d_intrin;                // cap x 4: fx fy cx cy of every image of a depth upload, read by the k_bgs_backproject that the
+                                           // upload queues and by nothing later; avt_bgsub_set_background_depth overwrites entry 0
     DevBuf<BgsInfo> d_info;                // cap
     DevBuf<unsigned> d_fault;              // sticky fault word of the handle
     int n_images = 0;
@@ -353,6 +359,53 @@ __global__ __launch_bounds__(256) void k_bgs_depth(const float* __restrict__ img
     if (b && (threadIdx.x & 63) == 0) atomicAdd(&in.fg_count, __popcll(b));
 }
 
+// CameraIntrin::depthToXYZ (Calibration.cpp:82-95) for one pixel: int to float, minus the centre, times z, over the focal
+// length; a true IEEE division, nothing fused (this file is built with -ffp-contract=off)
+__device__ __forceinline__ void backproject(float z, int r, int c, float fx, float fy, float cx, float cy, float& x, float& y) {
+    x = ((float)c - cx) * z / fx;
+    y = ((float)r - cy) * z / fy;
+}
+
+// A copy's shape: 4 B in, 12 B out per pixel.  A lane takes four consecutive pixels of image blockIdx.y, one 16-byte load
+// and three 16-byte stores (48 contiguous bytes), where both addresses are 16-byte aligned (an image's base is when its
+// offset in pixels is a multiple of 4: the first image of a buffer always, every image when npix % 4 == 0) and four pixels
+// are left; the scalar form otherwise.  Row and column follow the pixel index: a group may cross row ends.
+__global__ __launch_bounds__(256) void k_bgs_backproject(const float* __restrict__ depth, const float* __restrict__ intrin, float* __restrict__ xyz,
+                                                         int npix, int cols) {
+    const int img = blockIdx.y;
+    const int p0 = (int)(blockIdx.x * 256 + threadIdx.x) * 4;        // < npix + 1024 <= 2^30 + 1023 (avt_bgsub_create)
+    if (p0 >= npix) return;
+    const size_t base = (size_t)img * npix;
+    const float* d = depth + base + p0;
+    float* o = xyz + (base + p0) * 3;
+    const float fx = intrin[4 * img], fy = intrin[4 * img + 1], cx = intrin[4 * img + 2], cy = intrin[4 * img + 3];
+    int r = p0 / cols, c = p0 - r * cols;
+    if ((((size_t)d | (size_t)o) & 15) == 0 && p0 + 4 <= npix) {
+        const float4 z4 = *reinterpret_cast<const float4*>(d);
+        const float z[4] = {z4.x, z4.y, z4.z, z4.w};
+        float v[12];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            backproject(z[k], r, c, fx, fy, cx, cy, v[3 * k], v[3 * k + 1]);
+            v[3 * k + 2] = z[k];
+            if (++c == cols) { c = 0; ++r; }
+        }
+        float4* o4 = reinterpret_cast<float4*>(o);
+        o4[0] = make_float4(v[0], v[1], v[2], v[3]);
+        o4[1] = make_float4(v[4], v[5], v[6], v[7]);
+        o4[2] = make_float4(v[8], v[9], v[10], v[11]);
+        return;
+    }
+    const int left = min(4, npix - p0);
+    for (int k = 0; k < left; ++k) {
+        const float z = d[k];
+        float x, y;
+        backproject(z, r, c, fx, fy, cx, cy, x, y);
+        o[3 * k] = x; o[3 * k + 1] = y; o[3 * k + 2] = z;
+        if (++c == cols) { c = 0; ++r; }
+    }
+}
+
 // before the stream overwrites what a reader on another stream may still read
 int wait_for_reader(avt_bgsub* bg) {
     if (!bg->reader_pending) return 0;
@@ -376,6 +429,7 @@ int reserve(avt_bgsub* bg, int n) {
         if (bg->d_count.reserve(n * N)) return 1;
         if (bg->d_mask.reserve(n * N)) return 1;
         if (bg->d_depth.reserve(n * N)) return 1;
+        if (bg->d_intrin.reserve(n * 4)) return 1;
         // the slots the handle had keep their previous boxes (avt_bgsub.h: a batch without prev_boxes uses them); only the
         // new slots start at cv::Point()
         if (bg->d_info.grow(n, old, bg->stream, false)) return 1;
@@ -424,28 +478,60 @@ int create_impl(int device, int n_bg, int rows, int cols, const float* backgroun
     return 0;
 }
 
-int set_background_impl(avt_bgsub* bg, int index, const float* xyz) {
-    if (!bg || !xyz || index < 0 || index >= bg->n_bg) { avt_set_error("avt_bgsub_set_background: bad arguments"); return 1; }
+// n depth images at `staged` (device, n x N floats) with their cameras in d_intrin into n XYZ images at `xyz`
+void launch_backproject(avt_bgsub* bg, int n, const float* staged, float* xyz) {
+    const int npix = bg->rows * bg->cols;
+    hipLaunchKernelGGL(k_bgs_backproject, dim3((npix + 1023) / 1024, n), dim3(256), 0, bg->stream, staged, bg->d_intrin, xyz, npix, bg->cols);
+}
+
+// `intrin` null: `src` is the XYZ map; else `src` is a depth image (rows x cols) and intrin its camera (fx fy cx cy)
+int set_background_impl(avt_bgsub* bg, int index, const float* src, const float* intrin, bool from_depth) {
+    if (!bg || !src || (from_depth && !intrin) || index < 0 || index >= bg->n_bg) {
+        avt_set_error(from_depth ? "avt_bgsub_set_background_depth: bad arguments" : "avt_bgsub_set_background: bad arguments");
+        return 1;
+    }
     AVT_HIP(hipSetDevice(bg->device));
-    const size_t n = (size_t)bg->rows * bg->cols * 3;
-    AVT_HIP(hipMemcpyAsync(bg->d_bg + (size_t)index * n, xyz, n * sizeof(float), hipMemcpyHostToDevice, bg->stream));
+    const size_t N = (size_t)bg->rows * bg->cols;
+    float* dst = bg->d_bg + (size_t)index * N * 3;
+    if (!from_depth) {
+        AVT_HIP(hipMemcpyAsync(dst, src, N * 3 * sizeof(float), hipMemcpyHostToDevice, bg->stream));
+    } else {
+        // staged in the first slot of d_label, a run's scratch that holds nothing once the run has ended (d_depth would do for
+        // size, but the last run's masked depth stays downloadable across a change of background, as it does for an XYZ one)
+        if (reserve(bg, 1)) return 1;
+        float* staged = reinterpret_cast<float*>((int*)bg->d_label);
+        AVT_HIP(hipMemcpyAsync(staged, src, N * sizeof(float), hipMemcpyHostToDevice, bg->stream));
+        AVT_HIP(hipMemcpyAsync(bg->d_intrin, intrin, 4 * sizeof(float), hipMemcpyHostToDevice, bg->stream));
+        launch_backproject(bg, 1, staged, dst);
+        AVT_HIP(hipGetLastError());
+    }
     AVT_HIP(hipStreamSynchronize(bg->stream));
     return 0;
 }
 
-int upload_impl(avt_bgsub* bg, int n, const float* images, const int* bg_index, const int* prev_boxes) {
-    if (!bg || !images || n <= 0) { avt_set_error("avt_bgsub_images_upload: bad arguments"); return 1; }
+// intrin null: `src` holds n XYZ maps; else n depth images and intrin n x 4 (fx fy cx cy per image)
+int upload_impl(avt_bgsub* bg, int n, const float* src, const float* intrin, bool from_depth, const int* bg_index, const int* prev_boxes) {
+    const char* name = from_depth ? "avt_bgsub_depth_upload" : "avt_bgsub_images_upload";
+    if (!bg || !src || (from_depth && !intrin) || n <= 0) { avt_set_error(std::string(name) + ": bad arguments"); return 1; }
     std::vector<int> idx(n);
     for (int i = 0; i < n; ++i) {
         idx[i] = bg_index ? bg_index[i] : i;
-        if (idx[i] < 0 || idx[i] >= bg->n_bg) { avt_set_error("avt_bgsub_images_upload: background index out of range"); return 1; }
+        if (idx[i] < 0 || idx[i] >= bg->n_bg) { avt_set_error(std::string(name) + ": background index out of range"); return 1; }
     }
     AVT_HIP(hipSetDevice(bg->device));
     if (wait_for_reader(bg)) return 1;
     bg->ran = false;
     if (reserve(bg, n)) return 1;
     const size_t N = (size_t)bg->rows * bg->cols;
-    AVT_HIP(hipMemcpyAsync(bg->d_img, images, (size_t)n * N * 3 * sizeof(float), hipMemcpyHostToDevice, bg->stream));
+    if (!from_depth) {
+        AVT_HIP(hipMemcpyAsync(bg->d_img, src, (size_t)n * N * 3 * sizeof(float), hipMemcpyHostToDevice, bg->stream));
+    } else {
+        // staged in d_depth: the reader of the last run's masked depth has been waited for above, and the next run rewrites it
+        AVT_HIP(hipMemcpyAsync(bg->d_depth, src, (size_t)n * N * sizeof(float), hipMemcpyHostToDevice, bg->stream));
+        AVT_HIP(hipMemcpyAsync(bg->d_intrin, intrin, (size_t)n * 4 * sizeof(float), hipMemcpyHostToDevice, bg->stream));
+        launch_backproject(bg, n, bg->d_depth, bg->d_img);
+        AVT_HIP(hipGetLastError());
+    }
     AVT_HIP(hipMemcpyAsync(bg->d_bgidx, idx.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, bg->stream));
     if (prev_boxes)
         for (int i = 0; i < n; ++i) AVT_HIP(hipMemcpyAsync(bg->d_info[i].box, prev_boxes + 4 * (size_t)i, 4 * sizeof(int), hipMemcpyHostToDevice, bg->stream));
@@ -500,12 +586,21 @@ int download_impl(avt_bgsub* bg, int image, unsigned char* mask_out, float* dept
     return 0;
 }
 
-int run_impl(avt_bgsub* bg, int background_index, const float* xyz, float nn_rel, float neighb_rel, unsigned char* mask_out, float* depth_out,
-             avt_bgsub_frame* info) {
-    if (!bg || !xyz || !mask_out) { avt_set_error("avt_bgsub_run: null argument"); return 1; }
+int xyz_download_impl(avt_bgsub* bg, int image, float* xyz_out) {
+    if (!bg || !xyz_out || image < 0 || image >= bg->n_images) { avt_set_error("avt_bgsub_xyz_download: bad arguments (no such resident image)"); return 1; }
+    AVT_HIP(hipSetDevice(bg->device));
+    const size_t n = (size_t)bg->rows * bg->cols * 3;
+    AVT_HIP(hipMemcpyAsync(xyz_out, bg->d_img + image * n, n * sizeof(float), hipMemcpyDeviceToHost, bg->stream));
+    AVT_HIP(hipStreamSynchronize(bg->stream));
+    return 0;
+}
+
+int run_impl(avt_bgsub* bg, int background_index, const float* src, const float* intrin, bool from_depth, float nn_rel, float neighb_rel,
+             unsigned char* mask_out, float* depth_out, avt_bgsub_frame* info) {
+    if (!bg || !src || (from_depth && !intrin) || !mask_out) { avt_set_error(from_depth ? "avt_bgsub_run_depth: null argument" : "avt_bgsub_run: null argument"); return 1; }
     int box[4] = {0, 0, 0, 0};
     if (info) { box[0] = info->top_left[0]; box[1] = info->top_left[1]; box[2] = info->bot_right[0]; box[3] = info->bot_right[1]; }
-    if (upload_impl(bg, 1, xyz, &background_index, box)) return 1;
+    if (upload_impl(bg, 1, src, intrin, from_depth, &background_index, box)) return 1;
     if (run_resident_impl(bg, nn_rel, neighb_rel)) return 1;
     return download_impl(bg, 0, mask_out, depth_out, info);
 }
@@ -553,16 +648,16 @@ void avt_bgsub_destroy(avt_bgsub* bg) {
 }
 
 int avt_bgsub_set_background(avt_bgsub* bg, int index, const float* xyz) {
-    return avt_guard("avt_bgsub_set_background", [&]() -> int { return set_background_impl(bg, index, xyz); });
+    return avt_guard("avt_bgsub_set_background", [&]() -> int { return set_background_impl(bg, index, xyz, nullptr, false); });
 }
 
 int avt_bgsub_run(avt_bgsub* bg, int background_index, const float* xyz, float nn_rel, float neighb_rel, unsigned char* mask_out,
                   float* masked_depth_out, avt_bgsub_frame* info) {
-    return avt_guard("avt_bgsub_run", [&]() -> int { return run_impl(bg, background_index, xyz, nn_rel, neighb_rel, mask_out, masked_depth_out, info); });
+    return avt_guard("avt_bgsub_run", [&]() -> int { return run_impl(bg, background_index, xyz, nullptr, false, nn_rel, neighb_rel, mask_out, masked_depth_out, info); });
 }
 
 int avt_bgsub_images_upload(avt_bgsub* bg, int n_images, const float* images, const int* bg_index, const int* prev_boxes) {
-    return avt_guard("avt_bgsub_images_upload", [&]() -> int { return upload_impl(bg, n_images, images, bg_index, prev_boxes); });
+    return avt_guard("avt_bgsub_images_upload", [&]() -> int { return upload_impl(bg, n_images, images, nullptr, false, bg_index, prev_boxes); });
 }
 
 int avt_bgsub_run_resident(avt_bgsub* bg, float nn_rel, float neighb_rel) {
@@ -571,6 +666,23 @@ int avt_bgsub_run_resident(avt_bgsub* bg, float nn_rel, float neighb_rel) {
 
 int avt_bgsub_download(avt_bgsub* bg, int image, unsigned char* mask_out, float* masked_depth_out, avt_bgsub_frame* info) {
     return avt_guard("avt_bgsub_download", [&]() -> int { return download_impl(bg, image, mask_out, masked_depth_out, info); });
+}
+
+int avt_bgsub_depth_upload(avt_bgsub* bg, int n_images, const float* depth, const float* intrin, const int* bg_index, const int* prev_boxes) {
+    return avt_guard("avt_bgsub_depth_upload", [&]() -> int { return upload_impl(bg, n_images, depth, intrin, true, bg_index, prev_boxes); });
+}
+
+int avt_bgsub_run_depth(avt_bgsub* bg, int background_index, const float* depth, const float* intrin, float nn_rel, float neighb_rel,
+                        unsigned char* mask_out, float* masked_depth_out, avt_bgsub_frame* info) {
+    return avt_guard("avt_bgsub_run_depth", [&]() -> int { return run_impl(bg, background_index, depth, intrin, true, nn_rel, neighb_rel, mask_out, masked_depth_out, info); });
+}
+
+int avt_bgsub_set_background_depth(avt_bgsub* bg, int index, const float* depth, const float* intrin) {
+    return avt_guard("avt_bgsub_set_background_depth", [&]() -> int { return set_background_impl(bg, index, depth, intrin, true); });
+}
+
+int avt_bgsub_xyz_download(avt_bgsub* bg, int image, float* xyz_out) {
+    return avt_guard("avt_bgsub_xyz_download", [&]() -> int { return xyz_download_impl(bg, image, xyz_out); });
 }
 
 int avt_bgsub_sync(avt_bgsub* bg) {

@@ -11,11 +11,11 @@ from __future__ import annotations
 import numpy as np
 
 from . import api
+from .depth import CameraIntrin, intrin_array
 
 
-def subsample(xyz, part_mask, bbox, interval, num_parts):
-    """Every `interval`-th pixel of the bounding box (top, left, bottom, right; inclusive; None = the whole image) that carries a
-    body-part label (demo.cpp:216-250); y is negated (:245).  Returns (data_cloud (n,3) float64, labels (n,) int32)."""
+def _subsample(points_at, part_mask, bbox, interval, num_parts):
+    """The grid and the label checks of demo.cpp:216-250; `points_at(rows, cols, keep)` gives the kept pixels' (n,3) float32."""
     H, W = part_mask.shape
     top, left, bottom, right = bbox if bbox is not None else (0, 0, H - 1, W - 1)
     rows = np.arange(top, bottom + 1, interval)
@@ -24,9 +24,31 @@ def subsample(xyz, part_mask, bbox, interval, num_parts):
     keep = sub_mask != 255
     if (sub_mask[keep] >= num_parts).any():
         raise ValueError("body part prediction out of range (demo.cpp:236-243)")
-    pts = xyz[np.ix_(rows, cols)][keep].astype(np.float64)
+    pts = points_at(rows, cols, keep).astype(np.float64)
     pts[:, 1] = -pts[:, 1]
     return pts, sub_mask[keep].astype(np.int32)
+
+
+def subsample(xyz, part_mask, bbox, interval, num_parts):
+    """Every `interval`-th pixel of the bounding box (top, left, bottom, right; inclusive; None = the whole image) that carries a
+    body-part label (demo.cpp:216-250); y is negated (:245).  Returns (data_cloud (n,3) float64, labels (n,) int32)."""
+    return _subsample(lambda rows, cols, keep: xyz[np.ix_(rows, cols)][keep], part_mask, bbox, interval, num_parts)
+
+
+def subsample_depth(depth, intrin, part_mask, bbox, interval, num_parts):
+    """subsample() without an XYZ map: the three coordinates of the kept pixels alone, from the depth image (H,W) and the
+    camera by CameraIntrin::depthToXYZ's float32 expression (Calibration.cpp:91), so the result is exactly
+    subsample(depth.depth_to_xyz(depth, intrin), ...)."""
+    k = CameraIntrin.of(intrin)
+
+    def points_at(rows, cols, keep):
+        ri, ci = np.nonzero(keep)
+        r, c = rows[ri].astype(np.int32), cols[ci].astype(np.int32)
+        z = np.asarray(depth, np.float32)[r, c]
+        with np.errstate(all="ignore"):
+            return np.stack([(c.astype(np.float32) - k.cx) * z / k.fx, (r.astype(np.float32) - k.cy) * z / k.fy, z], 1).astype(np.float32)
+
+    return _subsample(points_at, part_mask, bbox, interval, num_parts)
 
 
 def frame_decision(tr, labels, num_parts):
@@ -83,7 +105,9 @@ class FrameTracker:
     def process(self, xyz, part_mask, bbox=None):
         """One tracked frame.  Returns True if the avatar was fitted, False if tracking was declared lost
         (too few body pixels: the next frame reinitialises, demo.cpp:225,283-285)."""
-        data, labels = self.subsample(xyz, part_mask, bbox)
+        return self._fit(*self.subsample(xyz, part_mask, bbox))
+
+    def _fit(self, data, labels):
         fit, icp_iters, reinit = frame_decision(self, labels, self.opt.numParts)
         if not fit:
             return False
@@ -97,10 +121,13 @@ class FrameTracker:
     def label(self, xyz, bbox):
         """Per-pixel body parts of a foreground XYZ map with the forest (demo.cpp:196-204): predictBest on the GPU at
         `rtree_interval` inside the bounding box, then postProcess.  bbox = (top, left, bottom, right) inclusive."""
+        return self.label_depth(np.ascontiguousarray(xyz[:, :, 2], np.float32), bbox)
+
+    def label_depth(self, depth, bbox):
+        """label() on the foreground depth image (H,W) itself."""
         if self.rtree is None:
             raise RuntimeError("FrameTracker.label: no RTree attached")
         top, left, bottom, right = bbox
-        depth = np.ascontiguousarray(xyz[:, :, 2], np.float32)
         mask = self.rtree.predictBest(depth, 0, self.rtreeInterval, (left, top), (right, bottom))
         self.comPre = self.rtree.postProcess(mask, self.comPre, self.rtreeInterval, 1, (left, top), (right, bottom), self.distToPreWeight)
         return mask
@@ -108,6 +135,13 @@ class FrameTracker:
     def process_depth(self, xyz, bbox):
         """One tracked frame from depth alone: label() then process()."""
         return self.process(xyz, self.label(xyz, bbox), bbox)
+
+    def process_depth_image(self, depth, intrin, bbox):
+        """process_depth() from the foreground depth image (H,W) float32 and its camera (a depth.CameraIntrin or fx, fy, cx, cy):
+        no XYZ map is built, the kept pixels alone are back-projected (subsample_depth)."""
+        depth = np.ascontiguousarray(depth, np.float32)
+        mask = self.label_depth(depth, bbox)
+        return self._fit(*subsample_depth(depth, intrin, mask, bbox, self.interval, self.opt.numParts))
 
 
 class _Stream:
@@ -174,9 +208,12 @@ class MultiFrameTracker:
         per-stream fitted flags (False: tracking lost, the stream's next fitted frame reinitialises)."""
         if len(frames) != self.S:
             raise ValueError(f"MultiFrameTracker.process: {len(frames)} frames for {self.S} streams")
+        return self._fit([subsample(xyz, mask, bbox, self.streams[s].interval, self.numParts) for s, (xyz, mask, bbox) in enumerate(frames)])
+
+    def _fit(self, clouds):
+        """process() behind the subsampling: `clouds` holds every stream's (data_cloud, labels)."""
         datas, labels, budgets, reinit, fitted = [], [], np.zeros(self.S, np.int32), [], []
-        for s, (xyz, mask, bbox) in enumerate(frames):
-            d, l = subsample(xyz, mask, bbox, self.streams[s].interval, self.numParts)
+        for s, (d, l) in enumerate(clouds):
             fit, icp_iters, re = frame_decision(self.streams[s], l, self.numParts)
             fitted.append(fit)
             if not fit:                               # nothing of a lost stream's frame is needed: it rides as an empty frame
@@ -220,15 +257,32 @@ class MultiFrameTracker:
         download of all labels and of the S boxes; postProcess per stream on the host (a sequential flood fill, as in the
         reference); then process() with the caller's XYZ.  A stream whose box is empty, or not inside the image, has an all-255
         mask: it goes through postProcess on the whole image (every comPre x becomes -1) and is lost in process()."""
-        if getattr(self, "bgsub", None) is None:
-            raise RuntimeError("MultiFrameTracker.process_depth: no front end attached (attach_front_end)")
-        if len(images) != self.S:
-            raise ValueError(f"MultiFrameTracker.process_depth: {len(images)} images for {self.S} streams")
+        self._front_end("process_depth", len(images))
         self.bgsub.upload(images)
+        return self.process([(images[s], mask, bbox) for s, (mask, bbox) in enumerate(self._label_resident())])
+
+    def process_depth_images(self, depths, intrins):
+        """process_depth() from S depth images (S, H, W) float32 and `intrins`, one camera for all streams or (S, 4) fx fy cx cy:
+        the depth is what crosses the bus, the XYZ maps are built on the device (BGSubtractor.upload_depth) and never come back;
+        the subsampling back-projects the kept pixels alone (subsample_depth)."""
+        self._front_end("process_depth_images", len(depths))
+        k = intrin_array(intrins, self.S)
+        self.bgsub.upload_depth(depths, k)
+        return self._fit([subsample_depth(depths[s], k[s], mask, bbox, self.streams[s].interval, self.numParts)
+                          for s, (mask, bbox) in enumerate(self._label_resident())])
+
+    def _front_end(self, who, n):
+        if getattr(self, "bgsub", None) is None:
+            raise RuntimeError(f"MultiFrameTracker.{who}: no front end attached (attach_front_end)")
+        if n != self.S:
+            raise ValueError(f"MultiFrameTracker.{who}: {n} images for {self.S} streams")
+
+    def _label_resident(self):
+        """The front end behind the upload, whatever its kind: per stream the post-processed part mask and the box to subsample."""
         self.bgsub.run_resident()
         self.rtree.predict_from_bgsub(self.bgsub, self.rtreeInterval)
         labels = self.rtree.download_all_labels()
-        frames = []
+        out = []
         for s in range(self.S):
             res = self.bgsub.info(s)
             tl, br = res.topLeft, res.botRight
@@ -240,9 +294,9 @@ class MultiFrameTracker:
             else:
                 self.comPre[s] = self.rtree.postProcess(labels[s], self.comPre[s], self.rtreeInterval, 1, (0, 0), (-1, -1), self.distToPreWeight)
                 bbox = (H - 1, W - 1, 0, 0)           # nothing to subsample
-            frames.append((images[s], labels[s], bbox))
+            out.append((labels[s], bbox))
         self.labels = labels                          # the step's post-processed part masks (S, H, W)
-        return self.process(frames)
+        return out
 
     def posed(self, stream):
         """(cloud (V,3), jointPos (J,3), jointTrans (J,12)) of the stream's last fit (one download; avt_get_posed)."""

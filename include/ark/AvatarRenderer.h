@@ -21,10 +21,6 @@
 
 namespace ark {
 
-struct Point2f {  // cv::Point2f stand-in
-    float x = 0.f, y = 0.f;
-};
-
 class AvatarRenderer {
 public:
     typedef std::pair<float, std::array<int, 3>> FaceType;

@@ -34,7 +34,19 @@ class FrameTracker {
      *  pixels; the next fitted frame reinitialises: live-demo.cpp:335-340, :379-383).  The decision: ark::frameDecision. */
     bool process(const float* xyz, const std::uint8_t* part_mask, int width, int height, const Rect& box) {
         (void)height;
-        const size_t cnz = subsample(xyz, part_mask, width, box, dataCloud, dataPartLabels);
+        return fit(subsample(xyz, part_mask, width, box, dataCloud, dataPartLabels));
+    }
+
+    /** process() on a depth image (height x width float) and its camera: no XYZ map is needed, the kept pixels alone are
+     *  back-projected (ark::subsampleFrameDepth). */
+    bool processDepthImage(const float* depth, const CameraIntrin& intrin, const std::uint8_t* part_mask, int width, int height, const Rect& box) {
+        (void)height;
+        return fit(subsampleFrameDepth(depth, intrin, part_mask, width, box, interval, avaOpt.numParts, dataCloud, dataPartLabels));
+    }
+
+   private:
+    /** process() behind the subsampling, on dataCloud / dataPartLabels */
+    bool fit(size_t cnz) {
         int icpIters = 0;
         bool reinitNow = false;
         if (!frameDecision(*this, dataPartLabels, cnz, avaOpt.numParts, icpIters, reinitNow)) return false;
@@ -46,6 +58,8 @@ class FrameTracker {
         ++framesFitted;
         return true;
     }
+
+   public:
 
     int interval = 12;            // demo.cpp:58   --data-interval
     int frameICPIters = 3;        // demo.cpp:63   --frame-icp-iters

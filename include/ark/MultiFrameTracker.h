@@ -9,7 +9,8 @@
 //
 // processDepth() puts the front end of demo.cpp:179-204 in front of a step for all streams at once: BGSubtractor::runBatch, then
 // RTree::predictBestFromBGSub on the masked depth where it lies on the device, one download of all labels, postProcess per stream
-// on the host (a sequential flood fill, as in the reference), then process() with the caller's XYZ maps.
+// on the host (a sequential flood fill, as in the reference), then process() with the caller's XYZ maps.  processDepthImages() is
+// the same from depth images and one camera per stream (BGSubtractor::runBatchDepth, ark::subsampleFrameDepth): no XYZ map on the host.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -54,6 +55,16 @@ class MultiFrameTracker {
     /** One step, one frame per stream.  fitted[s] = 1 if stream s was fitted, 0 if its tracking was declared lost. */
     void process(const std::vector<Frame>& frames, std::vector<int>& fitted) {
         if ((int)frames.size() != S) { std::fprintf(stderr, "MultiFrameTracker: %d frames for %d streams\n", (int)frames.size(), S); std::exit(1); }
+        fit([&](int s, int interval) {
+            const Frame& f = frames[(size_t)s];
+            return subsampleFrame(f.xyz, f.mask, f.width, f.box, interval, numParts, clouds[(size_t)s], labels[(size_t)s]);
+        }, fitted);
+    }
+
+   private:
+    /** process() around the subsampling: `subsampleStream(s, interval)` fills clouds[s], labels[s] and returns the point count */
+    template <class Sub>
+    void fit(Sub subsampleStream, std::vector<int>& fitted) {
         fitted.assign((size_t)S, 0);
         budgets.assign((size_t)S, 0);
         reinitStreams.clear();
@@ -61,8 +72,7 @@ class MultiFrameTracker {
         std::vector<double> wz((size_t)K, 0.0);
         for (int s = 0; s < S; ++s) {
             Stream& st = streams[(size_t)s];
-            cnz[(size_t)s] = subsampleFrame(frames[(size_t)s].xyz, frames[(size_t)s].mask, frames[(size_t)s].width, frames[(size_t)s].box, st.interval,
-                                            numParts, clouds[(size_t)s], labels[(size_t)s]);
+            cnz[(size_t)s] = subsampleStream(s, st.interval);
             int icp = 0;
             bool re = false;
             if (!frameDecision(st, labels[(size_t)s], cnz[(size_t)s], numParts, icp, re)) {
@@ -118,6 +128,8 @@ class MultiFrameTracker {
             if (fitted[(size_t)s]) { stats[(size_t)s] = st[(size_t)s]; ++streams[(size_t)s].framesFitted; }
     }
 
+   public:
+
     /** The front end of processDepth: a BGSubtractor holding one background per stream and a forest on the same device (both
      *  outlive the tracker's use of them); the interval of predictBest / postProcess (demo.cpp:198) and postProcess's weight. */
     void attachFrontEnd(BGSubtractor& bgsub, RTree& rtree, int rtree_interval = 2, double dist_to_pre_weight = 0.001) {
@@ -136,13 +148,39 @@ class MultiFrameTracker {
         if (!frontBG || !frontTree) { std::fprintf(stderr, "MultiFrameTracker::processDepth: no front end attached\n"); std::exit(1); }
         if ((int)images.size() != S) { std::fprintf(stderr, "MultiFrameTracker: %d images for %d streams\n", (int)images.size(), S); std::exit(1); }
         frontBG->runBatch(images);
-        partMasks = frontTree->predictBestFromBGSub(*frontBG, rtreeInterval);
+        const std::vector<Rect> box = labelBatch();
         std::vector<Frame> frames((size_t)S);
+        for (int s = 0; s < S; ++s) frames[(size_t)s] = {images[(size_t)s].data(), partMasks[(size_t)s].data(), partMasks[(size_t)s].cols, partMasks[(size_t)s].rows, box[(size_t)s]};
+        process(frames, fitted);
+    }
+
+    /** processDepth() from S depth images and their cameras (one per stream, or one for all): the depth is what is uploaded
+     *  (BGSubtractor::runBatchDepth), and the subsampling back-projects the kept pixels alone. */
+    void processDepthImages(const std::vector<ImageDepth>& depths, const std::vector<CameraIntrin>& intrins, std::vector<int>& fitted) {
+        if (!frontBG || !frontTree) { std::fprintf(stderr, "MultiFrameTracker::processDepthImages: no front end attached\n"); std::exit(1); }
+        if ((int)depths.size() != S || ((int)intrins.size() != S && intrins.size() != 1)) {
+            std::fprintf(stderr, "MultiFrameTracker: %d depth images, %d cameras for %d streams\n", (int)depths.size(), (int)intrins.size(), S);
+            std::exit(1);
+        }
+        frontBG->runBatchDepth(depths, intrins);
+        const std::vector<Rect> box = labelBatch();
+        fit([&](int s, int interval) {
+            return subsampleFrameDepth(depths[(size_t)s].data(), intrins[intrins.size() == 1 ? 0 : (size_t)s], partMasks[(size_t)s].data(),
+                                       partMasks[(size_t)s].cols, box[(size_t)s], interval, numParts, clouds[(size_t)s], labels[(size_t)s]);
+        }, fitted);
+    }
+
+   private:
+    /** The front end behind the batch run, whatever its source: labels on the device, postProcess per stream; fills partMasks and
+     *  boxes and returns every stream's box to subsample. */
+    std::vector<Rect> labelBatch() {
+        partMasks = frontTree->predictBestFromBGSub(*frontBG, rtreeInterval);
+        std::vector<Rect> out((size_t)S);
         for (int s = 0; s < S; ++s) {
             const BGSubtractor::BatchInfo b = frontBG->batchInfo(s);
             boxes[(size_t)s] = {b.topLeft.x, b.topLeft.y, b.botRight.x, b.botRight.y};
             Image8& m = partMasks[(size_t)s];
-            Rect box;
+            Rect& box = out[(size_t)s];
             if (0 <= b.topLeft.x && b.topLeft.x <= b.botRight.x && b.botRight.x < m.cols && 0 <= b.topLeft.y && b.topLeft.y <= b.botRight.y &&
                 b.botRight.y < m.rows) {
                 frontTree->postProcess(m, comPre[(size_t)s], rtreeInterval, 1, b.topLeft, b.botRight, distToPreWeight);
@@ -151,11 +189,11 @@ class MultiFrameTracker {
                 frontTree->postProcess(m, comPre[(size_t)s], rtreeInterval, 1, Point(0, 0), Point(-1, -1), distToPreWeight);
                 box.top = m.rows - 1; box.left = m.cols - 1; box.bottom = 0; box.right = 0;       // nothing to subsample
             }
-            frames[(size_t)s] = {images[(size_t)s].data(), m.data(), m.cols, m.rows, box};
         }
-        process(frames, fitted);
+        return out;
     }
 
+   public:
     /** ava.cloud (3 x V), jointPos (3 x J), jointTrans (12 x J) of stream s's last fit; any pointer may be null (avt_get_posed) */
     void posed(int s, double* cloud_3xV, double* joint_pos_3xJ = nullptr, double* joint_trans_12xJ = nullptr) {
         ARK_AVT_CHECK(avt_get_posed(ctx, s, cloud_3xV, joint_pos_3xJ, joint_trans_12xJ));

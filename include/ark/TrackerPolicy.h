@@ -13,10 +13,11 @@ namespace ark {
 
 struct TrackRect { int top = 0, left = 0, bottom = 0, right = 0; };   // inclusive, like bgsub.topLeft / botRight
 
-/** Every `interval`-th pixel of the box that carries a body-part label (demo.cpp:216-250); y negated (:245).  Returns the number
- *  of points; a label >= numParts is fatal exactly like demo.cpp:236-243. */
-inline size_t subsampleFrame(const float* xyz, const std::uint8_t* part_mask, int width, const TrackRect& box, int interval, int numParts,
-                             CloudType& dataCloud, VectorXi& dataPartLabels) {
+/** The grid walk of demo.cpp:216-250 behind subsampleFrame and subsampleFrameDepth: `point_at(r, c, out)` gives the three float
+ *  coordinates of a kept pixel. */
+template <class PointAt>
+size_t subsampleGrid(PointAt point_at, const std::uint8_t* part_mask, int width, const TrackRect& box, int interval, int numParts,
+                     CloudType& dataCloud, VectorXi& dataPartLabels) {
     size_t cnz = 0;
     for (int r = box.top; r <= box.bottom; r += interval) {
         const std::uint8_t* partptr = part_mask + (size_t)r * width;
@@ -26,7 +27,6 @@ inline size_t subsampleFrame(const float* xyz, const std::uint8_t* part_mask, in
     dataPartLabels.assign(cnz, 0);
     size_t i = 0;
     for (int r = box.top; r <= box.bottom; r += interval) {
-        const float* ptr = xyz + (size_t)r * width * 3;
         const std::uint8_t* partptr = part_mask + (size_t)r * width;
         for (int c = box.left; c <= box.right; c += interval) {
             if (partptr[c] == 255) continue;
@@ -34,14 +34,32 @@ inline size_t subsampleFrame(const float* xyz, const std::uint8_t* part_mask, in
                 std::fprintf(stderr, "FATAL: body part prediction %d is invalid, since there are only %d body parts\n", (int)partptr[c], numParts);
                 std::exit(1);
             }
-            dataCloud(0, i) = ptr[3 * c];
-            dataCloud(1, i) = -ptr[3 * c + 1];
-            dataCloud(2, i) = ptr[3 * c + 2];
+            float pt[3];
+            point_at(r, c, pt);
+            dataCloud(0, i) = pt[0];
+            dataCloud(1, i) = -pt[1];
+            dataCloud(2, i) = pt[2];
             dataPartLabels[i] = partptr[c];
             ++i;
         }
     }
     return cnz;
+}
+
+/** Every `interval`-th pixel of the box that carries a body-part label (demo.cpp:216-250); y negated (:245).  Returns the number
+ *  of points; a label >= numParts is fatal exactly like demo.cpp:236-243. */
+inline size_t subsampleFrame(const float* xyz, const std::uint8_t* part_mask, int width, const TrackRect& box, int interval, int numParts,
+                             CloudType& dataCloud, VectorXi& dataPartLabels) {
+    return subsampleGrid([&](int r, int c, float* out) { const float* p = xyz + ((size_t)r * width + c) * 3; out[0] = p[0]; out[1] = p[1]; out[2] = p[2]; },
+                         part_mask, width, box, interval, numParts, dataCloud, dataPartLabels);
+}
+
+/** subsampleFrame without an XYZ map: the kept pixels alone are back-projected from the depth image (height x width float) by
+ *  CameraIntrin::depthToXYZ's expression, so the result is subsampleFrame's on intrin.depthToXYZ(depth), bit for bit. */
+inline size_t subsampleFrameDepth(const float* depth, const CameraIntrin& intrin, const std::uint8_t* part_mask, int width, const TrackRect& box,
+                                  int interval, int numParts, CloudType& dataCloud, VectorXi& dataPartLabels) {
+    return subsampleGrid([&](int r, int c, float* out) { intrin.pixelToXYZ(r, c, depth[(size_t)r * width + c], out); },
+                         part_mask, width, box, interval, numParts, dataCloud, dataPartLabels);
 }
 
 /** The decision of one stream on its subsampled frame.  `T` carries the stream's policy and state under FrameTracker's member names

@@ -96,9 +96,67 @@ struct Size {  // cv::Size stand-in
     Size(int w, int h) : width(w), height(h) {}
 };
 
-struct CameraIntrin {  // Calibration.h:11-77: API-surface type only, does not influence optimize() (AvatarOptimizer.cpp:1271)
+struct Point2f {  // cv::Point2f stand-in
+    float x = 0.f, y = 0.f;
+    Point2f() {}
+    Point2f(float x_, float y_) : x(x_), y(y_) {}
+};
+using Vec3f = std::array<float, 3>;  // cv::Vec3f stand-in
+
+struct ImageDepth {  // row-major rows x cols float32, the layout of a continuous CV_32FC1 cv::Mat: a depth image, metres, 0 = nothing
+    int rows = 0, cols = 0;
+    std::vector<float> a;
+    ImageDepth() {}
+    ImageDepth(int r, int c, float fill = 0.f) : rows(r), cols(c), a((size_t)r * c, fill) {}
+    float& at(int r, int c) { return a[(size_t)r * cols + c]; }
+    float at(int r, int c) const { return a[(size_t)r * cols + c]; }
+    float* data() { return a.data(); }
+    const float* data() const { return a.data(); }
+    bool empty() const { return a.empty(); }
+};
+
+struct ImageXYZ {  // row-major rows x cols x 3 float32, the layout of a continuous CV_32FC3 cv::Mat (cv::Vec3f per pixel)
+    int rows = 0, cols = 0;
+    std::vector<float> a;
+    ImageXYZ() {}
+    ImageXYZ(int r, int c, float fill = 0.f) : rows(r), cols(c), a((size_t)r * c * 3, fill) {}
+    float* at(int r, int c) { return a.data() + ((size_t)r * cols + c) * 3; }
+    const float* at(int r, int c) const { return a.data() + ((size_t)r * cols + c) * 3; }
+    float* data() { return a.data(); }
+    const float* data() const { return a.data(); }
+    bool empty() const { return a.empty(); }
+};
+
+struct CameraIntrin {  // Calibration.h:11-77; does not influence optimize() (AvatarOptimizer.cpp:1271).  k[], p[] are carried, never read
     float fx = 606.438f, fy = 606.351f, cx = 637.294f, cy = 366.992f;
     float k[6] = {0, 0, 0, 0, 0, 0}, p[2] = {0, 0};
+
+    // The three members below are float32 in the reference's expression order (int column to float, minus cx, times z, over fx;
+    // no reciprocal, nothing fused, no double): avt_bgsub.hip's k_bgs_backproject and avatar_amd/depth.py give the same bits.
+    /** Calibration.cpp:68-74 */
+    Vec3f to3D(const Point2f& point, float depth) const {
+        return Vec3f{(point.x - cx) * depth / fx, (point.y - cy) * depth / fy, depth};
+    }
+    /** Calibration.cpp:76-80 */
+    Point2f to2D(const Vec3f& point) const {
+        return Point2f(point[0] * fx / point[2] + cx, point[1] * fy / point[2] + cy);
+    }
+    /** Calibration.cpp:82-95 */
+    ImageXYZ depthToXYZ(const ImageDepth& depth) const {
+        ImageXYZ xyz_map(depth.rows, depth.cols);
+        for (int r = 0; r < depth.rows; ++r) {
+            const float* inPtr = depth.data() + (size_t)r * depth.cols;
+            float* outPtr = xyz_map.data() + (size_t)r * depth.cols * 3;
+            for (int c = 0; c < depth.cols; ++c) pixelToXYZ(r, c, inPtr[c], outPtr + 3 * c);
+        }
+        return xyz_map;
+    }
+    /** One pixel of depthToXYZ (:91): out[3] = (c - cx) * z / fx, (r - cy) * z / fy, z */
+    void pixelToXYZ(int r, int c, float z, float* out) const {
+        out[0] = ((float)c - cx) * z / fx;
+        out[1] = ((float)r - cy) * z / fy;
+        out[2] = z;
+    }
 };
 
 // Eigen 3.3 closed forms used by optimize() to move between rotation matrices and quaternions

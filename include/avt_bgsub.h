@@ -69,6 +69,31 @@ int avt_bgsub_run_resident(avt_bgsub* bg, float nn_rel, float neighb_rel);
 int avt_bgsub_download(avt_bgsub* bg, int image, unsigned char* mask_out, float* masked_depth_out, avt_bgsub_frame* info);
 int avt_bgsub_sync(avt_bgsub* bg);
 
+/* Depth images in: the recorded-data path of the reference never receives an XYZ map, it reads a one-channel depth image
+ * (util::readDepth, Util.cpp:176-209; demo.cpp:126,166) and expands it with CameraIntrin::depthToXYZ
+ * (Calibration.cpp:82-95).  These entries take the depth image (row-major rows x cols float32) and a camera
+ * {fx, fy, cx, cy}, upload a third of the bytes and expand on the device, bit for bit depthToXYZ's float expression
+ *   x = ((float)c - cx) * z / fx,  y = ((float)r - cy) * z / fy,  z = z
+ * (IEEE division, nothing fused, denormals kept, nothing clamped or validated: a zero, negative, infinite or NaN depth
+ * or fx == 0 gives what IEEE gives).  Everything after the expansion is the XYZ path's.
+ *
+ * avt_bgsub_depth_upload is avt_bgsub_images_upload with depth images (n x rows x cols) and one camera per image
+ * (intrin n x 4): same argument checks, same bg_index / prev_boxes, same end state (avt_bgsub_run_resident next).  The
+ * depth is staged in the buffer of the run's masked depth, which holds nothing anyone may read between an upload and the
+ * next run (a reader on another stream is waited for first, as before any upload).
+ * avt_bgsub_run_depth is avt_bgsub_run on one depth image (intrin 4 floats).
+ * avt_bgsub_set_background_depth is avt_bgsub_set_background (live-demo.cpp:207) from a depth image; it is staged in the
+ * run's label scratch (dead between runs), not in the masked depth: the last run's result stays downloadable across a
+ * change of background, as it does for an XYZ one.  It also overwrites the first camera of the last depth upload, which
+ * nothing reads any more: that upload's expansion was queued by the upload itself, in front of this call.
+ * avt_bgsub_xyz_download copies the resident XYZ map of image `image` out (rows x cols x 3), after either kind of upload:
+ * for a caller who wants the map itself (a display, readXYZ's result, Util.cpp:211-217). */
+int avt_bgsub_depth_upload(avt_bgsub* bg, int n_images, const float* depth, const float* intrin, const int* bg_index, const int* prev_boxes);
+int avt_bgsub_run_depth(avt_bgsub* bg, int background_index, const float* depth, const float* intrin, float nn_rel, float neighb_rel,
+                        unsigned char* mask_out, float* masked_depth_out, avt_bgsub_frame* info);
+int avt_bgsub_set_background_depth(avt_bgsub* bg, int index, const float* depth, const float* intrin);
+int avt_bgsub_xyz_download(avt_bgsub* bg, int image, float* xyz_out);
+
 #ifdef __cplusplus
 }
 #endif
