@@ -160,7 +160,8 @@ class ModelArrays:
         self.parent = np.asarray(smpl["kintree_table"])[0].astype(np.int32).copy()
         self.parent[0] = -1                                                       # SMPL stores 2^32-1 for the root
         self.mesh = np.ascontiguousarray(f.astype(np.int32))                      # (F,3) rows == 3xF col-major
-        W = sp.csc_matrix(np.asarray(smpl["weights"], dtype=np.float64).T)        # J x V (sparseView, :67-71)
+        wt = smpl["weights"]        # (a scipy.sparse V x J matrix is taken entry by entry: a stored 0.0 stays a stored entry of the column)
+        W = sp.csc_matrix(wt.T.astype(np.float64) if sp.issparse(wt) else np.asarray(wt, dtype=np.float64).T)   # J x V (sparseView, :67-71)
         W.sort_indices()
         self.w_colptr = W.indptr.astype(np.int32); self.w_row = W.indices.astype(np.int32)
         self.w_val = W.data.astype(np.float64)

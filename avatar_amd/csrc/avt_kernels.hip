@@ -483,7 +483,8 @@ void launch_visibility(avt_ctx* c, int nframes, int enable, bool with_bucket_sca
         c->scatter_in_compact = with_bucket_scatter;
     } else if (enable) {
         const int nvis = (c->dm.d.F + 255) / 256;
-        hipLaunchKernelGGL(k_visibility, dim3(nvis + nb, nframes), dim3(256), 0, c->cur_stream, c->dm, c->fb, nvis);
+        // (a model without faces, F = 0, has no workgroup to launch outside the first ICP iteration: the cleared flags stand)
+        if (nvis + nb > 0) hipLaunchKernelGGL(k_visibility, dim3(nvis + nb, nframes), dim3(256), 0, c->cur_stream, c->dm, c->fb, nvis);
     } else if (nb) {
         hipLaunchKernelGGL(k_bucket_scatter, dim3(nb, nframes), dim3(256), 0, c->cur_stream, c->dm, c->fb);
     }
