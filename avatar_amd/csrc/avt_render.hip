@@ -252,17 +252,28 @@ __global__ __launch_bounds__(256) void k_paint_keys(DeviceModel dm, FrameBuffers
     fedge[(size_t)fl * F + face] = fabs(n[2]) < 0.1 ? 1 : 0;
 }
 
+// a sort key as 32 bits whose ascending unsigned order is the painter's order (decreasing float): -0 folded onto +0, which
+// compare equal; sign-fold (ascending unsigned = ascending float), complement.  A total order on every bit pattern, so NaN keys
+// have a place too, where the reference's std::sort is undefined: positive NaN before +inf, negative NaN
+// after -inf.  k_paint_rank and k_rend_sort both order by it.
+__device__ __forceinline__ unsigned painter_key_bits(float k) {
+    unsigned u = __float_as_uint(k == 0.0f ? 0.0f : k);
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ~u;
+}
+
 // position of every face in the painter's order = number of faces painted before it: those with a larger key, and those
-// with an equal key and a smaller face id.  All lanes read the same key at the same time (scalar loads), 13 776 steps.
+// with an equal key and a smaller face id (keys compared as painter_key_bits: the float order on every key that is not NaN).
+// All lanes read the same key at the same time (scalar loads), 13 776 steps.
 __global__ __launch_bounds__(256) void k_paint_rank(int F, const float* __restrict__ fkey, int* __restrict__ frank) {
     const int fl = blockIdx.y;
     const int face = blockIdx.x * 256 + threadIdx.x;
     const float* key = fkey + (size_t)fl * F;
-    const float mine = face < F ? key[face] : 0.f;
+    const unsigned mine = painter_key_bits(face < F ? key[face] : 0.f);
     int before = 0;
     for (int g = 0; g < F; ++g) {
-        const float k = key[g];
-        before += (k > mine || (k == mine && g < face)) ? 1 : 0;
+        const unsigned k = painter_key_bits(key[g]);
+        before += (k < mine || (k == mine && g < face)) ? 1 : 0;
     }
     if (face < F) frank[(size_t)fl * F + face] = before;
 }
@@ -503,12 +514,7 @@ __global__ __launch_bounds__(1024) void k_rend_sort(int F, const float* __restri
     const float* key = fkey + (size_t)img * F;
     for (int i = t; i < P; i += 1024) {
         unsigned long long v = ~0ull;
-        if (i < F) {
-            const float k = key[i];
-            unsigned u = __float_as_uint(k == 0.0f ? 0.0f : k);
-            u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);           // ascending unsigned = ascending float
-            v = ((unsigned long long)(~u) << 32) | (unsigned)i;        // complemented: descending float
-        }
+        if (i < F) v = ((unsigned long long)painter_key_bits(key[i]) << 32) | (unsigned)i;
         s[i] = v;
     }
     __syncthreads();

@@ -270,12 +270,7 @@ HAND_MESHES = {
 }
 
 
-def _tiny_model(cloud, mesh):
-    """a one-joint, one-shape-key model whose rest pose is `cloud` (the renderer only needs the mesh and the vertex -> joint map)"""
-    from avatar_amd import api
-    V = len(cloud)
-    return api.AvatarModel(dict(v_template=np.asarray(cloud, np.float64), f=np.asarray(mesh, np.int32), kintree_table=np.array([[-1], [0]]),
-                                J_regressor=np.full((1, V), 1.0 / V), weights=np.ones((V, 1)), shapedirs=np.zeros((V, 3, 1))))
+from avatar_render_cases import tiny_model as _tiny_model      # the one-joint model recipe, shared with the edge cases
 
 
 @pytest.mark.parametrize("name", list(HAND_MESHES))
