@@ -205,6 +205,7 @@ int train(avt_rtree_trainer* tr, int part_map_len, const int* part_map, int part
         levels.push_back(std::move(hn));
         sx.level_nodes[L] = M;
         sx.level_searched[L] = (int)list.size();
+        sx.level_large[L] = nl;
         sx.level_evals[L] = evals;
         sx.level_ms[L] = ms_since(t_level);
         sx.n_levels = L + 1;
@@ -359,6 +360,19 @@ int avt_rtree_trainer_create(int device, const avt_rtree_train_params* p, avt_rt
             return 1;
         }
         AVT_HIP(hipSetDevice(device));
+        // k_rt_search's dynamic LDS: decided here, so that no accepted parameter set fails in run().  The attribute is raised to
+        // the largest request the check above admits (P = 1, T = 8192 in the 256-thread form), or to the device's limit if lower.
+        int lds_limit = 0;
+        AVT_HIP(hipDeviceGetAttribute(&lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
+        size_t lds_most = 0;
+        for (int q = 1; q <= 127; ++q) lds_most = std::max(lds_most, rt_search_lds_bytes(q, 8192 / q, true));
+        const size_t lds_need = rt_search_lds_bytes(p->num_parts, p->min_samples_per_feature, true);
+        if (lds_need > (size_t)lds_limit || rt_search_set_attributes(std::min(lds_most, (size_t)lds_limit))) {
+            (void)hipGetLastError();
+            avt_set_error("avt_rtree_trainer_create: num_parts x T = " + std::to_string(p->num_parts) + " x " + std::to_string(p->min_samples_per_feature) +
+                          " needs " + std::to_string(lds_need) + " bytes of LDS per workgroup, the device grants " + std::to_string(lds_limit));
+            return 1;
+        }
         avt_rtree_trainer* tr = new avt_rtree_trainer();
         tr->device = device;
         tr->p = *p;

@@ -58,6 +58,7 @@ int rt_launch_partition(hipStream_t s, const int* list, int nlist, const RtNode*
 int rt_launch_transfer(hipStream_t s, const RtNodeDev* nodes, const float* depth, const unsigned char* mask, int n, int rows, int cols, int P,
                        unsigned long long* counts, int* bad);
 size_t rt_search_lds_bytes(int P, int T, bool large);
+int rt_search_set_attributes(size_t bytes);
 
 // the last run's depth and part-mask images of a renderer, visible to `s` after the renderer's queued work (avt_render.hip)
 int avt_renderer_images_for(avt_renderer* r, hipStream_t s, const float** depth, const unsigned char** mask, int* n, int* width, int* height);

@@ -211,6 +211,7 @@ __global__ __launch_bounds__(BS) void k_rt_search(const int* __restrict__ list, 
         if (tap_hist) {                                   // avt_rtree_trainer_root_histograms: the integer histogram as counted
             for (int j = tid; j < P * T; j += BS) tap_hist[(size_t)f * P * T + j] = hist[j];
             if (tid == 0) { tap_minmax[2 * f] = mn; tap_minmax[2 * f + 1] = mx; }
+            __syncthreads();                              // the rows are summed in place below: every wave's copy is done first
         }
         for (int k = tid; k < npres; k += BS) {
             int* h = hist + plist[k] * T;
@@ -342,6 +343,11 @@ int rt_launch_count(hipStream_t s, const RtNode* nodes, int m, const unsigned ch
     return rt_ok();
 }
 size_t rt_search_lds_bytes(int P, int T, bool large) { return 4 * rt_search_lds_ints(P, T, large ? 256 : 64); }
+// both forms of k_rt_search may be launched with up to `bytes` of dynamic LDS (above 64 KiB for three of the accepted shapes)
+int rt_search_set_attributes(size_t bytes) {
+    return hipFuncSetAttribute((const void*)k_rt_search<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess ||
+           hipFuncSetAttribute((const void*)k_rt_search<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess;
+}
 int rt_launch_search(hipStream_t s, bool large, const int* list, int nlist, int nchunks, int fchunk, const RtNode* nodes, const int* counts, RtSamples in,
                      const RtImg* imgs, const float* store, RtTrainArgs a, RtChunk* out, int* tap_hist, float* tap_minmax) {
     const unsigned grid = (unsigned)nlist * (unsigned)nchunks;

@@ -39,13 +39,13 @@ class TrainParams(C.Structure):
 class TrainStats(C.Structure):
     _fields_ = [("n_nodes", C.c_int), ("n_leafs", C.c_int), ("n_levels", C.c_int), ("n_images", C.c_int), ("n_samples", C.c_longlong),
                 ("total_ms", C.c_double), ("level_nodes", C.c_int * MAX_DEPTH), ("level_searched", C.c_int * MAX_DEPTH),
-                ("level_evals", C.c_longlong * MAX_DEPTH), ("level_ms", C.c_double * MAX_DEPTH)]
+                ("level_evals", C.c_longlong * MAX_DEPTH), ("level_ms", C.c_double * MAX_DEPTH), ("level_large", C.c_int * MAX_DEPTH)]
 
     def as_dict(self):
         L = self.n_levels
         return dict(n_nodes=self.n_nodes, n_leafs=self.n_leafs, n_levels=L, n_images=self.n_images, n_samples=self.n_samples,
                     total_ms=self.total_ms, level_nodes=list(self.level_nodes[:L]), level_searched=list(self.level_searched[:L]),
-                    level_evals=list(self.level_evals[:L]), level_ms=list(self.level_ms[:L]))
+                    level_evals=list(self.level_evals[:L]), level_ms=list(self.level_ms[:L]), level_large=list(self.level_large[:L]))
 
 
 def _images(depth, part_mask):

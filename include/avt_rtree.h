@@ -6,7 +6,10 @@
  *
  * Conventions: images are row-major, depth is float32 metres with 0 = background (demo.cpp:185-191), labels are
  * uint8 with 255 = none; a region of interest is (top_left, bot_right) inclusive, bot_right.x == -1 means the whole
- * image (RTree.cpp:3190-3193).  Functions return 0 on success; avt_last_error() (avt.h) describes a failure.
+ * image (RTree.cpp:3190-3193).  A probe offset / depth that leaves int32 (a tiny, subnormal or infinite quotient) lands
+ * outside the image and reads the background depth, as the reference's conversion does; a NaN depth is outside the
+ * contract: the reference's conversion of a NaN quotient to int is undefined.  Functions return 0 on success;
+ * avt_last_error() (avt.h) describes a failure.
  */
 #ifndef AVT_RTREE_H_
 #define AVT_RTREE_H_

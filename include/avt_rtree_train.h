@@ -29,7 +29,9 @@
  *               zero depth both read BACKGROUND_DEPTH); a sample's own depth is read from the full image.
  * Parameters of the reference's trainers that do not change V3's result (num_threads, num_features_filtered,
  * frac_samples_per_feature, threshes_per_feature, max_images_loaded, mem_limit_mb, train_partial_save_path) have no
- * counterpart here.  num_parts x min_samples_per_feature is limited to 8192 (the bucket histogram lives in LDS).
+ * counterpart here.  num_parts x min_samples_per_feature is limited to 8192 (the bucket histogram lives in LDS: up to
+ * 131 128 bytes per workgroup, asked of the device in avt_rtree_trainer_create, which refuses a parameter set whose
+ * LDS the device cannot give; an accepted one never fails for it in avt_rtree_trainer_run).
  *
  * Functions return 0 on success; avt_last_error() (avt.h) describes a failure.
  */
@@ -69,6 +71,8 @@ typedef struct avt_rtree_train_stats {
     int level_searched[AVT_RTREE_TRAIN_MAX_DEPTH];     /* ... of which searched for a split                          */
     long long level_evals[AVT_RTREE_TRAIN_MAX_DEPTH];  /* feature evaluations: sum over searched nodes of n x F      */
     double level_ms[AVT_RTREE_TRAIN_MAX_DEPTH];        /* wall clock of the level, host wait included                */
+    int level_large[AVT_RTREE_TRAIN_MAX_DEPTH];        /* searched nodes of >= 2048 samples: one 256-thread workgroup */
+                                                       /* per (node, chunk of features) instead of one wave          */
 } avt_rtree_train_stats;
 
 /* ---- the random draws, bit for bit (a restatement reproduces them from this text) ----------------------------------

@@ -101,6 +101,9 @@ struct Trainer {
     const float* dev_feature = nullptr;
     const int* dev_links = nullptr;
     int ties = 0;
+    // nodes at which two gains that are not bit-equal lie within 1e-12 relative - the best feature's and another feature's, or the
+    // best and another threshold of the chosen feature - counted from this restatement alone: `ties` can never exceed it
+    int near = 0;
 
     void choose_samples() {
         for (int i = 0; i < (int)imgs.size(); ++i) {
@@ -186,6 +189,18 @@ struct Trainer {
             else if (gains[f] > g2) g2 = gains[f];
         }
         if (bf < 0) { make_leaf(id, start, end); return; }       // no feature with a valid threshold: the split would be empty
+        {
+            auto close = [&](double g) { return g != bg && std::fabs(bg - g) <= 1e-12 * std::fabs(bg); };
+            bool nt = false;
+            for (int f = 0; f < F && !nt; ++f) nt = f != bf && close(gains[f]);
+            if (!nt) {
+                std::vector<double> all;
+                float t0;
+                info_gain(start, end, feat(key, bf), &t0, &all);
+                for (double g : all) nt = nt || close(g);          // NaN (an empty side) compares false
+            }
+            near += nt;
+        }
         if (dev_feature && id < dev_n && dev_links[3 * (size_t)id + 2] < 0 && std::isfinite(g2) && std::fabs(bg - g2) <= 1e-12 * std::fabs(bg)) {
             // near tie: the device's log2 may be one ulp away from glibc's; take the device's choice among the tied features
             for (int f = 0; f < F; ++f) {
@@ -236,7 +251,7 @@ struct Result {
     std::vector<Sample> samples;
     std::vector<float> feature, leaf;
     std::vector<int> links;
-    int ties = 0;
+    int ties = 0, near = 0;
 };
 
 }  // namespace
@@ -255,7 +270,7 @@ void* rst_train(int n, int rows, int cols, const float* depth, const unsigned ch
         t.new_node();
         t.node(0, 1, 0, t.samples.size(), max_depth);
     }
-    r->feature = t.feature; r->links = t.links; r->leaf = t.leaf; r->ties = t.ties;
+    r->feature = t.feature; r->links = t.links; r->leaf = t.leaf; r->ties = t.ties; r->near = t.near;
     return r;
 }
 
@@ -278,6 +293,8 @@ void rst_get(void* h, int* img, int* x, int* y, unsigned char* label, float* fea
     std::copy(r->links.begin(), r->links.end(), links);
     std::copy(r->leaf.begin(), r->leaf.end(), leaf);
 }
+
+int rst_near(void* h) { return ((Result*)h)->near; }
 
 void rst_free(void* h) { delete (Result*)h; }
 

@@ -26,6 +26,8 @@ def lib():
                                 C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
         L.rst_sizes.argtypes = [C.c_void_p] + [C.c_void_p] * 4
         L.rst_get.argtypes = [C.c_void_p] + [C.c_void_p] * 7
+        L.rst_near.restype = C.c_int
+        L.rst_near.argtypes = [C.c_void_p]
         L.rst_free.argtypes = [C.c_void_p]
         L.rst_transfer.restype = C.c_int
         L.rst_transfer.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
@@ -49,7 +51,8 @@ def _ptr(a):
 
 def train(depth, mask, num_parts, num_points_per_image, num_features, max_probe_offset, min_samples, max_tree_depth, T, seed,
           nthreads=1, device_tree=None, train=True):
-    """dict: samples (img, x, y, label), feature (n,5), links (n,3), leaf (nl,P), ties (near ties that took the device's choice).
+    """dict: samples (img, x, y, label), feature (n,5), links (n,3), leaf (nl,P), ties (near ties that took the device's choice),
+    near (nodes with two gains that are not bit-equal within 1e-12 relative, counted without a device tree: ties <= near).
     device_tree: (feature, links) of the GPU's tree; at a node whose two best gains (of two features, or of two thresholds of the
     chosen feature) lie within 1e-12 relative, the restatement takes the device's choice."""
     d = np.ascontiguousarray(depth, np.float32)
@@ -70,6 +73,7 @@ def train(depth, mask, num_parts, num_points_per_image, num_features, max_probe_
                feature=np.empty((nn.value, 5), np.float32), links=np.empty((nn.value, 3), np.int32),
                leaf=np.empty((nl.value, num_parts), np.float32), ties=ties.value)
     L.rst_get(h, *(_ptr(out[k]) for k in ("img", "x", "y", "label", "feature", "links", "leaf")))
+    out["near"] = L.rst_near(h)
     L.rst_free(h)
     return out
 
