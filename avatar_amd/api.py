@@ -222,6 +222,18 @@ def load_model_dir(path):
     return m
 
 
+def intrin_tuple(intrin):
+    """(fx, fy, cx, cy) of a dict with those keys, an object with those attributes (depth.CameraIntrin) or four numbers."""
+    if isinstance(intrin, dict):
+        return tuple(float(intrin[k]) for k in ("fx", "fy", "cx", "cy"))
+    if hasattr(intrin, "fx"):
+        return float(intrin.fx), float(intrin.fy), float(intrin.cx), float(intrin.cy)
+    k = tuple(float(v) for v in intrin)
+    if len(k) != 4:
+        raise ValueError("intrinsics must be fx, fy, cx, cy")
+    return k
+
+
 class Context:
     """One HIP device + stream + persistent buffers (avt_ctx)."""
 
@@ -262,6 +274,24 @@ class Context:
         cloud = np.ascontiguousarray(cloud, np.float64)
         vis = np.empty(self.model.numPoints(), np.uint8)
         check(self._lib.avt_visibility(self.h, dptr(cloud), C.c_int(int(enable)), bptr(vis)))
+        return vis
+
+    def set_occlusion_render(self, image_size=None, intrin=None):
+        """avt_set_occlusion_render: self-occlusion visibility from a face-id render at `image_size` (width, height) and `intrin`
+        (a dict with fx, fy, cx, cy, a depth.CameraIntrin, or the four numbers); image_size None turns the mode off."""
+        if image_size is None:
+            w = h = 0; k = (0.0, 0.0, 0.0, 0.0)
+        else:
+            w, h = int(image_size[0]), int(image_size[1])
+            if intrin is None:
+                raise ValueError("set_occlusion_render: a camera is needed with an image size")
+            k = intrin_tuple(intrin)
+        check(self._lib.avt_set_occlusion_render(self.h, C.c_int(w), C.c_int(h), *[C.c_float(float(v)) for v in k]))
+
+    def get_visibility(self, frame=0):
+        """The visibility flags (V,) uint8 of the last ICP iteration the last optimize call ran on `frame`."""
+        vis = np.empty(self.model.numPoints(), np.uint8)
+        check(self._lib.avt_get_visibility(self.h, C.c_int(frame), bptr(vis)))
         return vis
 
     def nn(self, model_cloud, visible, data, labels):
@@ -578,9 +608,12 @@ class Avatar:
 
 
 class AvatarOptimizer:
-    """`class AvatarOptimizer` (AvatarOptimizer.h:11-61).  `intrin` and `image_size` are accepted for signature
-    parity; they do not influence optimize() in the reference either (renderer unused, AvatarOptimizer.cpp:1271,
-    :1369-1385)."""
+    """`class AvatarOptimizer` (AvatarOptimizer.h:11-61).  `intrin` and `image_size` (width, height) do not influence optimize() in
+    the reference (renderer unused, AvatarOptimizer.cpp:1271, :1369-1385); here they are the camera of `renderOcclusion`.
+
+    renderOcclusion (default False) is NOT a reference member: with enableOcclusion it adds to the back-face test the face-id
+    render the reference left commented out at AvatarOptimizer.cpp:1369-1385 (avt_set_occlusion_render, include/avt.h: a vertex
+    is visible iff one of its front-facing faces owns a pixel of renderFaces at intrin / imageSize)."""
 
     ROT_SIZE = 4
 
@@ -594,6 +627,8 @@ class AvatarOptimizer:
         self.nnStep = 20                                   # :33
         self.maxItersPerICP = 10                           # :36
         self.enableOcclusion = True                        # :39
+        self.renderOcclusion = False                       # not a reference member (:1369-1385, commented out there)
+        self._occ_applied = None                           # what the context was last told (avt_set_occlusion_render)
         self.functionTolerance = 1e-4                      # not a member of the reference's class: what its optimize() hard-codes at AvatarOptimizer.cpp:1333 (0 = no early exit)
         self.r = np.zeros((J, 4)); self.r[:, 3] = 1.0      # quaternions (x,y,z,w), :25
         self.ctx = Context(ava.model, self.numParts, self.partMap, max_points, 1)
@@ -607,8 +642,19 @@ class AvatarOptimizer:
         o.function_tolerance = self.functionTolerance
         return o
 
+    def _apply_render_occlusion(self):
+        want = None
+        if self.renderOcclusion:
+            if self.intrin is None or self.imageSize is None:
+                raise ValueError("AvatarOptimizer.renderOcclusion needs the intrin and image_size the optimizer was made with")
+            want = (tuple(int(v) for v in self.imageSize), intrin_tuple(self.intrin))
+        if want != self._occ_applied:
+            self.ctx.set_occlusion_render(*(want if want else (None, None)))
+            self._occ_applied = want
+
     def optimize(self, data_cloud, data_part_labels, icp_iters=1, num_threads=4):
         ava = self.ava
+        self._apply_render_occlusion()
         self.r = rot_to_quat(ava.r)                                              # :1250-1254
         if icp_iters >= 1:      # one call, one synchronisation: the fit and the outputs of the update() the launch sequence ends with (:1497)
             ava.p, self.r, ava.w, self.last_stats, ava.cloud, ava.jointPos, ava.jointTrans = self.ctx.optimize_posed(

@@ -310,9 +310,9 @@ int run_optimize(avt_ctx* c, const avt_options* o, const int* budget = nullptr) 
     // hip::GraphExec::Run, which rearranges a per-device set of helper streams for graphs with parallel branches).  The calls
     // only enqueue, so the lock is held for microseconds.
     std::lock_guard<std::mutex> graph_lock(g_graph_mutex);
-    char key[160];
-    snprintf(key, sizeof key, "%d|%d|%d|%d|%d|%d|%d|%d%s", nf, ngroups, c->fb.G, c->launch_maxN, o->icp_iters, o->max_iters_per_icp, o->enable_occlusion, c->fb.use_moments,
-             budget ? "|budgets" : "");      // (the budgets themselves live in device memory: a changing pattern replays the same graph)
+    char key[200];
+    snprintf(key, sizeof key, "%d|%d|%d|%d|%d|%d|%d|%d|%dx%d%s", nf, ngroups, c->fb.G, c->launch_maxN, o->icp_iters, o->max_iters_per_icp, o->enable_occlusion, c->fb.use_moments,
+             c->occ_w, c->occ_w > 0 ? c->occ_h : 0, budget ? "|budgets" : "");      // (the budgets themselves live in device memory: a changing pattern replays the same graph)
     avt_ctx::GraphEntry* hit = nullptr;
     for (auto& e : c->graphs) if (e.key == key) { hit = &e; break; }
     if (!hit) {
@@ -1212,6 +1212,48 @@ int avt_set_data_term(avt_ctx* c, int form) {
 }
 
 int avt_get_data_term(avt_ctx* c) { return c ? c->data_term : -1; }
+
+int avt_set_occlusion_render(avt_ctx* c, int width, int height, float fx, float fy, float cx, float cy) {
+    return avt_guard("avt_set_occlusion_render", [&]() -> int {
+        if (!c) { avt_set_error("avt_set_occlusion_render: null context"); return 1; }
+        if (width != 0 && (width < 0 || height <= 0 || width >= 65536 || (long long)width * height >= (1ll << 31))) {
+            avt_set_error("avt_set_occlusion_render: bad image size (0 < width < 65536, height > 0, width x height < 2^31; width 0 turns the mode off)");
+            return 1;
+        }
+        AVT_HIP(hipSetDevice(c->device));
+        // the scratch of the new size first, beside the old one: a refused call leaves the previous setting in force
+        DevBuf<int> faces, order, rank; DevBuf<float> fkey, proj; DevBuf<unsigned char> front;
+        if (width > 0) {
+            const size_t nf = (size_t)c->fb.max_frames, F = (size_t)std::max(c->dm.d.F, 1), V = (size_t)c->dm.d.V;
+            if (faces.reserve(nf * width * height) || order.reserve(nf * F) || rank.reserve(nf * F) || fkey.reserve(nf * F) || proj.reserve(nf * 2 * V) ||
+                front.reserve(nf * F)) {
+                (void)hipGetLastError();
+                avt_set_error(std::string("avt_set_occlusion_render: the device cannot hold the face images of every frame slot (") + avt_last_error() + ")");
+                return 1;
+            }
+        }
+        AVT_HIP(hipStreamSynchronize(c->stream));      // nothing queued reads the old scratch any more
+        {   // the launch sequences captured so far hold the old rule and the old scratch
+            std::lock_guard<std::mutex> graph_lock(g_graph_mutex);
+            for (auto& e : c->graphs) (void)hipGraphExecDestroy(e.exec);
+            c->graphs.clear();
+        }
+        c->occ_faces = std::move(faces); c->occ_order = std::move(order); c->occ_rank = std::move(rank);
+        c->occ_fkey = std::move(fkey); c->occ_proj = std::move(proj); c->occ_front = std::move(front);
+        c->occ_w = width; c->occ_h = width > 0 ? height : 0;
+        c->occ_fx = fx; c->occ_fy = fy; c->occ_cx = cx; c->occ_cy = cy;
+        return 0;
+    });
+}
+
+int avt_get_visibility(avt_ctx* c, int frame, unsigned char* visible) {
+    if (!c || !visible || frame < 0 || frame >= c->nframes) { avt_set_error("avt_get_visibility: bad argument"); return 1; }
+    if (!c->frames_valid || c->ran_icp_iters <= 0) { avt_set_error("avt_get_visibility: no optimize call with an ICP iteration has run on the resident frames"); return 1; }
+    AVT_HIP(hipSetDevice(c->device));
+    AVT_HIP(hipMemcpyAsync(visible, c->fb.visible + (size_t)frame * c->dm.d.V, (size_t)c->dm.d.V, hipMemcpyDeviceToHost, c->stream));
+    AVT_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
 
 int avt_debug_trace(avt_ctx* c, int frame, double* out64) {
     if (!c || !out64 || frame < 0 || frame >= c->fb.max_frames) { avt_set_error("avt_debug_trace: bad argument"); return 1; }

@@ -409,6 +409,12 @@ struct avt_ctx {
     // (avt_budget_hold_doubles), and what budget[] was last set to (a repeated pattern is not uploaded again)
     DevBuf<int> budget; DevBuf<double> budget_hold;
     std::vector<int> budget_host;
+    // avt_set_occlusion_render (occ_w == 0: off): the camera, and the scratch of the face-id render for max_frames frames, allocated by
+    // that call - per frame the face image (W x H painter positions), the faces' sort keys, painter order and positions, the projected
+    // vertices (float pairs) and the faces' back-face flags
+    int occ_w = 0, occ_h = 0;
+    float occ_fx = 0, occ_fy = 0, occ_cx = 0, occ_cy = 0;
+    DevBuf<int> occ_faces, occ_order, occ_rank; DevBuf<float> occ_fkey, occ_proj; DevBuf<unsigned char> occ_front;
 };
 
 void avt_set_error(const std::string& s);
@@ -424,6 +430,8 @@ bool avt_lbs_can_init(const AvtDims& d);
 size_t avt_visibility_frame_lds(const AvtDims& d);
 bool avt_nn_few(const avt_ctx* c, int nframes);
 void launch_visibility(avt_ctx* c, int nframes, int enable, bool with_bucket_scatter = false);
+// the shape of launch_visibility with the render occlusion on (avt_render.hip); the flags are cleared already
+void launch_visibility_render(avt_ctx* c, int nframes, bool with_bucket_scatter);
 void launch_bucket(avt_ctx* c, int nframes, bool clear_after);
 void launch_state_reset(avt_ctx* c, int nframes);
 void launch_nn(avt_ctx* c, int nframes);

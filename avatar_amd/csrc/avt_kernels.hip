@@ -477,6 +477,8 @@ void launch_visibility(avt_ctx* c, int nframes, int enable, bool with_bucket_sca
     if (!c->lbs_cleared) (void)hipMemsetAsync(c->fb.visible + (size_t)c->fb.f0 * V, enable ? 0 : 1, (size_t)nframes * V, c->cur_stream);
     const int nb = with_bucket_scatter ? std::max(1, (c->launch_maxN + BUCKET_TILE - 1) / BUCKET_TILE) : 0;
     c->scatter_in_compact = false;
+    // avt_set_occlusion_render: back-face test AND a pixel of the face-id render (a model without faces marks nothing either way)
+    if (enable && c->occ_w > 0 && c->dm.d.F > 0) { launch_visibility_render(c, nframes, with_bucket_scatter); return; }
     if (enable && c->lbs_cleared && c->vis_frame_min > 0 && nframes >= c->vis_frame_min && !avt_nn_few(c, nframes)) {
         // inside optimize(), frame batches: one workgroup per frame; k_compact follows and takes the scatter workgroups
         hipLaunchKernelGGL(k_visibility_frame, dim3(nframes), dim3(1024), avt_visibility_frame_lds(c->dm.d), c->cur_stream, c->dm, c->fb);

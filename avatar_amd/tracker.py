@@ -80,8 +80,13 @@ def reinit_state(data, num_joints, num_shape_keys):
 
 class FrameTracker:
     def __init__(self, ava_opt: "api.AvatarOptimizer", interval=12, frame_icp_iters=3, reinit_icp_iters=6, reinit_cnz=1000,
-                 num_threads=4, rtree=None, rtree_interval=2, dist_to_pre_weight=0.001, initial_per_part_cnz=0, initial_icp_iters=None):
+                 num_threads=4, rtree=None, rtree_interval=2, dist_to_pre_weight=0.001, initial_per_part_cnz=0, initial_icp_iters=None,
+                 render_occlusion=None):
+        """render_occlusion: True / False sets ava_opt.renderOcclusion (self-occlusion from a face-id render at the optimizer's own
+        intrin and imageSize; not a reference behaviour); None leaves it as it is."""
         self.opt = ava_opt
+        if render_occlusion is not None:
+            ava_opt.renderOcclusion = bool(render_occlusion)
         self.ava = ava_opt.ava
         self.interval = interval                      # demo.cpp:58  --data-interval
         self.frameICPIters = frame_icp_iters          # demo.cpp:63  --frame-icp-iters
@@ -172,8 +177,13 @@ class MultiFrameTracker:
 
     def __init__(self, ctx, num_streams, interval=12, frame_icp_iters=3, reinit_icp_iters=6, reinit_cnz=1000, initial_per_part_cnz=0,
                  initial_icp_iters=None, beta_pose=0.1, beta_shape=1.0, max_iters_per_icp=10, enable_occlusion=True,
-                 function_tolerance=1e-4):
+                 function_tolerance=1e-4, render_occlusion=None):
+        """render_occlusion: None (off), or (intrin, (width, height)): self-occlusion visibility from a face-id render with that camera
+        (api.Context.set_occlusion_render; not a reference behaviour).  `renderOcclusion` holds it; set_render_occlusion changes it."""
         self.ctx = ctx
+        self.renderOcclusion = None
+        if render_occlusion:
+            self.set_render_occlusion(render_occlusion)
         self.S = int(num_streams)
         self.numParts = ctx.num_parts
         self.J, self.K = ctx.model.numJoints(), ctx.model.numShapeKeys()
@@ -195,6 +205,16 @@ class MultiFrameTracker:
         pm = np.arange(J, dtype=np.int32) if part_map is None else np.asarray(part_map, np.int32)
         ctx = api.Context(model, J if num_parts is None else num_parts, pm, max_points, num_streams, device)
         return cls(ctx, num_streams, **kw)
+
+    def set_render_occlusion(self, render_occlusion):
+        """None / False: off; (intrin, (width, height)): on with that camera.  Takes effect for the following steps."""
+        if not render_occlusion:
+            self.ctx.set_occlusion_render(None)
+            self.renderOcclusion = None
+        else:
+            intrin, size = render_occlusion
+            self.ctx.set_occlusion_render(size, intrin)
+            self.renderOcclusion = (intrin, tuple(size))
 
     def options(self, icp_iters):
         o = api.Options.reference_defaults()

@@ -8,9 +8,9 @@ namespace ark {
 /** Optimize avatar to fit a point cloud */
 class AvatarOptimizer {
    public:
-    /** Same signature as the reference; `intrin` and `image_size` do not influence optimize() there either
-     *  (renderer constructed but unused, AvatarOptimizer.cpp:1271,:1369-1385).  `part_map` must have >= numJoints
-     *  entries (AvatarOptimizer.cpp:1229) and is kept by reference, like the reference does. */
+    /** Same signature as the reference.  `intrin` and `image_size` do not influence optimize() there (renderer constructed but
+     *  unused, AvatarOptimizer.cpp:1271,:1369-1385); here they are the camera and image size of `renderOcclusion`.  `part_map`
+     *  must have >= numJoints entries (AvatarOptimizer.cpp:1229) and is kept by reference, like the reference does. */
     AvatarOptimizer(Avatar& ava, const CameraIntrin& intrin, const Size& image_size, int num_parts, const std::vector<int>& part_map)
         : ava(ava), intrin(intrin), imageSize(image_size), numParts(num_parts), partMap(part_map) {
         r.resize(ava.model.numJoints());
@@ -30,6 +30,11 @@ class AvatarOptimizer {
             if (ctx) avt_ctx_destroy(ctx);
             capacity = N > 65536 ? N : 65536;
             ARK_AVT_CHECK(avt_ctx_create(ava.device, ava.model.handle, numParts, partMap.data(), capacity, 1, &ctx));
+            occlusionRenderSet = false;
+        }
+        if (renderOcclusion != occlusionRenderSet) {       // the context follows the member (a new context starts with the mode off)
+            ARK_AVT_CHECK(avt_set_occlusion_render(ctx, renderOcclusion ? imageSize.width : 0, imageSize.height, intrin.fx, intrin.fy, intrin.cx, intrin.cy));
+            occlusionRenderSet = renderOcclusion;
         }
         for (int i = 0; i < J; ++i) r[i] = rotationToQuaternion(ava.r[i]);       // :1250-1254
         avt_options o;
@@ -56,6 +61,13 @@ class AvatarOptimizer {
         }
     }
 
+    /** The visibility flags (numPoints bytes, 0 / 1) of the last ICP iteration of the last optimize() (avt_get_visibility) */
+    std::vector<unsigned char> visibility() const {
+        std::vector<unsigned char> v((size_t)ava.model.numPoints());
+        ARK_AVT_CHECK(avt_get_visibility(ctx, 0, v.data()));
+        return v;
+    }
+
     /** Rotation representation size */
     static const int ROT_SIZE = 4;
     /** Optimization parameter r */
@@ -68,6 +80,11 @@ class AvatarOptimizer {
     int maxItersPerICP = 10;
     /** Whether to elimiate occluded points before NN matching */
     bool enableOcclusion = true;
+    /** NOT a member of the reference's class: the true-occlusion block its author left commented out as too slow
+     *  (AvatarOptimizer.cpp:1369-1385).  With enableOcclusion, a point is visible iff one of its front-facing faces owns a pixel
+     *  of renderFaces(imageSize) of the current cloud at `intrin` (include/avt.h, avt_set_occlusion_render): a body part in front
+     *  of another hides it.  Off by default; takes effect at the next optimize(). */
+    bool renderOcclusion = false;
     /** Not a member of the reference's class: the value its optimize() hard-codes as options.function_tolerance
      *  (AvatarOptimizer.cpp:1333) - a step that lowers the objective by no more than this fraction ends the inner iterations
      *  of the ICP iteration; 0 = always maxItersPerICP iterations (include/avt.h, avt_options::function_tolerance) */
@@ -86,5 +103,6 @@ class AvatarOptimizer {
    private:
     avt_ctx* ctx = nullptr;
     int capacity = 0;
+    bool occlusionRenderSet = false;   // what ctx was last told
 };
 }  // namespace ark

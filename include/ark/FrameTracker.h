@@ -54,6 +54,7 @@ class FrameTracker {
             reinitState(dataCloud, cnz, ava.p.data(), ava.w, ava.r);
             ava.update();
         }
+        if (renderOcclusion >= 0) avaOpt.renderOcclusion = renderOcclusion != 0;
         avaOpt.optimize(dataCloud, dataPartLabels, icpIters, numThreads);
         ++framesFitted;
         return true;
@@ -71,6 +72,9 @@ class FrameTracker {
     bool reinit = true;           // demo.cpp:151
     bool firstTime = true;        // live-demo.cpp:256
     long framesFitted = 0;
+    /** not a reference member: 1 / 0 sets avaOpt.renderOcclusion before every fit (self-occlusion from a face-id render with the
+     *  optimizer's own intrin and imageSize, AvatarOptimizer.cpp:1369-1385); -1 (default) leaves the optimizer's member alone */
+    int renderOcclusion = -1;
 
     AvatarOptimizer& avaOpt;
     Avatar& ava;

@@ -52,6 +52,21 @@ class MultiFrameTracker {
     MultiFrameTracker(const MultiFrameTracker&) = delete;
     MultiFrameTracker& operator=(const MultiFrameTracker&) = delete;
 
+    /** Not a reference behaviour: self-occlusion visibility from a face-id render of every stream's current cloud at this camera
+     *  (include/avt.h, avt_set_occlusion_render; AvatarOptimizer.cpp:1369-1385 is the block the reference left commented out).
+     *  on = false turns it off again.  Takes effect for the following steps; `renderOcclusion` tells what is in force. */
+    void setRenderOcclusion(bool on, const Size& image_size = Size(), const CameraIntrin& intrin = CameraIntrin()) {
+        ARK_AVT_CHECK(avt_set_occlusion_render(ctx, on ? image_size.width : 0, image_size.height, intrin.fx, intrin.fy, intrin.cx, intrin.cy));
+        renderOcclusion = on;
+        if (on) { occlusionSize = image_size; occlusionIntrin = intrin; }
+    }
+    /** the visibility flags (numPoints bytes) of the last ICP iteration of the last step on stream s (avt_get_visibility) */
+    std::vector<unsigned char> visibility(int s) const {
+        std::vector<unsigned char> v((size_t)model.numPoints());
+        ARK_AVT_CHECK(avt_get_visibility(ctx, s, v.data()));
+        return v;
+    }
+
     /** One step, one frame per stream.  fitted[s] = 1 if stream s was fitted, 0 if its tracking was declared lost. */
     void process(const std::vector<Frame>& frames, std::vector<int>& fitted) {
         if ((int)frames.size() != S) { std::fprintf(stderr, "MultiFrameTracker: %d frames for %d streams\n", (int)frames.size(), S); std::exit(1); }
@@ -240,6 +255,9 @@ class MultiFrameTracker {
     double betaPose = 0.1, betaShape = 1.0, functionTolerance = 1e-4;
     int maxItersPerICP = 10;
     bool enableOcclusion = true;
+    bool renderOcclusion = false;                  // read-only: set by setRenderOcclusion, with the camera below
+    Size occlusionSize;
+    CameraIntrin occlusionIntrin;
     std::vector<int> budgets, reinitStreams;       // of the last step (0 = not fitted)
     // processDepth: per stream the previous centres of mass (demo.cpp:148), the last step's box and post-processed labels
     std::vector<MatrixNX<2>> comPre;

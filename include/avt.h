@@ -162,8 +162,24 @@ int avt_sync(avt_ctx* c);
 int avt_lbs_update(avt_ctx* c, int nframes, const double* w, const double* p, const double* R,
                    double* cloud, double* joint_pos, double* joint_trans);
 
-/* ---- back-face visibility (AvatarOptimizer.cpp:1342-1367). visible: V bytes (0/1). */
+/* ---- back-face visibility (AvatarOptimizer.cpp:1342-1367). visible: V bytes (0/1).  Follows the context's setting of
+ * avt_set_occlusion_render: with the render occlusion on and enable_occlusion != 0 the flags are those of the rule below. */
 int avt_visibility(avt_ctx* c, const double* cloud_3xV, int enable_occlusion, unsigned char* visible);
+
+/* ---- self-occlusion from a face-id render (NOT a reference behaviour: the block its author left commented out as too slow,
+ * AvatarOptimizer.cpp:1369-1385, decided here).  With width > 0 every later call on this context that runs visibility with
+ * enable_occlusion != 0 - avt_optimize*, the resident and budget calls, avt_visibility - uses, for the frame's current cloud:
+ *   visible[v] = 1 iff some face f contains v, f passes the back-face test (the expression and rounding of :1349-1367, > 1e-4), and
+ *   f's painter position is the value of at least one pixel of AvatarRenderer::renderFaces of that cloud with these intrinsics and
+ *   this image size (float intrinsics; painter order by decreasing mean-depth key, ties by ascending face id; end-exclusive row fill;
+ *   every face painted, back-facing ones included: exactly the AVT_RENDER_FACES image of include/avt_render.h).
+ * So a pixel won by a back-facing face marks nothing and hides what lies behind it, and a face that covers no pixel centre, lies
+ * outside the image or has z <= 0 marks nothing.  enable_occlusion == 0 still means every point is visible.  Nothing downstream changes.
+ * width == 0 turns the mode off again (the default).  The call allocates the render's per-frame scratch for the context's max_frames
+ * (4 bytes per pixel and frame, plus 13 bytes per face and 8 per vertex), waits for the context's stream and drops its captured graphs.
+ * It refuses non-positive sizes, width >= 65536, width x height >= 2^31 and an allocation the device cannot give; a refused call
+ * leaves the previous setting in force. */
+int avt_set_occlusion_render(avt_ctx* c, int width, int height, float fx, float fy, float cx, float cy);
 
 /* ---- findNN(..., invert=true) (AvatarOptimizer.cpp:841-907): for each data point the exact nearest
  * visible model point of its own part; -1 where the part has no visible model point (:899). */
@@ -239,6 +255,9 @@ int avt_frames_download(avt_ctx* c, int frame, double* data_3xN, int* labels);
 /* ---- introspection of the last optimize call (tests / diagnostics) */
 int avt_get_correspondences(avt_ctx* c, int frame, int* model_idx_out /* N of that frame */);
 int avt_get_cloud(avt_ctx* c, int frame, double* cloud_3xV);       /* ava.cloud after the final update() */
+/* the visibility flags (V bytes, 0/1) of the last ICP iteration the last optimize call ran on that frame (the closing update() leaves
+ * them alone); with per-frame budgets: of the call's last ICP iteration, like avt_get_correspondences */
+int avt_get_visibility(avt_ctx* c, int frame, unsigned char* visible_V);
 /* ava.cloud, ava.jointPos (3 x J) and ava.jointTrans (12 x J) as the update() that ends optimize() left them
  * (AvatarOptimizer.cpp:1494-1497, Avatar.cpp:22-75): a caller refreshes its Avatar from these instead of running
  * update() a second time.  Any pointer may be NULL. */
