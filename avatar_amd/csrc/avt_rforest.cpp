@@ -1,0 +1,263 @@
+// avt_rforest.cpp — host side of the forest of several trees (include/avt_rforest.h): validation of the members against each
+// other, the packed device image (one node array with rebased links, one leaf table), image staging and the resident forms,
+// argument for argument what avt_rtree.cpp does for one tree.
+#include "avt_rforest.h"
+
+#include <algorithm>
+#include <string>
+
+#include "avt_bgsub_internal.h"
+#include "avt_internal.h"
+
+namespace {
+
+const char* const kHostOnly = "rforest: created host-only (device < 0): inference needs a GPU";
+
+int roi_ok(int rows, int cols, int interval, int& tlx, int& tly, int& brx, int& bry) {
+    if (brx == -1) { brx = cols - 1; bry = rows - 1; }
+    if (rows <= 0 || cols <= 0 || interval <= 0 || tlx < 0 || tly < 0 || brx >= cols || bry >= rows || tlx > brx || tly > bry || rows >= 32768 ||
+        cols >= 32768) {
+        avt_set_error("rforest: bad image size, interval or region of interest");
+        return 1;
+    }
+    return 0;
+}
+
+int batch_ok(int n_images) {      // blockIdx.z is the image
+    if (n_images > 65535) { avt_set_error("rforest: at most 65535 images per call"); return 1; }
+    return 0;
+}
+
+// every tree's nodes behind each other, links rebased; a leaf's rnode is its row in the forest's one table
+int pack(avt_rforest* rf, const avt_rtree* const* trees) {
+    size_t n_total = 0, l_total = 0;
+    for (int t = 0; t < rf->n_trees; ++t) { n_total += trees[t]->links.size() / 3; l_total += trees[t]->leaf_best.size(); }
+    if (n_total >= (1u << 30) || l_total * (size_t)rf->num_parts >= (1u << 30)) { avt_set_error("avt_rforest_create: the forest is too large"); return 1; }
+    rf->nodes.reserve(n_total);
+    rf->leaf.reserve(l_total * rf->num_parts);
+    for (int t = 0; t < rf->n_trees; ++t) {
+        const avt_rtree* rt = trees[t];
+        const int n = (int)(rt->links.size() / 3), node0 = (int)rf->nodes.size(), leaf0 = (int)(rf->leaf.size() / rf->num_parts);
+        rf->roots.push_back(node0);
+        for (int i = 0; i < n; ++i) {
+            const float* f = &rt->feature[5 * (size_t)i];
+            const int leaf = rt->links[3 * i + 2];
+            rf->nodes.push_back(RtNodeDev{f[0], f[1], f[2], f[3], f[4], leaf < 0 ? node0 + rt->links[3 * i] : (int)rt->leaf_best[leaf],
+                                          leaf < 0 ? node0 + rt->links[3 * i + 1] : leaf0 + leaf, leaf < 0 ? 0 : 1});
+        }
+        rf->leaf.insert(rf->leaf.end(), rt->leaf_data.begin(), rt->leaf_data.end());
+    }
+    return 0;
+}
+
+int upload_forest(avt_rforest* rf) {
+    if (rf->device < 0) return 0;
+    AVT_HIP(hipSetDevice(rf->device));
+    AVT_HIP(hipStreamCreateWithFlags(&rf->stream, hipStreamNonBlocking));
+    if (rf->d_nodes.reserve(rf->nodes.size()) || rf->d_roots.reserve(rf->roots.size()) || rf->d_leaf.reserve(std::max<size_t>(1, rf->leaf.size()))) return 1;
+    AVT_HIP(hipMemcpyAsync(rf->d_nodes, rf->nodes.data(), sizeof(RtNodeDev) * rf->nodes.size(), hipMemcpyHostToDevice, rf->stream));
+    AVT_HIP(hipMemcpyAsync(rf->d_roots, rf->roots.data(), sizeof(int) * rf->roots.size(), hipMemcpyHostToDevice, rf->stream));
+    AVT_HIP(hipMemcpyAsync(rf->d_leaf, rf->leaf.data(), sizeof(float) * rf->leaf.size(), hipMemcpyHostToDevice, rf->stream));
+    AVT_HIP(hipStreamSynchronize(rf->stream));     // the legacy stream is never used (a host thread may be capturing)
+    return 0;
+}
+
+int reserve_images(avt_rforest* rf, size_t pixels) {
+    if (rf->device < 0) { avt_set_error(kHostOnly); return 1; }
+    if (pixels <= rf->d_depth.cap && pixels <= rf->d_labels.cap) return 0;
+    AVT_HIP(hipSetDevice(rf->device));
+    return rf->d_depth.reserve(pixels) || rf->d_labels.reserve(pixels);
+}
+
+int create_impl(const avt_rtree* const* trees, int n_trees, int device, avt_rforest** out) {
+    if (!trees || !out) { avt_set_error("avt_rforest_create: null argument"); return 1; }
+    if (n_trees < 1 || n_trees > AVT_RFOREST_MAX_TREES) {
+        avt_set_error("avt_rforest_create: " + std::to_string(n_trees) + " trees: a forest has 1 to " + std::to_string(AVT_RFOREST_MAX_TREES));
+        return 1;
+    }
+    for (int t = 0; t < n_trees; ++t) {
+        if (!trees[t]) { avt_set_error("avt_rforest_create: tree " + std::to_string(t) + " is null"); return 1; }
+        const std::string who = "avt_rforest_create: tree " + std::to_string(t);
+        if (trees[t]->num_parts != trees[0]->num_parts) {
+            avt_set_error(who + " has num_parts " + std::to_string(trees[t]->num_parts) + ", tree 0 has " + std::to_string(trees[0]->num_parts));
+            return 1;
+        }
+        if (trees[t]->part_map != trees[0]->part_map) { avt_set_error(who + " has another part map than tree 0"); return 1; }
+        if (trees[t]->part_map_type != trees[0]->part_map_type) { avt_set_error(who + " has another part-map type than tree 0"); return 1; }
+    }
+    avt_rforest* rf = new avt_rforest();
+    rf->device = device;
+    rf->n_trees = n_trees;
+    rf->num_parts = trees[0]->num_parts;
+    rf->part_map = trees[0]->part_map;
+    rf->part_map_type = trees[0]->part_map_type;
+    if (pack(rf, trees) || upload_forest(rf)) { avt_rforest_destroy(rf); return 1; }
+    *out = rf;
+    return 0;
+}
+
+int images_upload_impl(avt_rforest* rf, int n_images, int rows, int cols, const float* depth) {
+    if (!rf || !depth || n_images <= 0 || rows <= 0 || cols <= 0) { avt_set_error("avt_rforest_images_upload: bad arguments"); return 1; }
+    if (batch_ok(n_images)) return 1;
+    const size_t pixels = (size_t)n_images * rows * cols;
+    if (reserve_images(rf, pixels)) return 1;
+    AVT_HIP(hipSetDevice(rf->device));
+    AVT_HIP(hipMemcpyAsync(rf->d_depth, depth, pixels * sizeof(float), hipMemcpyHostToDevice, rf->stream));
+    rf->n_images = rf->n_labels = n_images; rf->rows = rows; rf->cols = cols;
+    return 0;
+}
+
+int labels_download_impl(avt_rforest* rf, int image, unsigned char* out) {
+    if (!rf || !out || image < 0 || image >= rf->n_labels) { avt_set_error("avt_rforest_labels_download: bad arguments"); return 1; }
+    const size_t px = (size_t)rf->rows * rf->cols;
+    AVT_HIP(hipMemcpyAsync(out, rf->d_labels + px * image, px, hipMemcpyDeviceToHost, rf->stream));
+    AVT_HIP(hipStreamSynchronize(rf->stream));
+    return 0;
+}
+
+int labels_download_all_impl(avt_rforest* rf, unsigned char* out) {
+    if (!rf || !out || rf->n_labels <= 0) { avt_set_error("avt_rforest_labels_download_all: bad arguments or no labelled images"); return 1; }
+    AVT_HIP(hipMemcpyAsync(out, rf->d_labels, (size_t)rf->n_labels * rf->rows * rf->cols, hipMemcpyDeviceToHost, rf->stream));
+    AVT_HIP(hipStreamSynchronize(rf->stream));
+    return 0;
+}
+
+int predict_best_impl(avt_rforest* rf, const float* depth, int rows, int cols, int interval, int tlx, int tly, int brx, int bry, int fill,
+                      unsigned char* labels_out) {
+    if (!rf || !depth || !labels_out) { avt_set_error("avt_rforest_predict_best: null argument"); return 1; }
+    if (roi_ok(rows, cols, interval, tlx, tly, brx, bry)) return 1;
+    if (images_upload_impl(rf, 1, rows, cols, depth)) return 1;
+    if (avt_rforest_launch_predict(rf, rf->d_depth, nullptr, 0, 1, rows, cols, interval, tlx, tly, brx, bry, fill)) {
+        avt_set_error("rforest: kernel launch failed");
+        return 1;
+    }
+    return labels_download_impl(rf, 0, labels_out);
+}
+
+int predict_impl(avt_rforest* rf, const float* depth, int rows, int cols, float* dist_out) {
+    if (!rf || !depth || !dist_out || rows <= 0 || cols <= 0) { avt_set_error("avt_rforest_predict: bad arguments"); return 1; }
+    if (rows >= 32768 || cols >= 32768) { avt_set_error("rforest: bad image size, interval or region of interest"); return 1; }
+    if (images_upload_impl(rf, 1, rows, cols, depth)) return 1;
+    const size_t n = (size_t)rf->num_parts * rows * cols;
+    DevBuf<float> d_out;
+    if (d_out.reserve(n)) return 1;
+    int rc = avt_rforest_launch_predict_dist(rf, rows, cols, d_out);
+    if (rc) avt_set_error("rforest: kernel launch failed");
+    if (!rc && hipMemcpyAsync(dist_out, d_out, n * sizeof(float), hipMemcpyDeviceToHost, rf->stream) != hipSuccess) { avt_set_error("rforest: download failed"); rc = 1; }
+    if (hipStreamSynchronize(rf->stream) != hipSuccess && !rc) { avt_set_error("rforest: stream failed"); rc = 1; }   // on every path, before d_out goes
+    return rc;
+}
+
+int predict_best_resident_boxes_impl(avt_rforest* rf, int interval, const int* boxes, int fill) {
+    if (!rf || !boxes) { avt_set_error("avt_rforest_predict_best_resident_boxes: null argument"); return 1; }
+    if (rf->device < 0) { avt_set_error(kHostOnly); return 1; }
+    if (rf->n_images <= 0) { avt_set_error("avt_rforest_predict_best_resident_boxes: no images resident"); return 1; }
+    const int n = rf->n_images, rows = rf->rows, cols = rf->cols;
+    // everything is checked before anything is queued: after a failure the labels of the previous call are still there
+    std::vector<int> b(boxes, boxes + 4 * (size_t)n);
+    for (int i = 0; i < n; ++i) {
+        int* q = &b[4 * (size_t)i];
+        if (q[2] == -1) { q[2] = cols - 1; q[3] = rows - 1; }
+        if (q[0] > q[2] || q[1] > q[3]) continue;          // an empty box: that image stays 255 (a lost stream does not fail the batch)
+        if (roi_ok(rows, cols, interval, q[0], q[1], q[2], q[3])) return 1;
+    }
+    int tlx = 0, tly = 0, brx = -1, bry = -1;
+    if (roi_ok(rows, cols, interval, tlx, tly, brx, bry)) return 1;     // the interval and the image size, when every box is empty
+    AVT_HIP(hipSetDevice(rf->device));
+    if (rf->d_boxes.reserve(4 * (size_t)n)) return 1;
+    AVT_HIP(hipMemcpyAsync(rf->d_boxes, b.data(), b.size() * sizeof(int), hipMemcpyHostToDevice, rf->stream));
+    AVT_HIP(hipStreamSynchronize(rf->stream));             // `b` is on this stack frame
+    if (avt_rforest_launch_predict(rf, rf->d_depth, rf->d_boxes, 4, n, rows, cols, interval, 0, 0, 0, 0, fill)) {
+        avt_set_error("rforest: kernel launch failed");
+        return 1;
+    }
+    return 0;
+}
+
+int predict_best_from_bgsub_impl(avt_rforest* rf, avt_bgsub* bg, int interval, int fill) {
+    if (!rf) { avt_set_error("avt_rforest_predict_best_from_bgsub: null forest"); return 1; }
+    if (rf->device < 0) { avt_set_error(kHostOnly); return 1; }
+    if (!bg) { avt_set_error("avt_rforest_predict_best_from_bgsub: null background subtractor"); return 1; }
+    avt_bgsub_view v;
+    if (avt_bgsub_last_run(bg, &v)) return 1;
+    if (v.device != rf->device) { avt_set_error("avt_rforest_predict_best_from_bgsub: the forest and the background subtractor are on different devices"); return 1; }
+    int tlx = 0, tly = 0, brx = -1, bry = -1;
+    if (roi_ok(v.rows, v.cols, interval, tlx, tly, brx, bry) || batch_ok(v.n_images)) return 1;
+    AVT_HIP(hipSetDevice(rf->device));
+    const size_t pixels = (size_t)v.n_images * v.rows * v.cols;
+    if (rf->d_labels.reserve(pixels)) return 1;
+    // the labels are these images' from here on, and the forest has no resident depth of its own until the next images_upload
+    rf->n_images = 0; rf->n_labels = v.n_images; rf->rows = v.rows; rf->cols = v.cols;
+    // the forest's stream waits for the run; bg's next upload / run / destroy waits for the labelling.  No copy, no host wait.
+    if (avt_bgsub_reader_begin(bg, rf->stream)) return 1;
+    const int rc = avt_rforest_launch_predict(rf, v.d_depth, v.d_boxes, v.box_stride, v.n_images, v.rows, v.cols, interval, 0, 0, 0, 0, fill);
+    if (avt_bgsub_reader_end(bg, rf->stream)) return 1;    // also after a failed launch: the memset may be queued
+    if (rc) { avt_set_error("rforest: kernel launch failed"); return 1; }
+    return 0;
+}
+
+}  // namespace
+
+// ---- exported entry points: no C++ exception crosses the C ABI
+extern "C" {
+
+int avt_rforest_create(const avt_rtree* const* trees, int n_trees, int device, avt_rforest** out) {
+    return avt_guard("avt_rforest_create", [&]() -> int { return create_impl(trees, n_trees, device, out); });
+}
+
+void avt_rforest_destroy(avt_rforest* rf) {
+    if (!rf) return;
+    // the buffers go with `delete`, after the stream: it is drained first, so nothing is queued on them either way
+    if (rf->stream) (void)hipStreamSynchronize(rf->stream);
+    if (rf->stream) (void)hipStreamDestroy(rf->stream);
+    delete rf;
+}
+
+int avt_rforest_info(const avt_rforest* rf, int* n_trees, int* num_parts, int* part_map_len, int* part_map_type, int* total_nodes, int* total_leafs) {
+    if (!rf) { avt_set_error("avt_rforest_info: null forest"); return 1; }
+    if (n_trees) *n_trees = rf->n_trees;
+    if (num_parts) *num_parts = rf->num_parts;
+    if (part_map_len) *part_map_len = (int)rf->part_map.size();
+    if (part_map_type) *part_map_type = rf->part_map_type;
+    if (total_nodes) *total_nodes = (int)rf->nodes.size();
+    if (total_leafs) *total_leafs = (int)(rf->leaf.size() / rf->num_parts);
+    return 0;
+}
+
+int avt_rforest_predict(avt_rforest* rf, const float* depth, int rows, int cols, float* dist_out) {
+    return avt_guard("avt_rforest_predict", [&]() -> int { return predict_impl(rf, depth, rows, cols, dist_out); });
+}
+
+int avt_rforest_predict_best(avt_rforest* rf, const float* depth, int rows, int cols, int interval, int tlx, int tly, int brx, int bry, int fill,
+                             unsigned char* labels_out) {
+    return avt_guard("avt_rforest_predict_best", [&]() -> int { return predict_best_impl(rf, depth, rows, cols, interval, tlx, tly, brx, bry, fill, labels_out); });
+}
+
+int avt_rforest_images_upload(avt_rforest* rf, int n_images, int rows, int cols, const float* depth) {
+    return avt_guard("avt_rforest_images_upload", [&]() -> int { return images_upload_impl(rf, n_images, rows, cols, depth); });
+}
+
+int avt_rforest_predict_best_resident_boxes(avt_rforest* rf, int interval, const int* boxes, int fill) {
+    return avt_guard("avt_rforest_predict_best_resident_boxes", [&]() -> int { return predict_best_resident_boxes_impl(rf, interval, boxes, fill); });
+}
+
+int avt_rforest_predict_best_from_bgsub(avt_rforest* rf, avt_bgsub* bg, int interval, int fill) {
+    return avt_guard("avt_rforest_predict_best_from_bgsub", [&]() -> int { return predict_best_from_bgsub_impl(rf, bg, interval, fill); });
+}
+
+int avt_rforest_labels_download(avt_rforest* rf, int image, unsigned char* labels_out) {
+    return avt_guard("avt_rforest_labels_download", [&]() -> int { return labels_download_impl(rf, image, labels_out); });
+}
+
+int avt_rforest_labels_download_all(avt_rforest* rf, unsigned char* labels_out) {
+    return avt_guard("avt_rforest_labels_download_all", [&]() -> int { return labels_download_all_impl(rf, labels_out); });
+}
+
+int avt_rforest_sync(avt_rforest* rf) {
+    if (!rf) { avt_set_error("avt_rforest_sync: null forest"); return 1; }
+    if (rf->device < 0) { avt_set_error(kHostOnly); return 1; }
+    AVT_HIP(hipStreamSynchronize(rf->stream));
+    return 0;
+}
+
+}  // extern "C"

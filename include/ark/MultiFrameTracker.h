@@ -19,6 +19,7 @@
 #include "../avt_render.h"
 #include "AvatarOptimizer.h"
 #include "BGSubtractor.h"
+#include "RForest.h"
 #include "RTree.h"
 #include "TrackerPolicy.h"
 
@@ -148,7 +149,16 @@ class MultiFrameTracker {
     /** The front end of processDepth: a BGSubtractor holding one background per stream and a forest on the same device (both
      *  outlive the tracker's use of them); the interval of predictBest / postProcess (demo.cpp:198) and postProcess's weight. */
     void attachFrontEnd(BGSubtractor& bgsub, RTree& rtree, int rtree_interval = 2, double dist_to_pre_weight = 0.001) {
-        frontBG = &bgsub; frontTree = &rtree;
+        frontBG = &bgsub; frontTree = &rtree; frontForest = nullptr;
+        rtreeInterval = rtree_interval; distToPreWeight = dist_to_pre_weight;
+        comPre.assign((size_t)S, MatrixNX<2>());
+        boxes.assign((size_t)S, {0, 0, 0, 0});
+        partMasks.clear();
+    }
+
+    /** The same front end with a forest of several trees in the tree's place (ark/RForest.h). */
+    void attachFrontEnd(BGSubtractor& bgsub, RForest& rforest, int rtree_interval = 2, double dist_to_pre_weight = 0.001) {
+        frontBG = &bgsub; frontTree = nullptr; frontForest = &rforest;
         rtreeInterval = rtree_interval; distToPreWeight = dist_to_pre_weight;
         comPre.assign((size_t)S, MatrixNX<2>());
         boxes.assign((size_t)S, {0, 0, 0, 0});
@@ -160,7 +170,7 @@ class MultiFrameTracker {
      *  empty or not inside the image has an all-255 mask: it goes through postProcess on the whole image (every comPre x becomes
      *  -1) and is lost in process().  Afterwards partMasks[s] and boxes[s] (tl.x tl.y br.x br.y) hold the step's labels and boxes. */
     void processDepth(const std::vector<ImageXYZ>& images, std::vector<int>& fitted) {
-        if (!frontBG || !frontTree) { std::fprintf(stderr, "MultiFrameTracker::processDepth: no front end attached\n"); std::exit(1); }
+        if (!frontBG || (!frontTree && !frontForest)) { std::fprintf(stderr, "MultiFrameTracker::processDepth: no front end attached\n"); std::exit(1); }
         if ((int)images.size() != S) { std::fprintf(stderr, "MultiFrameTracker: %d images for %d streams\n", (int)images.size(), S); std::exit(1); }
         frontBG->runBatch(images);
         const std::vector<Rect> box = labelBatch();
@@ -172,7 +182,7 @@ class MultiFrameTracker {
     /** processDepth() from S depth images and their cameras (one per stream, or one for all): the depth is what is uploaded
      *  (BGSubtractor::runBatchDepth), and the subsampling back-projects the kept pixels alone. */
     void processDepthImages(const std::vector<ImageDepth>& depths, const std::vector<CameraIntrin>& intrins, std::vector<int>& fitted) {
-        if (!frontBG || !frontTree) { std::fprintf(stderr, "MultiFrameTracker::processDepthImages: no front end attached\n"); std::exit(1); }
+        if (!frontBG || (!frontTree && !frontForest)) { std::fprintf(stderr, "MultiFrameTracker::processDepthImages: no front end attached\n"); std::exit(1); }
         if ((int)depths.size() != S || ((int)intrins.size() != S && intrins.size() != 1)) {
             std::fprintf(stderr, "MultiFrameTracker: %d depth images, %d cameras for %d streams\n", (int)depths.size(), (int)intrins.size(), S);
             std::exit(1);
@@ -189,7 +199,11 @@ class MultiFrameTracker {
     /** The front end behind the batch run, whatever its source: labels on the device, postProcess per stream; fills partMasks and
      *  boxes and returns every stream's box to subsample. */
     std::vector<Rect> labelBatch() {
-        partMasks = frontTree->predictBestFromBGSub(*frontBG, rtreeInterval);
+        partMasks = frontTree ? frontTree->predictBestFromBGSub(*frontBG, rtreeInterval) : frontForest->predictBestFromBGSub(*frontBG, rtreeInterval);
+        auto postProcess = [&](Image8& m, MatrixNX<2>& com, Point tl, Point br) {
+            if (frontTree) frontTree->postProcess(m, com, rtreeInterval, 1, tl, br, distToPreWeight);
+            else frontForest->postProcess(m, com, rtreeInterval, 1, tl, br, distToPreWeight);
+        };
         std::vector<Rect> out((size_t)S);
         for (int s = 0; s < S; ++s) {
             const BGSubtractor::BatchInfo b = frontBG->batchInfo(s);
@@ -198,10 +212,10 @@ class MultiFrameTracker {
             Rect& box = out[(size_t)s];
             if (0 <= b.topLeft.x && b.topLeft.x <= b.botRight.x && b.botRight.x < m.cols && 0 <= b.topLeft.y && b.topLeft.y <= b.botRight.y &&
                 b.botRight.y < m.rows) {
-                frontTree->postProcess(m, comPre[(size_t)s], rtreeInterval, 1, b.topLeft, b.botRight, distToPreWeight);
+                postProcess(m, comPre[(size_t)s], b.topLeft, b.botRight);
                 box.top = b.topLeft.y; box.left = b.topLeft.x; box.bottom = b.botRight.y; box.right = b.botRight.x;
             } else {
-                frontTree->postProcess(m, comPre[(size_t)s], rtreeInterval, 1, Point(0, 0), Point(-1, -1), distToPreWeight);
+                postProcess(m, comPre[(size_t)s], Point(0, 0), Point(-1, -1));
                 box.top = m.rows - 1; box.left = m.cols - 1; box.bottom = 0; box.right = 0;       // nothing to subsample
             }
         }
@@ -276,6 +290,7 @@ class MultiFrameTracker {
     avt_ctx* ctx = nullptr;
     BGSubtractor* frontBG = nullptr;
     RTree* frontTree = nullptr;
+    RForest* frontForest = nullptr;   // in frontTree's place when a forest was attached
     int device_ = 0;
     avt_renderer* rend = nullptr;                  // render(): created on first use, again when the size or the intrinsics change
     int rendW = 0, rendH = 0;

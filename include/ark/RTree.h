@@ -219,6 +219,10 @@ public:
             die("postProcess");
     }
 
+    /** The C handle (ark::RForest copies the tree through it); a tree filled in through the public members is uploaded first.
+     *  Null when the tree is empty. */
+    avt_rtree* handle() { return ensure() ? h_ : nullptr; }
+
     std::vector<RNode> nodes;
     std::vector<Distribution> leafData;
     std::vector<uint8_t> leafBestMatch;

@@ -1,0 +1,78 @@
+/* avt_rforest.h — C ABI of a forest of several trained trees run as one (ark::RForest), part of libavatar_hip.so.
+ *
+ * The reference's tools load any number of models and classify each pixel from all of them (rtree-run.cpp:82-122,
+ * rtree-run-dataset.cpp:98-159): RTree::predict(depth) per model, the per-part distributions added in model order, the
+ * arg-max per pixel.  A forest here is T trees, 1 <= T <= AVT_RFOREST_MAX_TREES, that share num_parts, the part map and the
+ * part-map type; anything else is refused at creation with a message.
+ *
+ * THE RULE.  For a pixel that is walked, let leaf_t be the leaf tree t reaches and d_t its distribution.  Then
+ *     sum[p] = (((d_0[p] + d_1[p]) + d_2[p]) + ...)                               in float32, tree order, starting from tree
+ * 0's value and not from 0, never contracted (result = model_results; result[i] += ..., rtree-run-dataset.cpp:128-138), and
+ *     label  = the first p in ascending order with sum[p] > best, best starting at 0.f            (rtree-run-dataset.cpp:143-158):
+ * ties go to the lowest index, a pixel whose sums are all <= 0 or NaN gets 255, and a NaN never wins (the test is `>`).
+ * rtree-run.cpp:101-103 divides the sums by T before its arg-max; that is an OpenCV scalar division whose rounding cannot be
+ * pinned without OpenCV, so the contract here is the UNDIVIDED sum of rtree-run-dataset.
+ *
+ * TWO WALKING RULES, each the reference call it extends:
+ *   distribution form  RTree::predict(depth) (RTree.cpp:3156-3182): every pixel with depth > 0, probes bounded by the image;
+ *                      out = num_parts planes of sums, 0 elsewhere.
+ *   label form         RTree::predictBest(depth, ..., interval, top_left, bot_right, fill_in_gaps) (RTree.cpp:3184-3262), as
+ *                      avt_rtree_predict_best walks: the interval grid inside the box with the first row skipped, pixels with
+ *                      depth == 0 skipped, probes bounded by the region of interest, upscaleGrid's fill clamped to the row.
+ *                      Only the last step differs from one tree: leafBestMatch is replaced by the sum and arg-max above, so
+ *                      with T = 1 the labels are avt_rtree_predict_best's wherever the leaf has a positive entry.
+ *
+ * Conventions are avt_rtree.h's: row-major images, float32 depth in metres with 0 = background, uint8 labels with 255 = none,
+ * inclusive regions with bot_right.x == -1 for the whole image.  Functions return 0 on success; avt_last_error() (avt.h)
+ * describes a failure.
+ */
+#ifndef AVT_RFOREST_H_
+#define AVT_RFOREST_H_
+
+#include "avt_rtree.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define AVT_RFOREST_MAX_TREES 16
+
+typedef struct avt_rforest avt_rforest;
+
+/* The models of rtree-run-dataset.cpp:98-104, in this order.  Copies the trees (they may be destroyed afterwards) and uploads
+ * the packed forest to `device`; device < 0 makes a host-only forest that validates and answers avt_rforest_info but whose
+ * inference calls fail.  The trees themselves may be host-only or on any device. */
+int avt_rforest_create(const avt_rtree* const* trees, int n_trees, int device, avt_rforest** out);
+void avt_rforest_destroy(avt_rforest* rf);
+/* models.size(), numParts, partMap.size() and its type (rtree-run-dataset.cpp:98-104), nodes and leaves over all trees; any
+ * pointer may be NULL. */
+int avt_rforest_info(const avt_rforest* rf, int* n_trees, int* num_parts, int* part_map_len, int* part_map_type, int* total_nodes, int* total_leafs);
+
+/* Distribution form: the summed planes of rtree-run-dataset.cpp:124-138 (RTree::predict per model, RTree.cpp:3156-3182);
+ * dist_out = num_parts planes of rows x cols float32. */
+int avt_rforest_predict(avt_rforest* rf, const float* depth, int rows, int cols, float* dist_out);
+/* Label form: RTree::predictBest's walk (RTree.cpp:3184-3262) with the arg-max of rtree-run-dataset.cpp:143-158; host image
+ * in, host labels out (rows x cols bytes). */
+int avt_rforest_predict_best(avt_rforest* rf, const float* depth, int rows, int cols, int interval, int tl_x, int tl_y, int br_x, int br_y,
+                             int fill_in_gaps, unsigned char* labels_out);
+
+/* Resident forms, as the tree's (avt_rtree.h): the labelling of demo.cpp:179-204 for a batch of streams. */
+int avt_rforest_images_upload(avt_rforest* rf, int n_images, int rows, int cols, const float* depth);
+/* boxes: n_images x 4 host ints tl.x tl.y br.x br.y, inclusive; br.x == -1 is the whole image; an empty box (tl > br in either
+ * axis) leaves that image all 255 and is no error; a box shorter than `interval` rows labels nothing.  A box outside the image
+ * or a bad interval fails before anything is queued (demo.cpp:179-204 per stream). */
+int avt_rforest_predict_best_resident_boxes(avt_rforest* rf, int interval, const int* boxes, int fill_in_gaps);
+/* demo.cpp:179-204 without the host in between: labels every image of `bg`'s last avt_bgsub_run_resident inside the box that
+ * run left on the device, reading the masked depth where it lies.  No copy of the depth, no host synchronisation: the forest's
+ * stream waits for the run, and bg's next images_upload, run_resident and destroy wait for the labelling.  A box on the device
+ * that does not lie inside the image labels nothing.  Both handles must be on one device; `bg` must have a run behind it. */
+int avt_rforest_predict_best_from_bgsub(avt_rforest* rf, struct avt_bgsub* bg, int interval, int fill_in_gaps);
+/* One image's labels / every image's labels of the last labelling call (demo.cpp:179-204), and the wait for the stream. */
+int avt_rforest_labels_download(avt_rforest* rf, int image, unsigned char* labels_out);
+int avt_rforest_labels_download_all(avt_rforest* rf, unsigned char* labels_out);
+int avt_rforest_sync(avt_rforest* rf);
+
+#ifdef __cplusplus
+}
+#endif
+#endif
