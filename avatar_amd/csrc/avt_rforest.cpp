@@ -8,6 +8,7 @@
 
 #include "avt_bgsub_internal.h"
 #include "avt_internal.h"
+#include "avt_rtree_train.h"
 
 namespace {
 
@@ -196,6 +197,102 @@ int predict_best_from_bgsub_impl(avt_rforest* rf, avt_bgsub* bg, int interval, i
     return 0;
 }
 
+// ---- the score (include/avt_rforest.h): a call counts into the scratch matrix and is committed only when no label was refused
+int score_begin(avt_rforest* rf) {
+    const size_t cells = (size_t)(rf->num_parts + 1) * (rf->num_parts + 1);
+    if (rf->d_score.reserve(cells) || rf->d_score_bad.reserve(1)) return 1;
+    AVT_HIP(hipMemsetAsync(rf->d_score, 0, cells * sizeof(unsigned long long), rf->stream));
+    AVT_HIP(hipMemsetAsync(rf->d_score_bad, 0, sizeof(int), rf->stream));
+    return 0;
+}
+
+// waits for the call's kernels (also the contract of avt_renderer_images_for), then adds the scratch matrix to the totals
+int score_commit(avt_rforest* rf, const char* who, int n_images, int rows, int cols, int stride) {
+    const size_t cells = (size_t)(rf->num_parts + 1) * (rf->num_parts + 1);
+    std::vector<unsigned long long> add(cells);
+    int bad = 0;
+    AVT_HIP(hipMemcpyAsync(add.data(), rf->d_score, cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, rf->stream));
+    AVT_HIP(hipMemcpyAsync(&bad, rf->d_score_bad, sizeof(int), hipMemcpyDeviceToHost, rf->stream));
+    AVT_HIP(hipStreamSynchronize(rf->stream));
+    if (bad) {
+        avt_set_error(std::string(who) + ": a part-mask label is >= num_parts (" + std::to_string(rf->num_parts) + ") and not 255; the call's counts were dropped");
+        return 1;
+    }
+    if (rf->score_conf.empty()) rf->score_conf.assign(cells, 0);
+    for (size_t i = 0; i < cells; ++i) rf->score_conf[i] += (long long)add[i];
+    rf->score_images += n_images;
+    rf->score_pixels += (long long)n_images * ((rows - 1) / stride + 1) * ((cols - 1) / stride + 1);
+    return 0;
+}
+
+int score_images_impl(avt_rforest* rf, int n, int rows, int cols, const float* depth, const unsigned char* mask, int stride) {
+    const char* who = "avt_rforest_score_images";
+    if (!rf || !depth || !mask) { avt_set_error(std::string(who) + ": null argument"); return 1; }
+    if (n < 1 || rows < 1 || cols < 1 || stride < 1 || rows >= 32768 || cols >= 32768) {
+        avt_set_error(std::string(who) + ": needs n_images >= 1, stride >= 1 and images of 1 to 32767 rows and columns");
+        return 1;
+    }
+    if (rf->device < 0) { avt_set_error(kHostOnly); return 1; }
+    AVT_HIP(hipSetDevice(rf->device));
+    // staged in buffers of this call, in bounded batches: the resident images and labels are not touched
+    const size_t npix = (size_t)rows * cols;
+    const int batch = (int)std::max<size_t>(1, std::min<size_t>(n, ((size_t)256 << 20) / (npix * 5)));
+    DevBuf<float> d_depth;
+    DevBuf<unsigned char> d_mask;
+    // the temporaries go away on return: no failure leaves work on them queued
+    auto fail = [&]() { avt_set_error(std::string(who) + ": device call failed"); (void)hipStreamSynchronize(rf->stream); return 1; };
+    if (d_depth.reserve(batch * npix) || d_mask.reserve(batch * npix) || score_begin(rf)) return fail();
+    for (int i0 = 0; i0 < n; i0 += batch) {
+        const int k = std::min(batch, n - i0);
+        if (hipMemcpyAsync(d_depth, depth + i0 * npix, k * npix * sizeof(float), hipMemcpyHostToDevice, rf->stream) != hipSuccess ||
+            hipMemcpyAsync(d_mask, mask + i0 * npix, k * npix, hipMemcpyHostToDevice, rf->stream) != hipSuccess ||
+            avt_rforest_launch_score(rf, d_depth, d_mask, k, rows, cols, stride, rf->d_score, rf->d_score_bad) ||
+            hipStreamSynchronize(rf->stream) != hipSuccess)   // the next batch goes into the same buffers
+            return fail();
+    }
+    return score_commit(rf, who, n, rows, cols, stride);
+}
+
+int score_rendered_impl(avt_rforest* rf, avt_renderer* r, int stride) {
+    const char* who = "avt_rforest_score_rendered";
+    if (!rf) { avt_set_error(std::string(who) + ": null forest"); return 1; }
+    if (stride < 1) { avt_set_error(std::string(who) + ": needs stride >= 1"); return 1; }
+    if (rf->device < 0) { avt_set_error(kHostOnly); return 1; }
+    if (!r) { avt_set_error(std::string(who) + ": null renderer"); return 1; }
+    const float* depth = nullptr;
+    const unsigned char* mask = nullptr;
+    int n = 0, w = 0, h = 0;
+    if (avt_renderer_images_for(r, rf->stream, &depth, &mask, &n, &w, &h)) return 1;
+    // from here the forest's stream waits for the renderer; every path below drains it before it returns, as that function asks
+    hipPointerAttribute_t at;
+    int rc = 0;
+    if (hipPointerGetAttributes(&at, depth) != hipSuccess || at.device != rf->device) {
+        (void)hipGetLastError();
+        avt_set_error(std::string(who) + ": the forest and the renderer are on different devices");
+        rc = 1;
+    }
+    if (hipSetDevice(rf->device) != hipSuccess) rc = 1;
+    if (!rc && (h >= 32768 || w >= 32768)) { avt_set_error(std::string(who) + ": images of at most 32767 rows and columns"); rc = 1; }
+    if (!rc && (score_begin(rf) || avt_rforest_launch_score(rf, depth, mask, n, h, w, stride, rf->d_score, rf->d_score_bad))) {
+        avt_set_error(std::string(who) + ": device call failed");
+        rc = 1;
+    }
+    if (rc) { (void)hipStreamSynchronize(rf->stream); return 1; }
+    return score_commit(rf, who, n, h, w, stride);      // the images were read where they lie; the stream has finished
+}
+
+int score_get_impl(avt_rforest* rf, long long* confusion, long long* n_images, long long* n_pixels) {
+    if (!rf) { avt_set_error("avt_rforest_score_get: null forest"); return 1; }
+    const size_t cells = (size_t)(rf->num_parts + 1) * (rf->num_parts + 1);
+    if (confusion) {
+        if (rf->score_conf.empty()) std::fill(confusion, confusion + cells, 0ll);
+        else std::copy(rf->score_conf.begin(), rf->score_conf.end(), confusion);
+    }
+    if (n_images) *n_images = rf->score_images;
+    if (n_pixels) *n_pixels = rf->score_pixels;
+    return 0;
+}
+
 }  // namespace
 
 // ---- exported entry points: no C++ exception crosses the C ABI
@@ -258,6 +355,25 @@ int avt_rforest_sync(avt_rforest* rf) {
     if (rf->device < 0) { avt_set_error(kHostOnly); return 1; }
     AVT_HIP(hipStreamSynchronize(rf->stream));
     return 0;
+}
+
+int avt_rforest_score_reset(avt_rforest* rf) {
+    if (!rf) { avt_set_error("avt_rforest_score_reset: null forest"); return 1; }
+    rf->score_conf.clear();
+    rf->score_images = rf->score_pixels = 0;
+    return 0;
+}
+
+int avt_rforest_score_images(avt_rforest* rf, int n_images, int rows, int cols, const float* depth, const unsigned char* part_mask, int stride) {
+    return avt_guard("avt_rforest_score_images", [&]() -> int { return score_images_impl(rf, n_images, rows, cols, depth, part_mask, stride); });
+}
+
+int avt_rforest_score_rendered(avt_rforest* rf, struct avt_renderer* r, int stride) {
+    return avt_guard("avt_rforest_score_rendered", [&]() -> int { return score_rendered_impl(rf, r, stride); });
+}
+
+int avt_rforest_score_get(avt_rforest* rf, long long* confusion, long long* n_images, long long* n_pixels) {
+    return avt_guard("avt_rforest_score_get", [&]() -> int { return score_get_impl(rf, confusion, n_images, n_pixels); });
 }
 
 }  // extern "C"

@@ -27,6 +27,12 @@ struct avt_rforest {
     int n_images = 0, rows = 0, cols = 0;     // n_images: resident depth images of the forest's own (0 after a hand-over from bgsub)
     int n_labels = 0;                         // images d_labels holds (rows x cols each)
     DevBuf<int> d_boxes;
+    // the score (avt_rforest_score_*): the totals live on the host, a call counts into a scratch matrix on the device and is
+    // added only when its bad-label flag is clear
+    std::vector<long long> score_conf;        // (num_parts + 1)^2, empty until the first good call
+    long long score_images = 0, score_pixels = 0;
+    DevBuf<unsigned long long> d_score;
+    DevBuf<int> d_score_bad;
 };
 
 // distribution form: d_depth is the forest's one resident image, d_out num_parts planes
@@ -35,3 +41,7 @@ int avt_rforest_launch_predict_dist(avt_rforest* rf, int rows, int cols, float* 
 // labels to 255 first; grid sized as avt_rtree_launch_predict / avt_rtree_launch_predict_boxes size theirs
 int avt_rforest_launch_predict(avt_rforest* rf, const float* d_depth, const int* d_boxes, int box_stride, int n_images, int rows, int cols, int interval,
                                int tlx, int tly, int brx, int bry, int fill);
+// the score: (truth, predicted) counts of n_images depth / mask images on the device added to d_conf ((num_parts + 1)^2), d_bad
+// set when a mask byte is >= num_parts and not 255; one lane per pixel of the stride grid
+int avt_rforest_launch_score(avt_rforest* rf, const float* d_depth, const unsigned char* d_mask, int n_images, int rows, int cols, int stride,
+                             unsigned long long* d_conf, int* d_bad);

@@ -10,6 +10,8 @@
 // each part the T table entries are added in tree order, starting from tree 0's value, and the running best is carried
 // (first p with sum > best, best starting at 0.f): T x num_parts cached loads, no per-part accumulators, and for the label
 // form no plane is ever written.  Built with -ffp-contract=off; the probe arithmetic is rt_score_by_feature, unchanged.
+#include <algorithm>
+
 #include "avt_rforest.h"
 #include "avt_rtree_score.h"
 
@@ -119,6 +121,68 @@ __global__ __launch_bounds__(RF_LANES) void k_rforest_dist(const RtNodeDev* __re
     for (int p = 0; p < num_parts; ++p) out[(size_t)p * plane + o] = rf_sum(leaf, col, T, num_parts, p);
 }
 
+// Scoring (include/avt_rforest.h, "THE SCORE"): walk, sum, arg-max, compare with the part mask and count, fused.  One lane per
+// pixel of the stride grid, 16 x 16 of them per workgroup, blockIdx.z the image; the walk is the distribution form's (depth >
+// 0, probes bounded by this image: `d` is the image's own base, so a probe never reads a neighbour of the batch).  The (truth,
+// predicted) pairs are counted in a workgroup histogram in LDS and its non-zero cells are flushed to the call's 64-bit matrix
+// with integer atomics, so the result does not depend on any order.  A workgroup counts at most 256 pairs, so two 16-bit cells
+// share a word (the add is 1 or 1 << 16 and never carries): (P + 1)^2 cells take 32 KiB at P = 127 next to s_state's 16 KiB,
+// below the 64 KiB every launch is granted, and one path serves every P.  A tile with no walked and no labelled pixel leaves
+// before it touches the histogram (an avatar render is mostly background).  No label image, no plane is written.
+__global__ __launch_bounds__(RF_LANES) void k_rforest_score(const RtNodeDev* __restrict__ nodes, const int* __restrict__ roots,
+                                                            const float* __restrict__ leaf, int T, int P, const float* __restrict__ depth,
+                                                            const unsigned char* __restrict__ mask, int rows, int cols, int stride, int gcols,
+                                                            int grows, unsigned long long* __restrict__ conf, int* __restrict__ bad) {
+    __shared__ int s_state[AVT_RFOREST_MAX_TREES * RF_LANES];
+    extern __shared__ unsigned int s_hist[];          // ((P + 1)^2 + 1) / 2 words
+    const int gc = blockIdx.x * 16 + (threadIdx.x & 15), gr = blockIdx.y * 16 + (threadIdx.x >> 4);
+    const size_t base = (size_t)blockIdx.z * rows * cols;
+    const float* d = depth + base;
+    int r = 0, c = 0, t = P;
+    float sample = 0.f;
+    if (gc < gcols && gr < grows) {                   // r <= rows - 1, c <= cols - 1
+        r = gr * stride; c = gc * stride;
+        sample = d[(size_t)r * cols + c];
+        const int m = mask[base + (size_t)r * cols + c];
+        if (m < P) t = m;
+        else if (m != 255) atomicOr(bad, 1);          // refused by the host: the call's counts are dropped
+    }
+    const bool walked = sample > 0.f;                 // zero, negative and NaN depths are not walked
+    if (!__syncthreads_or(walked || t != P)) return;
+    const int words = ((P + 1) * (P + 1) + 1) / 2;
+    for (int i = threadIdx.x; i < words; i += RF_LANES) s_hist[i] = 0u;
+    __syncthreads();
+    int q = P;
+    if (walked) {
+        int* col = s_state + threadIdx.x;
+        rf_walk(nodes, roots, T, col, d, cols, 0, 0, cols - 1, rows - 1, c, r, sample);
+        float best = 0.f;
+        for (int p = 0; p < P; ++p) {
+            const float s = rf_sum(leaf, col, T, P, p);
+            if (s > best) { best = s; q = p; }        // a NaN never wins, a tie stays with the lower index
+        }
+    }
+    const int cell = (t != P || q != P) ? t * (P + 1) + q : -1;
+#ifdef AVT_RF_SCORE_MERGE
+    // timing experiment (libavatar_hip_rf_score_merge.so, tools/rforest_score_measure.py): the lanes of a wave that share a cell
+    // add once, through the lowest of them; same counts
+    for (unsigned long long todo = __ballot(cell >= 0); todo;) {
+        const int lead = __shfl(cell, __ffsll((long long)todo) - 1);
+        const unsigned long long same = __ballot(cell == lead);
+        if ((threadIdx.x & 63) == __ffsll((long long)todo) - 1) atomicAdd(&s_hist[lead >> 1], (unsigned int)__popcll(same) << (16 * (lead & 1)));
+        todo &= ~same;
+    }
+#else
+    if (cell >= 0) atomicAdd(&s_hist[cell >> 1], 1u << (16 * (cell & 1)));
+#endif
+    __syncthreads();
+    for (int i = threadIdx.x; i < words; i += RF_LANES) {
+        const unsigned int w = s_hist[i];
+        if (w & 0xffffu) atomicAdd(&conf[2 * i], (unsigned long long)(w & 0xffffu));
+        if (w >> 16) atomicAdd(&conf[2 * i + 1], (unsigned long long)(w >> 16));       // the cell past an odd count stays 0
+    }
+}
+
 int avt_rforest_launch_predict_dist(avt_rforest* rf, int rows, int cols, float* d_out) {
     dim3 grid((cols + 15) / 16, (rows + 15) / 16);
     hipLaunchKernelGGL(k_rforest_dist, grid, dim3(RF_LANES), 0, rf->stream, rf->d_nodes, rf->d_roots, rf->d_leaf, rf->n_trees, rf->num_parts, rf->d_depth,
@@ -138,4 +202,17 @@ int avt_rforest_launch_predict(avt_rforest* rf, const float* d_depth, const int*
     hipLaunchKernelGGL(k_rforest_label, grid, dim3(RF_LANES), 0, rf->stream, rf->d_nodes, rf->d_roots, rf->d_leaf, rf->n_trees, rf->num_parts, d_depth,
                        rf->d_labels, d_boxes, box_stride, rows, cols, interval, tlx, tly, brx, bry, gcols, grows, fill);
     return hipGetLastError() != hipSuccess;
+}
+
+int avt_rforest_launch_score(avt_rforest* rf, const float* d_depth, const unsigned char* d_mask, int n_images, int rows, int cols, int stride,
+                             unsigned long long* d_conf, int* d_bad) {
+    const int P = rf->num_parts, grows = (rows - 1) / stride + 1, gcols = (cols - 1) / stride + 1;
+    const size_t lds = 4 * (size_t)(((P + 1) * (P + 1) + 1) / 2), npix = (size_t)rows * cols;
+    for (int i0 = 0; i0 < n_images; i0 += 65535) {    // blockIdx.z is the image
+        dim3 grid((gcols + 15) / 16, (grows + 15) / 16, std::min(65535, n_images - i0));
+        hipLaunchKernelGGL(k_rforest_score, grid, dim3(RF_LANES), lds, rf->stream, rf->d_nodes, rf->d_roots, rf->d_leaf, rf->n_trees, P,
+                           d_depth + i0 * npix, d_mask + i0 * npix, rows, cols, stride, gcols, grows, d_conf, d_bad);
+        if (hipGetLastError() != hipSuccess) return 1;
+    }
+    return 0;
 }

@@ -102,6 +102,17 @@ public:
         return img;
     }
 
+    /** renderDepth and renderPartMask in one run, left on the device for a consumer that reads them there
+     *  (RForest::scoreRendered); nothing is downloaded.  False (and a warning) when the avatar has no posed cloud. */
+    bool renderDepthAndPartMaskOnDevice(const Size& image_size, const std::vector<int>& part_map = {}) const {
+        if (!hasCloud()) { noCloudWarning(); return false; }
+        runOn(image_size, AVT_RENDER_DEPTH | AVT_RENDER_PART_MASK, &part_map);
+        return true;
+    }
+
+    /** The C handle of the last render (null before the first one), for the calls that take over its images on the device. */
+    avt_renderer* handle() const { return gpu_.handle; }
+
     /** Index into getOrderedFaces() of the face painted last at every pixel, -1 where none is (AvatarRenderer.cpp:204-217).
      *  num_threads is accepted for source compatibility and ignored. */
     Image<int32_t> renderFaces(const Size& image_size, int num_threads = 1) const {

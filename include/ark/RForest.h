@@ -4,8 +4,13 @@
 // The members are ark::RTree's inference side (predictBest, predictBestBatch, predictBestFromBGSub, predict, postProcess,
 // numParts, partMap, partMapType), so a forest stands where a tree stands (MultiFrameTracker::attachFrontEnd).  As with
 // ark::RTree a failure is fatal (message + exit).
+//
+// The score (avt_rforest.h, THE SCORE) is what rtree-run-dataset leaves to the eye: the forest's arg-max against ground-truth
+// part masks as a (numParts + 1)^2 confusion matrix of 64-bit counts, accumulated on the GPU (scoreReset, score, scoreRendered,
+// scoreGet), and scoreFromAvatar, the held-out counterpart of RTree::trainFromAvatar.
 #pragma once
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -15,10 +20,50 @@
 
 #include "../avt.h"
 #include "../avt_rforest.h"
+#include "AvatarRenderer.h"
 #include "BGSubtractor.h"
 #include "RTree.h"
 
 namespace ark {
+
+/** What RForest::scoreGet returns: the counts and the figures derived from them on the host, in double from the integers.  A
+ *  figure with a zero denominator is NaN; meanIoU is over the parts whose IoU is not NaN. */
+struct ForestScore {
+    int numParts = 0;
+    std::vector<long long> confusion;          // (numParts + 1)^2, row-major conf[truth][predicted]; index numParts = none (255)
+    long long numImages = 0, numPixels = 0;    // numPixels: those the stride selected
+    double accuracy = 0, meanIoU = 0;
+    std::vector<double> recall, precision, iou;
+    long long missed = 0, spurious = 0;        // labelled pixels left unlabelled; background pixels the forest labels
+
+    long long at(int truth, int predicted) const { return confusion[(size_t)truth * (numParts + 1) + predicted]; }
+    /** Fills the derived figures from confusion */
+    void derive() {
+        const int P = numParts;
+        const double nan = std::nan("");
+        auto ratio = [nan](long long a, long long b) { return b ? (double)a / (double)b : nan; };
+        std::vector<long long> row(P, 0), col(P, 0);
+        long long trace = 0, labelled = 0;
+        missed = spurious = 0;
+        for (int t = 0; t <= P; ++t)
+            for (int q = 0; q <= P; ++q) {
+                if (t < P) row[t] += at(t, q);
+                if (q < P) col[q] += at(t, q);
+            }
+        recall.assign(P, nan); precision.assign(P, nan); iou.assign(P, nan);
+        double iouSum = 0;
+        int iouCount = 0;
+        for (int p = 0; p < P; ++p) {
+            trace += at(p, p); labelled += row[p]; missed += at(p, P); spurious += at(P, p);
+            recall[p] = ratio(at(p, p), row[p]);
+            precision[p] = ratio(at(p, p), col[p]);
+            iou[p] = ratio(at(p, p), row[p] + col[p] - at(p, p));
+            if (!std::isnan(iou[p])) { iouSum += iou[p]; ++iouCount; }
+        }
+        accuracy = ratio(trace, labelled);
+        meanIoU = iouCount ? iouSum / iouCount : nan;
+    }
+};
 
 class RForest {
 public:
@@ -86,6 +131,87 @@ public:
     void postProcess(Image8& image, MatrixNX<2>& com_pre, int interval = 1, int num_threads = 1, Point top_left = Point(0, 0),
                      Point bot_right = Point(-1, -1), double dist_to_pre_weight = 0.001) {
         first_->postProcess(image, com_pre, interval, num_threads, top_left, bot_right, dist_to_pre_weight);
+    }
+
+    // ---- the score: a confusion matrix against ground-truth part masks (avt_rforest.h, THE SCORE)
+    /** Puts the totals back to zero */
+    void scoreReset() {
+        if (avt_rforest_score_reset(h_) != 0) die("scoreReset");
+    }
+
+    /** Adds same-size depth images and their part masks (255 = none) to the totals: every pixel of the stride grid */
+    void score(const std::vector<ImageF>& depth, const std::vector<Image8>& part_mask, int stride = 1) {
+        if (depth.empty() || depth.size() != part_mask.size()) fatal("score", "need as many part masks as depth images, at least one");
+        const int rows = depth[0].rows, cols = depth[0].cols;
+        std::vector<float> d;
+        std::vector<uint8_t> m;
+        for (size_t i = 0; i < depth.size(); ++i) {
+            if (depth[i].rows != rows || depth[i].cols != cols || part_mask[i].rows != rows || part_mask[i].cols != cols)
+                fatal("score", "the images must share one size");
+            d.insert(d.end(), depth[i].a.begin(), depth[i].a.end());
+            m.insert(m.end(), part_mask[i].a.begin(), part_mask[i].a.end());
+        }
+        if (avt_rforest_score_images(h_, (int)depth.size(), rows, cols, d.data(), m.data(), stride) != 0) die("score");
+    }
+
+    /** Adds what `renderer` left on the device (AvatarRenderer::renderDepthAndPartMaskOnDevice), read where it lies */
+    void scoreRendered(AvatarRenderer& renderer, int stride = 1) {
+        if (avt_rforest_score_rendered(h_, renderer.handle(), stride) != 0) die("scoreRendered");
+    }
+
+    /** The totals since the last reset and the figures derived from them */
+    ForestScore scoreGet() {
+        ForestScore s;
+        s.numParts = numParts;
+        s.confusion.assign((size_t)(numParts + 1) * (numParts + 1), 0);
+        if (avt_rforest_score_get(h_, s.confusion.data(), &s.numImages, &s.numPixels) != 0) die("scoreGet");
+        s.derive();
+        return s;
+    }
+
+    /** The held-out loop, RTree::trainFromAvatar's with the score in the trainer's place: image idx in [first_image, first_image
+     *  + num_images) is avatar_model posed by Avatar::randomize(true, true, true, idx ^ xorKey) (xorKey = avt_rt_xor_key(seed)),
+     *  skinned by avt_lbs_update into a context of this call, rendered by the GPU renderer with part_map (empty: the joint id
+     *  itself) and scored device to device, `batch` images at a time; no image crosses to the host.  With the training run's
+     *  seed and first_image = its num_images the poses are ones the forest never saw, from the same distribution.  Starts from a
+     *  reset; the result does not depend on `batch`. */
+    ForestScore scoreFromAvatar(AvatarModel& avatar_model, const CameraIntrin& intrin, const Size& image_size, int num_images, int first_image = 0,
+                                const std::vector<int>& part_map = {}, uint64_t seed = 0, int batch = 64, int stride = 1) {
+        const int J = avatar_model.numJoints(), K = avatar_model.numShapeKeys();
+        std::vector<int> pm(part_map);
+        if (pm.empty()) for (int j = 0; j < J; ++j) pm.push_back(j);
+        if ((int)pm.size() < J || num_images < 1 || batch < 1 || first_image < 0)
+            fatal("scoreFromAvatar", "part_map needs one entry per joint; num_images, batch >= 1; first_image >= 0");
+        int np = 0;
+        for (int v : pm) np = v + 1 > np ? v + 1 : np;
+        avt_ctx* ctx = nullptr;
+        avt_renderer* rend = nullptr;
+        if (avt_ctx_create(device_, avatar_model.handle, np, pm.data(), 64, batch, &ctx) != 0 ||
+            avt_renderer_create(device_, avatar_model.handle, image_size.width, image_size.height, intrin.fx, intrin.fy, intrin.cx, intrin.cy, batch,
+                                &rend) != 0 ||
+            avt_renderer_set_part_map(rend, (int)pm.size(), pm.data()) != 0)
+            die("scoreFromAvatar");
+        const uint32_t xorKey = avt_rt_xor_key(seed);
+        Avatar ava(avatar_model);
+        std::vector<double> w, p, R;
+        scoreReset();
+        for (int i0 = first_image; i0 < first_image + num_images; i0 += batch) {
+            const int k = first_image + num_images - i0 < batch ? first_image + num_images - i0 : batch;
+            w.assign((size_t)K * k, 0.0); p.assign((size_t)3 * k, 0.0); R.assign((size_t)9 * J * k, 0.0);
+            for (int i = 0; i < k; ++i) {
+                ava.randomize(true, true, true, (uint32_t)(i0 + i) ^ xorKey);
+                for (int c = 0; c < K; ++c) w[(size_t)i * K + c] = ava.w[c];
+                for (int c = 0; c < 3; ++c) p[(size_t)i * 3 + c] = ava.p(c);
+                for (int j = 0; j < J; ++j)
+                    for (int c = 0; c < 9; ++c) R[((size_t)i * J + j) * 9 + c] = ava.r[j].data()[c];
+            }
+            if (avt_lbs_update(ctx, k, w.data(), p.data(), R.data(), nullptr, nullptr, nullptr) != 0 || avt_renderer_from_ctx(rend, ctx, k, nullptr) != 0 ||
+                avt_renderer_run(rend, AVT_RENDER_DEPTH | AVT_RENDER_PART_MASK) != 0 || avt_rforest_score_rendered(h_, rend, stride) != 0)
+                die("scoreFromAvatar");
+        }
+        avt_renderer_destroy(rend);
+        avt_ctx_destroy(ctx);
+        return scoreGet();
     }
 
     int numTrees = 0;

@@ -22,6 +22,23 @@
  *                      Only the last step differs from one tree: leafBestMatch is replaced by the sum and arg-max above, so
  *                      with T = 1 the labels are avt_rtree_predict_best's wherever the leaf has a positive entry.
  *
+ * THE SCORE.  rtree-run-dataset calls itself an "empirical validation tool": it shows the arg-max image beside the dataset's
+ * part mask.  The score is that comparison in numbers.  Let P = num_parts.  It is a (P + 1) x (P + 1) matrix of 64-bit counts,
+ * row-major as conf[truth][predicted]; index P means "none" (255) on either axis.  Of every image, every pixel (r, c) with
+ * r % stride == 0 and c % stride == 0 is scored (stride >= 1; 1 takes every pixel):
+ *   prediction q  the distribution form's rule and nothing new: a pixel is walked iff depth > 0 (zero, negative and NaN depths
+ *                 are not); probes are bounded by the whole image (stride selects which pixels are scored, never what a probe
+ *                 reads); every tree is walked; sum and arg-max as in THE RULE; q = P when no sum exceeds 0 and for a pixel
+ *                 that is not walked.
+ *   truth t       the mask byte, 255 mapped to P.  A byte >= P that is not 255 is refused, as avt_rtree_transfer_* refuses it:
+ *                 the call fails with a message that names num_parts and adds nothing to the totals, not even the counts of
+ *                 the images before the bad one.
+ *   counting      t == P and q == P counts nothing, so conf[P][P] is always 0; otherwise ++conf[t][q].  Row P holds pixels the
+ *                 forest labels that the truth calls background; column P holds labelled pixels the forest leaves unlabelled
+ *                 (no positive depth, or a leaf sum that is all <= 0 or NaN).
+ * Depth values are taken as they come, as predict takes them.  Totals accumulate over calls until a reset and do not depend on
+ * how the images are split into calls or batches; counts are 64-bit from the first flush out of a workgroup to the caller.
+ *
  * Conventions are avt_rtree.h's: row-major images, float32 depth in metres with 0 = background, uint8 labels with 255 = none,
  * inclusive regions with bot_right.x == -1 for the whole image.  Functions return 0 on success; avt_last_error() (avt.h)
  * describes a failure.
@@ -38,6 +55,7 @@ extern "C" {
 #define AVT_RFOREST_MAX_TREES 16
 
 typedef struct avt_rforest avt_rforest;
+struct avt_renderer;      /* avt_render.h */
 
 /* The models of rtree-run-dataset.cpp:98-104, in this order.  Copies the trees (they may be destroyed afterwards) and uploads
  * the packed forest to `device`; device < 0 makes a host-only forest that validates and answers avt_rforest_info but whose
@@ -71,6 +89,19 @@ int avt_rforest_predict_best_from_bgsub(avt_rforest* rf, struct avt_bgsub* bg, i
 int avt_rforest_labels_download(avt_rforest* rf, int image, unsigned char* labels_out);
 int avt_rforest_labels_download_all(avt_rforest* rf, unsigned char* labels_out);
 int avt_rforest_sync(avt_rforest* rf);
+
+/* THE SCORE above.  The totals start at zero, and score_reset puts them back there. */
+int avt_rforest_score_reset(avt_rforest* rf);
+/* n_images host images of rows x cols: float32 depth and uint8 part masks (255 = none).  They are staged in buffers of the call,
+ * in bounded batches: the resident images and labels of images_upload and of the labelling calls stay as they were. */
+int avt_rforest_score_images(avt_rforest* rf, int n_images, int rows, int cols, const float* depth, const unsigned char* part_mask, int stride);
+/* The depth and part-mask images of r's last run (it must have rendered AVT_RENDER_DEPTH | AVT_RENDER_PART_MASK), read where
+ * they lie: no copy, no image crosses to the host.  Returns after the forest's stream has finished, so the renderer may run
+ * again at once.  Both handles must be on one device. */
+int avt_rforest_score_rendered(avt_rforest* rf, struct avt_renderer* r, int stride);
+/* The totals since the last reset: confusion = (num_parts + 1)^2 counts conf[truth][predicted], the number of images and the
+ * number of pixels the stride selected; zeros on a forest that has scored nothing.  Any pointer may be NULL. */
+int avt_rforest_score_get(avt_rforest* rf, long long* confusion, long long* n_images, long long* n_pixels);
 
 #ifdef __cplusplus
 }
