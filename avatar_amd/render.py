@@ -196,17 +196,24 @@ class AvatarRenderer:
         return self._render(size, FACES)["faces"]
 
 
-def render_streams(tracker, streams, size, intrin, what=LAMBERT, part_map=None):
-    """The last fit of the given streams of a tracker.MultiFrameTracker rendered on the device in one run: a list of download()
-    dicts.  The renderer is kept on the tracker and re-created when the size or the stream count outgrows it."""
+def stream_renderer(tracker, n, size, intrin):
+    """The renderer a tracker.MultiFrameTracker keeps for its own streams: re-created when the size, the camera or the stream
+    count outgrows it."""
     r = getattr(tracker, "_renderer", None)
     W, H = int(size[0]), int(size[1])
-    if r is None or (r.width, r.height) != (W, H) or r.max_images < len(streams) or _intrin(r._intrin) != _intrin(intrin):
-        r = Renderer(tracker.ctx.model, W, H, intrin, max(len(streams), 1), getattr(tracker.ctx, "device", 0))
+    if r is None or (r.width, r.height) != (W, H) or r.max_images < n or _intrin(r._intrin) != _intrin(intrin):
+        r = Renderer(tracker.ctx.model, W, H, intrin, max(n, 1), getattr(tracker.ctx, "device", 0))
         r._intrin = intrin
         tracker._renderer = r
+    return r
+
+
+def render_streams(tracker, streams, size, intrin, what=LAMBERT, part_map=None, download=True):
+    """The last fit of the given streams of a tracker.MultiFrameTracker rendered on the device in one run: a list of download()
+    dicts, or with download=False the renderer itself, its images left on the device for a consumer that reads them there."""
+    r = stream_renderer(tracker, len(streams), size, intrin)
     if what & PART_MASK:
         r.set_part_map(part_map)
     r.from_context(tracker.ctx, list(streams))
     r.run(what)
-    return [r.download(i, what) for i in range(len(streams))]
+    return [r.download(i, what) for i in range(len(streams))] if download else r

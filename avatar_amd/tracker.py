@@ -328,6 +328,27 @@ class MultiFrameTracker:
         from . import render
         return render.render_streams(self, streams, size, intrin, render.LAMBERT if what is None else what, part_map)
 
+    def fit_score(self, streams, size, intrin, tol=None, stride=1, part_map=None):
+        """How well the last fit of the given streams explains the depth images of the last step (avatar_amd.fitscore, the numbers
+        behind the overlay of live-demo.cpp:428-445): depth and part mask of the streams' fit are rendered from the context with
+        the tracker's own renderer and scored on the device against the attached front end's last batch, image streams[i] of it,
+        inside the box that run found.  Returns the (len(streams), numParts + 1, 7) int64 tables (fitscore.metrics derives the
+        figures).  `tol` defaults to fitscore.DEFAULT_TOL, a choice and not a measurement; `part_map` as in render().  Nothing
+        calls this by default and no threshold is offered: a caller who trusts one sets streams[s].reinit = True on it."""
+        from . import fitscore, render
+        if getattr(self, "bgsub", None) is None:
+            raise RuntimeError("MultiFrameTracker.fit_score: no front end attached (attach_front_end)")
+        if self.labels is None:
+            raise RuntimeError("MultiFrameTracker.fit_score: no step behind the front end (process_depth or process_depth_images)")
+        if not self.state_resident:
+            raise RuntimeError("MultiFrameTracker.fit_score: no stream has been fitted yet")
+        streams = [int(s) for s in streams]
+        sc = getattr(self, "_fit_scorer", None)
+        if sc is None or sc.max_images < len(streams):
+            sc = self._fit_scorer = fitscore.FitScorer(self.numParts, max(self.S, len(streams)), getattr(self.ctx, "device", 0))
+        r = render.render_streams(self, streams, size, intrin, render.DEPTH | render.PART_MASK, part_map, download=False)
+        return sc.score_rendered_from_bgsub(r, self.bgsub, streams, fitscore.DEFAULT_TOL if tol is None else tol, stride)
+
     def rotations(self, stream):
         """The stream's joint rotations (J,3,3), as FrameTracker's Avatar.r holds them."""
         return api.quat_to_rot(self.q[stream])

@@ -19,6 +19,7 @@
 #include "../avt_render.h"
 #include "AvatarOptimizer.h"
 #include "BGSubtractor.h"
+#include "FitScore.h"
 #include "RForest.h"
 #include "RTree.h"
 #include "TrackerPolicy.h"
@@ -47,6 +48,7 @@ class MultiFrameTracker {
         device_ = device;
     }
     ~MultiFrameTracker() {
+        delete scorer;
         avt_renderer_destroy(rend);
         if (ctx) avt_ctx_destroy(ctx);
     }
@@ -254,6 +256,22 @@ class MultiFrameTracker {
         return o;
     }
 
+    /** How well the last fit of the given streams explains the depth images of the last step (ark/FitScore.h, the numbers behind
+     *  the overlay of live-demo.cpp:428-445): depth and part mask of the streams' fit are rendered from the context with the
+     *  tracker's own renderer and scored on the device against the attached front end's last batch, image stream_ids[i] of it,
+     *  inside the box that run found.  One FitScore per stream.  Refused without a front end or before a step.  Nothing calls this
+     *  by default; see fitLost (ark/TrackerPolicy.h) for the idiom. */
+    std::vector<FitScore> fitScore(const std::vector<int>& stream_ids, const Size& image_size, const CameraIntrin& intrin,
+                                   float tol = FitScore::kDefaultTol, int stride = 1, const std::vector<int>& part_map = {}) {
+        if (!frontBG || frontBG->batchSize() <= 0 || !stateResident) {
+            std::fprintf(stderr, "MultiFrameTracker::fitScore: needs an attached front end and a fitted step behind it\n");
+            std::exit(1);
+        }
+        render(stream_ids, image_size, intrin, AVT_RENDER_DEPTH | AVT_RENDER_PART_MASK, part_map);
+        if (!scorer) scorer = new FitScorer(numParts, S, device_);
+        return scorer->scoreRenderedFromBGSub(rend, frontBG->handle(), stream_ids, tol, stride);
+    }
+
     const double* pos(int s) const { return &p[3 * (size_t)s]; }
     const double* shape(int s) const { return &w[(size_t)K * s]; }
     const double* quats(int s) const { return &q[4 * (size_t)J * s]; }           // J quaternions (x, y, z, w)
@@ -295,6 +313,7 @@ class MultiFrameTracker {
     avt_renderer* rend = nullptr;                  // render(): created on first use, again when the size or the intrinsics change
     int rendW = 0, rendH = 0;
     CameraIntrin rendIntrin;
+    FitScorer* scorer = nullptr;                   // fitScore(): created on first use
     bool stateResident = false;
     std::vector<CloudType> clouds;
     std::vector<VectorXi> labels;

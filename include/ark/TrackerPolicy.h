@@ -1,6 +1,7 @@
 // ark/TrackerPolicy.h — the per-frame protocol pieces of the reference's trackers (demo.cpp:215-290, live-demo.cpp:376-418) that
 // ark::FrameTracker and ark::MultiFrameTracker share: interval subsampling of a labelled XYZ map, the tracking-loss /
-// reinitialisation decision of one stream, and the start state of a reinitialisation.  Header-only, no OpenCV.
+// reinitialisation decision of one stream, the start state of a reinitialisation, and fitLost, an optional loss test on the fit
+// score.  Header-only, no OpenCV.
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -8,6 +9,7 @@
 #include <vector>
 
 #include "Avatar.h"
+#include "FitScore.h"
 
 namespace ark {
 
@@ -106,6 +108,15 @@ inline void reinitState(const CloudType& dataCloud, size_t cnz, double p[3], std
     Matrix3d r0;
     r0(0, 0) = -1.0; r0(2, 2) = -1.0;
     r[0] = r0;
+}
+
+/** A loss test on the fit score (ark/FitScore.h, MultiFrameTracker::fitScore): true when the image's IoU is below minIoU or its
+ *  violation above maxViolation; a NaN figure (nothing to compare) counts as lost.  Nothing calls it by default and there are no
+ *  default bounds: nobody has measured what a good or a bad fit scores on real data.  A caller who has bounds sets
+ *  `streams[s].reinit = true` on it, which makes the stream's next fitted frame reinitialise, as frameDecision's own loss does. */
+inline bool fitLost(const FitScore& score, double minIoU, double maxViolation) {
+    const FitFigures f = score.derive();
+    return !(f.iou >= minIoU) || !(f.violation <= maxViolation);
 }
 
 }  // namespace ark
