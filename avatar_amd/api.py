@@ -114,7 +114,7 @@ class AvatarModel:
         ijp = np.empty(3 * self.numJoints()); jsr = np.empty(3 * self.numJoints() * self.numShapeKeys())
         check(self._lib.avt_model_joint_regression(self.h, dptr(ijp), dptr(jsr)))
         self.initialJointPos = ijp.reshape(-1, 3)
-        self.jointShapeReg = jsr.reshape(self.numShapeKeys(), -1).T
+        self.jointShapeReg = jsr.reshape(self.numShapeKeys(), 3 * self.numJoints()).T      # (K = 0: an empty (3J, 0) table)
         mj = np.empty(self.numPoints(), np.int32)
         check(self._lib.avt_model_main_joint(self.h, iptr(mj)))
         self.mainJoint = mj

@@ -158,15 +158,15 @@ typedef double d2v __attribute__((ext_vector_type(2)));
 // estimated cost (a batch costs a fixed part for the row builder plus one unit per live tile pair of its matrix phase: hip
 // batches touch ten pairs, torso batches three), so that the workgroups of a frame finish together - k_eval lasts as long as
 // its busiest workgroup.  erange[g] = the first batch whose cost prefix reaches g/G of the frame's total.  Deterministic.
-// s_pre: AVT_ERANGE_CAP + 1 ints of LDS scratch.
+// s_pre: cap + 1 ints of LDS scratch, cap <= AVT_ERANGE_CAP (the smallest systems' LDS holds fewer: k_solve).
 #define AVT_ERANGE_CAP 1024                          // batches a frame can have here (V <= 16384); beyond: equal counts
 template <int NTH>
-__device__ __forceinline__ void eval_ranges(const AvtDims& d, const FrameBuffers& fb, int f, int t, int* __restrict__ s_pre) {
+__device__ __forceinline__ void eval_ranges(const AvtDims& d, const FrameBuffers& fb, int f, int t, int* __restrict__ s_pre, int cap) {
     constexpr int CAP = AVT_ERANGE_CAP;
     __shared__ int s_wsum[NTH / 64];
     const int nb = (fb.ctl[f].M + AVT_EVAL_PTS - 1) / AVT_EVAL_PTS, G = fb.G;
     int* out = fb.erange + (size_t)f * AVT_ERANGE;
-    if (nb > CAP) {
+    if (nb > cap) {
         for (int g = t; g <= G; g += NTH) out[g] = (int)(((long long)g * nb) / G);
         return;
     }
@@ -192,10 +192,10 @@ __device__ __forceinline__ void eval_ranges(const AvtDims& d, const FrameBuffers
     int base = incl - sum;
     for (int w = 0; w < (t >> 6); ++w) base += s_wsum[w];
 #pragma unroll
-    for (int i = 0; i < PER; ++i) { const int b = t * PER + i; if (b < CAP) s_pre[b + 1] = base + loc[i]; }
+    for (int i = 0; i < PER; ++i) { const int b = t * PER + i; if (b < cap) s_pre[b + 1] = base + loc[i]; }
     if (t == 0) s_pre[0] = 0;
     __syncthreads();
-    const long long total = s_pre[min(nb, CAP)];
+    const long long total = s_pre[min(nb, cap)];
     for (int g = t; g <= G; g += NTH) {
         const long long want = (total * g) / G;            // first batch b with prefix(b) = s_pre[b] >= want
         int lo = 0, hi = nb;
@@ -364,7 +364,7 @@ __device__ __forceinline__ void backsub_chain(const double* __restrict__ Lblk, i
     {
         const double q0 = quad_dpp<0x00>(uf0), q1 = quad_dpp<0x55>(uf0), q2 = quad_dpp<0xAA>(uf0), q3 = quad_dpp<0xFF>(uf0);
         const double dl = fma(n0a.x, q0, n0a.y * q1) + fma(n0b.x, q2, n0b.y * q3);
-        s_delta[t] = -dl;
+        if (t < 4 * NB) s_delta[t] = -dl;      // (systems of fewer than 64 rows: the lanes past the last block have no unknown - and s_delta ends at HS + 2, g and D of the predicted decrease lie behind it)
         const double p0 = quad_dpp<0x00>(uf1), p1 = quad_dpp<0x55>(uf1), p2 = quad_dpp<0xAA>(uf1), p3 = quad_dpp<0xFF>(uf1);
         const double dh = fma(n1a.x, p0, n1a.y * p1) + fma(n1b.x, p2, n1b.y * p3);
         if (t + 64 < 4 * NB) s_delta[t + 64] = -dh;
@@ -404,8 +404,11 @@ __device__ __forceinline__ void backsub_tri(const double* __restrict__ Lblk, con
     };
     // (two named buffers swapping roles instead of the copy below cost more than the copy: the kernel runs at 128 registers per lane
     // and the second buffer spilled - 66 k clocks against 40 k)
-    Step nx = fetch(NB - 1);
-    for (int kb = NB - 1; kb >= 0; --kb) {
+    // from the last block with a pivot: with P a multiple of four the last block holds row P alone - no round factored it, its reciprocal
+    // pivots and its diagonal block are whatever the LDS held (a NaN there times the zero unknown poisoned every sum)
+    const int KB0 = ((P + 3) >> 2) - 1;
+    Step nx = fetch(KB0);
+    for (int kb = KB0; kb >= 0; --kb) {
         const Step cu = nx;
         if (kb > 0) nx = fetch(kb - 1);
         const int base = 4 * kb;
@@ -597,6 +600,11 @@ __device__ __forceinline__ bool mf_rounds(v4f64 (&accA)[6], v4f64 (&accB)[2], do
 // rows above the panel read as zero by a select.
 // -------------------------------------------------------------------------------------------------
 #define MFG_SLOTS 5
+// doubles of the area the packed factor and, once it is dead, the skeleton scratch (prep_layout's doubles, the work items, the level table) share
+__host__ __device__ inline size_t solve_tri_area_doubles(size_t nblk, const PrepLayout& L) {
+    const size_t prep = ((size_t)L.ndoubles + (size_t)L.nitems + AVT_MAX_JOINTS + 2 + 1) & ~(size_t)1;
+    return nblk * 18 > prep ? nblk * 18 : prep;
+}
 #define MFG_PB_DOUBLES (192 * MF_PB_STRIDE)
 struct MfgSlots { int rb[MFG_SLOTS], cb[MFG_SLOTS]; };      // rb = -1: empty slot
 
@@ -875,9 +883,13 @@ __global__ __launch_bounds__(NTH) void k_solve(DeviceModel dm_arg, FrameBuffers 
     // (256-thread shape: the small arrays every round of the factorisation touches - panel, reciprocal pivots - lie IN FRONT of the 70 KB factor:
     // below 64 KB an LDS address is an immediate offset of the instruction, above it three instructions that build it in a register)
     const size_t nblk = TRI ? (size_t)NBk * (NBk + 1) / 2 : (size_t)NBk * NBk;
+    const PrepLayout L = prep_layout(J, K, d.xsize);
+    // (triangular shape: the skeleton scratch lies ON the factor and may be the larger of the two - few joints with many shape keys, P = 88 with
+    // K = 13: 46 KB against 39 KB -, so what follows the factor starts behind the larger one: solve_tri_area_doubles, as solve_lds_bytes asks for)
+    const size_t tri_area = solve_tri_area_doubles(nblk, L);
     const size_t small_doubles = (size_t)(TRI ? MFG_PB_DOUBLES : MF_PB_DOUBLES) + ((max(HS, 4 * J) + 3) & ~1) + HS + 2 + (TRI ? 0 : 2 * HS);
     double* Lblk = TRI ? (double*)smem : (double*)smem + small_doubles;
-    double* s_PB = TRI ? Lblk + nblk * 18 : (double*)smem;  // [96 or 192][4] the four panel columns of a round
+    double* s_PB = TRI ? Lblk + tri_area : (double*)smem;  // [96 or 192][4] the four panel columns of a round
     double* s_W = s_PB + (TRI ? MFG_PB_DOUBLES : MF_PB_DOUBLES);         // [max(HS, 4J) + 2]  reciprocal pivots, later the new quaternions
     double* s_delta = s_W + ((max(HS, 4 * J) + 3) & ~1);    // [HS]
     // [2][HS] gradient and diagonal of the undamped system (predicted decrease of the step, gain-ratio schedule); the 1024-thread
@@ -886,7 +898,6 @@ __global__ __launch_bounds__(NTH) void k_solve(DeviceModel dm_arg, FrameBuffers 
     // (SOLVE_DECIDE - the accept test alone, moment form - touches nothing of the above: its launch asks for the two state slots only)
     double* s_gD = s_delta + HS + 2;                        // (256-thread shape) [2][HS]: g | D, left there by the assembly (sys_tile)
     double* s_x = MODE == SOLVE_DECIDE ? (double*)smem : (TRI ? s_gD : Lblk + nblk * 18);      // [2][xsize] both state slots
-    const PrepLayout L = prep_layout(J, K, d.xsize);
     // skeleton scratch: behind the factor (SMPL shape: staged at kernel start, hidden behind the factorisation) or ON it
     // (triangular shape: the factor is dead once the back substitution is done)
     double* B = TRI ? Lblk : s_x + ((2 * d.xsize + 1) & ~1);
@@ -944,7 +955,13 @@ __global__ __launch_bounds__(NTH) void k_solve(DeviceModel dm_arg, FrameBuffers 
         __syncthreads();
         if (t == 0) ctl.try_valid = 1;
         // frame batches: which batches each evaluation workgroup takes (scratch: the end of the factor's area, unused here)
-        if (fb.G < 64) eval_ranges<NTH>(d, fb, f, t, (int*)(Lblk + nblk * 18) - (AVT_ERANGE_CAP + 2));
+        if (fb.G < 64) {
+            if constexpr (TRI) eval_ranges<NTH>(d, fb, f, t, (int*)s_PB, AVT_ERANGE_CAP);      // (the panel buffer: 768 doubles, unused here; the factor's area holds the skeleton scratch)
+            else {      // the end of the factor's area - as much of it as lies inside this workgroup's LDS (HS = 8: 492 of the 513 doubles)
+                const int room = min(AVT_ERANGE_CAP + 2, (int)(2 * (small_doubles + nblk * 18)));
+                eval_ranges<NTH>(d, fb, f, t, (int*)(Lblk + nblk * 18) - room, room - 2);
+            }
+        }
         const double* xc = s_x + cur * xs;
         for (int e = t; e < xs; e += NTH) x0[(size_t)tr * xs + e] = xc[e];
         prep_set_state(d, L, B, xc + 3, xc + 3 + 4 * J, xc);
@@ -1632,9 +1649,10 @@ static size_t solve_lds_bytes(const AvtDims& d) {
     const PrepLayout L = prep_layout(d.J, d.K, d.xsize);
     const size_t nblk = solve_big(d) ? (size_t)NB * (NB + 1) / 2 : (size_t)NB * NB;
     const size_t prep_bytes = sizeof(double) * (size_t)L.ndoubles + sizeof(int) * (2 * (size_t)L.nitems + 2 * AVT_MAX_JOINTS + 4);
+    static_assert(MFG_PB_DOUBLES * 2 >= AVT_ERANGE_CAP + 2, "k_solve<1024, true, SOLVE_INIT> deals the evaluation ranges in the panel buffer");
     const size_t fixed = sizeof(double) * (((std::max(HS, 4 * d.J) + 3) & ~1) + HS + 2 + (solve_big(d) ? 0 : 2 * HS) + ((2 * d.xsize + 1) & ~1));
     const size_t factor = sizeof(double) * nblk * 18;
-    return (solve_big(d) ? std::max(factor, prep_bytes) + sizeof(double) * MFG_PB_DOUBLES + fixed
+    return (solve_big(d) ? sizeof(double) * solve_tri_area_doubles(nblk, L) + sizeof(double) * MFG_PB_DOUBLES + fixed
                          : factor + sizeof(double) * MF_PB_DOUBLES + fixed + prep_bytes) + 64;
 }
 

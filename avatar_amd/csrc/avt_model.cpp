@@ -81,7 +81,7 @@ static void build_tile_layout(avt_model* m, const int* parent) {
     for (int c : children[0]) { std::vector<int> g = pack(c); if (!g.empty()) groups.push_back(g); }
     while ((int)groups.size() > NT - 1) {       // too many branches: merge the two smallest while they fit one tile
         std::stable_sort(groups.begin(), groups.end(), [](const std::vector<int>& a, const std::vector<int>& b) { return a.size() < b.size(); });
-        if (groups[0].size() + groups[1].size() > cap) { plain(); return; }
+        if (groups.size() < 2 || groups[0].size() + groups[1].size() > cap) { plain(); return; }      // (NT = 1 with joints under the root: no tile for a group)
         groups[1].insert(groups[1].end(), groups[0].begin(), groups[0].end());
         groups.erase(groups.begin());
     }
