@@ -294,6 +294,30 @@ class Context:
         check(self._lib.avt_get_visibility(self.h, C.c_int(frame), bptr(vis)))
         return vis
 
+    def set_corr_gate(self, g=None):
+        """avt_set_corr_gate: the maximum correspondence distance (metres) of every search this context runs from now on.  None: off
+        (the default); a scalar: that distance for every part; a sequence of num_parts values: per part (+inf = off for that part).
+        A query further than its part's gate from its nearest visible model point gets no correspondence (-1), as if its part had no
+        visible model point.  Not a reference behaviour; no value is offered."""
+        if g is None:
+            check(self._lib.avt_set_corr_gate(self.h, C.c_int(0), None))
+            return
+        a = np.ascontiguousarray(np.atleast_1d(np.asarray(g, np.float64)).reshape(-1))
+        check(self._lib.avt_set_corr_gate(self.h, C.c_int(len(a)), dptr(a)))
+
+    def corr_gate(self):
+        """The gates in force, float64 (num_parts,), +inf where off (avt_get_corr_gate)."""
+        out = np.empty(self.num_parts)
+        check(self._lib.avt_get_corr_gate(self.h, dptr(out)))
+        return out
+
+    def gated(self, frame=0):
+        """How many queries of `frame`'s last search had a nearest visible model point and lost it to the gate (avt_get_gated); valid
+        where nn_sums is."""
+        n = C.c_int()
+        check(self._lib.avt_get_gated(self.h, C.c_int(frame), C.byref(n)))
+        return int(n.value)
+
     def nn(self, model_cloud, visible, data, labels):
         mc = np.ascontiguousarray(model_cloud, np.float64); vis = np.ascontiguousarray(visible, np.uint8)
         data = np.ascontiguousarray(data, np.float64); labels = np.ascontiguousarray(labels, np.int32)
@@ -613,7 +637,11 @@ class AvatarOptimizer:
 
     renderOcclusion (default False) is NOT a reference member: with enableOcclusion it adds to the back-face test the face-id
     render the reference left commented out at AvatarOptimizer.cpp:1369-1385 (avt_set_occlusion_render, include/avt.h: a vertex
-    is visible iff one of its front-facing faces owns a pixel of renderFaces at intrin / imageSize)."""
+    is visible iff one of its front-facing faces owns a pixel of renderFaces at intrin / imageSize).
+
+    max_corr_dist (default +inf = off) is NOT a reference member either: a data point further than this from the nearest visible model
+    point of its part gets no correspondence (avt_set_corr_gate, include/avt.h); a sequence of numParts values gates per part
+    (set_correspondence_gate).  Followed before every fit; last_gated() tells how many points the last fit's last search dropped."""
 
     ROT_SIZE = 4
 
@@ -629,6 +657,8 @@ class AvatarOptimizer:
         self.enableOcclusion = True                        # :39
         self.renderOcclusion = False                       # not a reference member (:1369-1385, commented out there)
         self._occ_applied = None                           # what the context was last told (avt_set_occlusion_render)
+        self.max_corr_dist = math.inf                      # not a reference member: the correspondence gate (avt_set_corr_gate), off
+        self._gate_applied = None                          # what the context was last told
         self.functionTolerance = 1e-4                      # not a member of the reference's class: what its optimize() hard-codes at AvatarOptimizer.cpp:1333 (0 = no early exit)
         self.r = np.zeros((J, 4)); self.r[:, 3] = 1.0      # quaternions (x,y,z,w), :25
         self.ctx = Context(ava.model, self.numParts, self.partMap, max_points, 1)
@@ -652,9 +682,25 @@ class AvatarOptimizer:
             self.ctx.set_occlusion_render(*(want if want else (None, None)))
             self._occ_applied = want
 
+    def set_correspondence_gate(self, gates):
+        """Per-part gates (numParts distances, +inf = off for that part); the same as assigning the sequence to max_corr_dist."""
+        self.max_corr_dist = [float(v) for v in gates]
+
+    def last_gated(self):
+        """Data points the last search of the last optimize() dropped at the gate (Context.gated)."""
+        return self.ctx.gated(0)
+
+    def _apply_corr_gate(self):
+        g = self.max_corr_dist
+        want = tuple(float(v) for v in g) if np.ndim(g) else (math.inf if g is None else float(g),)
+        if want != self._gate_applied:
+            self.ctx.set_corr_gate(None if want == (math.inf,) else want)
+            self._gate_applied = want
+
     def optimize(self, data_cloud, data_part_labels, icp_iters=1, num_threads=4):
         ava = self.ava
         self._apply_render_occlusion()
+        self._apply_corr_gate()
         self.r = rot_to_quat(ava.r)                                              # :1250-1254
         if icp_iters >= 1:      # one call, one synchronisation: the fit and the outputs of the update() the launch sequence ends with (:1497)
             ava.p, self.r, ava.w, self.last_stats, ava.cloud, ava.jointPos, ava.jointTrans = self.ctx.optimize_posed(

@@ -246,6 +246,9 @@ SIGNATURES = {
     "avt_get_data_term": [_vp],
     "avt_set_occlusion_render": [_vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float],
     "avt_get_visibility": [_vp, C.c_int, c_ubyte_p],
+    "avt_set_corr_gate": [_vp, C.c_int, c_double_p],
+    "avt_get_corr_gate": [_vp, c_double_p],
+    "avt_get_gated": [_vp, C.c_int, c_int_p],
     "avt_debug_trace": [_vp, C.c_int, c_double_p],
     "avt_debug_mfma_count": [_vp, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)],
     "avt_debug_nn_sums": [_vp, C.c_int, c_int_p, C.POINTER(C.c_longlong), c_double_p],

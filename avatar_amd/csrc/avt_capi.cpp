@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 
 #include <memory>
 #include <mutex>
@@ -702,6 +703,15 @@ static int ctx_create_impl(int device, const avt_model* m, int num_parts, const 
         if (dev_alloc(c, &pr, 1)) return 1;
         fb.params = pr;
     }
+    {   // the correspondence gate (avt_set_corr_gate): off, i.e. +inf for every part
+        double* g2 = nullptr;
+        if (dev_alloc(c, &g2, (size_t)num_parts) || dev_alloc(c, &fb.gated, (size_t)max_frames)) return 1;
+        fb.gate2 = g2;
+        c->gate_host.assign((size_t)num_parts, std::numeric_limits<double>::infinity());
+        c->gate2_host = c->gate_host;
+        AVT_HIP(hipMemcpyAsync(g2, c->gate2_host.data(), (size_t)num_parts * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        AVT_HIP(hipMemsetAsync(fb.gated, 0, (size_t)max_frames * sizeof(int), c->stream));
+    }
     fb.spec_frames = std::min(max_frames, AVT_SPEC_FRAMES);
     if (dev_alloc(c, &fb.partial_spec, (size_t)fb.spec_frames * AVT_MAX_SPEC * AVT_G_MAX * 256) || dev_alloc(c, &fb.wmask_spec, (size_t)fb.spec_frames * AVT_MAX_SPEC * AVT_G_MAX) ||
         dev_alloc(c, &fb.prior_spec, (size_t)fb.spec_frames * AVT_MAX_SPEC * AVT_MAX_COMPS * AVT_PRIOR_STRIDE))
@@ -1242,6 +1252,56 @@ int avt_set_occlusion_render(avt_ctx* c, int width, int height, float fx, float 
         c->occ_fkey = std::move(fkey); c->occ_proj = std::move(proj); c->occ_front = std::move(front);
         c->occ_w = width; c->occ_h = width > 0 ? height : 0;
         c->occ_fx = fx; c->occ_fy = fy; c->occ_cx = cx; c->occ_cy = cy;
+        return 0;
+    });
+}
+
+int avt_set_corr_gate(avt_ctx* c, int n, const double* max_dist) {
+    return avt_guard("avt_set_corr_gate", [&]() -> int {
+        if (!c) { avt_set_error("avt_set_corr_gate: null context"); return 1; }
+        const int np = c->dm.d.num_parts;
+        if (!max_dist) n = 0;
+        if (n != 0 && n != 1 && n != np) {
+            avt_set_error("avt_set_corr_gate: " + std::to_string(n) + " values; 0 (off), 1 (every part) or num_parts = " + std::to_string(np) + " wanted");
+            return 1;
+        }
+        for (int i = 0; i < n; ++i)
+            if (!(max_dist[i] >= 0.0)) {      // (a NaN fails every comparison)
+                avt_set_error("avt_set_corr_gate: value " + std::to_string(i) + " is negative or not a number (each of the 1 or num_parts = " + std::to_string(np) +
+                              " gates is a distance >= 0, +inf allowed)");
+                return 1;
+            }
+        std::vector<double> g((size_t)np, std::numeric_limits<double>::infinity()), g2((size_t)np);
+        for (int q = 0; q < np && n > 0; ++q) g[(size_t)q] = max_dist[n == 1 ? 0 : q];
+        for (int q = 0; q < np; ++q) g2[(size_t)q] = g[(size_t)q] * g[(size_t)q];
+        c->gate_host = g;
+        if (std::memcmp(g2.data(), c->gate2_host.data(), (size_t)np * sizeof(double)) == 0) return 0;      // what the device holds already
+        AVT_HIP(hipSetDevice(c->device));
+        AVT_HIP(hipStreamSynchronize(c->stream));      // (nothing queued reads gate2_host any more)
+        c->gate2_host = g2;
+        // on the context's stream, behind every search already queued; not part of the launch shape: the captured graphs stay valid
+        AVT_HIP(hipMemcpyAsync((void*)c->fb.gate2, c->gate2_host.data(), (size_t)np * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        AVT_HIP(hipStreamSynchronize(c->stream));      // gate2_host may be rewritten by the next call
+        return 0;
+    });
+}
+
+int avt_get_corr_gate(avt_ctx* c, double* max_dist) {
+    if (!c || !max_dist) { avt_set_error("avt_get_corr_gate: null argument"); return 1; }
+    std::copy(c->gate_host.begin(), c->gate_host.end(), max_dist);
+    return 0;
+}
+
+int avt_get_gated(avt_ctx* c, int frame, int* gated) {
+    return avt_guard("avt_get_gated", [&]() -> int {
+        if (!c || !gated || frame < 0 || frame >= c->fb.max_frames) { avt_set_error("avt_get_gated: bad argument"); return 1; }
+        // like the counts and sums (avt_debug_nn_sums): what the last search left, a stand-alone avt_nn in frame 0
+        const bool after_nn = c->nn_sums_frame0 && !c->frames_valid && frame == 0;
+        const bool after_opt = c->frames_valid && c->ran_icp_iters > 0 && frame < c->nframes;
+        if (!after_nn && !after_opt) { avt_set_error("avt_get_gated: neither a stand-alone avt_nn (frame 0) nor an optimize call with an ICP iteration has run last"); return 1; }
+        AVT_HIP(hipSetDevice(c->device));
+        AVT_HIP(hipMemcpyAsync(gated, c->fb.gated + frame, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        AVT_HIP(hipStreamSynchronize(c->stream));
         return 0;
     });
 }

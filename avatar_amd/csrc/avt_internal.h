@@ -340,6 +340,10 @@ struct FrameBuffers {
     double* mom_E;        // [max_frames][2] sum_m |fsum_m|^2 / c_m
     double* mom_rec;      // [max_frames][avt_moments_frame_scratch] what k_pairpass hands to k_assemble (avt_moments.hip)
     int use_moments;      // the GN iterations take their normal equations from the moments (k_assemble) instead of k_eval + k_reduce
+    // the correspondence gate (avt_nn.hip; behind everything else: no kernel's argument layout moved when it came)
+    const double* gate2;  // [num_parts] the correspondence gate of every part, SQUARED (avt_set_corr_gate; +inf = off): in device memory, not a
+                          // kernel argument value, so that a tracker that changes it replays the same captured graphs (like params)
+    int* gated;           // [max_frames] queries of the frame's last search that had a nearest visible model point and lost it to the gate
 };
 
 struct avt_model {
@@ -387,6 +391,7 @@ struct avt_ctx {
     std::vector<GraphEntry> graphs;     // small LRU cache keyed on the launch SHAPE only (frames, groups, grids, iteration counts)
     unsigned long long graph_clock = 0;
     AvtRunParams params_host = {};      // what fb.params currently holds
+    std::vector<double> gate_host, gate2_host;   // the gates as avt_set_corr_gate was given them (num_parts, +inf = off) and what fb.gate2 holds
     bool params_valid = false;
     bool frames_valid = false, state_valid = false;   // resident frames / start state usable by avt_optimize_resident
     bool nn_sums_frame0 = false;        // a stand-alone avt_nn has left its counts and sums in frame slot 0 (avt_debug_nn_sums)

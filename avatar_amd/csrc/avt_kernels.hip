@@ -185,6 +185,7 @@ __global__ __launch_bounds__(256) void k_lbs(DeviceModel dm, FrameBuffers fb, co
         fb.cnt[(size_t)f * V + v] = 0;
         long long* fs = fb.fsum + (size_t)f * 3 * V;
         fs[v] = 0; fs[(size_t)V + v] = 0; fs[2 * (size_t)V + v] = 0;
+        if (v == 0) fb.gated[f] = 0;      // the frame's gated count goes with its counts (avt_nn.hip)
     }
     if (dm.part_pos && write_pc) {     // the part-sorted copy k_nn_vis scans (few frames; frame batches gather from the cloud in k_compact)
         const int pp = dm.part_pos[v];
@@ -366,6 +367,7 @@ __global__ __launch_bounds__(256) void k_lbs_multi(DeviceModel dm, FrameBuffers 
             fb.cnt[(size_t)f * V + v] = 0;
             long long* fs = fb.fsum + (size_t)f * 3 * V;
             fs[v] = 0; fs[(size_t)V + v] = 0; fs[2 * (size_t)V + v] = 0;
+            if (v == 0) fb.gated[f] = 0;
         }
         if (pp >= 0) {
             if (vis_init >= 0) fb.vis_sorted[(size_t)f * V + pp] = (unsigned char)vis_init;

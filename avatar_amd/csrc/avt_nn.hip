@@ -43,6 +43,15 @@ __device__ __forceinline__ long long rint_to_ll(double x) {
     return __double_as_longlong(x + C) - __double_as_longlong(C);
 }
 
+// ---- the correspondence gate (avt_set_corr_gate).  Applied to the WINNER of a search, after the scan: a query whose
+// exact minimum squared distance d2 exceeds g2 = gate * gate of its part loses its match and is from here on a query whose part has no
+// visible model point.  g2 = +inf (the default) makes the test false for every d2, NaN included: nothing changes.  It is never a search
+// bound.  The frame's count of such queries: one ballot and one popcount per wave, one integer atomic per wave that gated something.
+__device__ __forceinline__ void nn_count_gated(const FrameBuffers& fb, int f, bool drop) {
+    const unsigned long long bal = __ballot(drop);
+    if (bal != 0ull && lane_id() == (int)__ffsll((long long)bal) - 1) atomicAdd(fb.gated + f, __popcll(bal));
+}
+
 // ---- correspondence bookkeeping.  Neighbouring pixels usually hit the same model vertex, so runs of equal
 // vertices among the wave's consecutive queries are merged first (segmented inclusive scan over the query lanes,
 // integer adds: order-independent) and only the last lane of each run issues the global atomics (which are what this
@@ -119,6 +128,8 @@ __global__ __launch_bounds__(256) void k_nn(DeviceModel dm, FrameBuffers fb) {
 
     __shared__ double c_x[NN_TILE], c_y[NN_TILE], c_z[NN_TILE];
     __shared__ int s_qlo, s_qhi;
+    __shared__ double s_g2[AVT_MAX_PARTS];      // the parts' gates: one coalesced load per workgroup, read from LDS once the winner is known
+    if (t < np) s_g2[t] = fb.gate2[t];
     // part of the first / last point of this workgroup (binary search over part_off)
     if (t == 0) {
         int lo = 0, hi = np - 1;
@@ -210,7 +221,10 @@ __global__ __launch_bounds__(256) void k_nn(DeviceModel dm, FrameBuffers fb) {
         const int oi = __shfl_xor(bi, m, 64);
         if (ob < best || (ob == best && oi < bi)) { best = ob; bi = oi; }
     }
-    const int mv = (active && sub == 0 && bi != 0x7fffffff) ? fb.vcid[(size_t)f * V + bi] : -1;
+    const bool has = active && sub == 0 && bi != 0x7fffffff;
+    const bool drop = has && best > s_g2[q];
+    nn_count_gated(fb, f, drop);
+    const int mv = (has && !drop) ? fb.vcid[(size_t)f * V + bi] : -1;
     nn_record<LANES>(fb, ctl, f, V, base, s, active, sub, mv, a0, a1, a2);
 }
 
@@ -242,6 +256,8 @@ __global__ __launch_bounds__(256) void k_nn_vis(DeviceModel dm, FrameBuffers fb)
     __shared__ double c_x[NN_TILE], c_y[NN_TILE], c_z[NN_TILE];
     __shared__ int c_id[NN_TILE], s_pre[NN_TILE + 4], s_wtot[4];
     __shared__ int s_qlo, s_qhi;
+    __shared__ double s_g2[AVT_MAX_PARTS];      // the parts' gates: one coalesced load per workgroup, read from LDS once the winner is known
+    if (t < np) s_g2[t] = fb.gate2[t];
     if (t == 0) {
         int lo = 0, hi = np - 1;
         while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (po[mid] <= s0) lo = mid; else hi = mid - 1; }
@@ -349,7 +365,9 @@ __global__ __launch_bounds__(256) void k_nn_vis(DeviceModel dm, FrameBuffers fb)
         const int ok = __shfl_xor(bkey, m, 64), ov = __shfl_xor(bv, m, 64);
         if (ob < best || (ob == best && ok < bkey)) { best = ob; bkey = ok; bv = ov; }
     }
-    nn_record<LANES>(fb, ctl, f, V, base, s, active, sub, bv, a0, a1, a2);
+    const bool drop = active && sub == 0 && bv >= 0 && best > s_g2[q];
+    nn_count_gated(fb, f, drop);
+    nn_record<LANES>(fb, ctl, f, V, base, s, active, sub, drop ? -1 : bv, a0, a1, a2);
 }
 
 // max over the wave of NON-NEGATIVE doubles, identical in every lane's return value: row_shr scans inside the rows of 16 lanes
@@ -442,6 +460,7 @@ __global__ __launch_bounds__(256) void k_nn_part(DeviceModel dm, FrameBuffers fb
     const int pb = __builtin_amdgcn_readfirstlane(dm.part_start[q]);
     const int vc = __builtin_amdgcn_readfirstlane(fb.vcount[(size_t)f * np + q]);
     const bool sorted = (vc & NN_SORTED_FLAG) != 0;                    // k_compact sorted them by (y, vertex id): slab scan below
+    const double g2 = fb.gate2[q];                                      // the part's gate (wave-uniform; used once the winners are known)
 #ifdef AVT_NN_NO_SCAN          // (timing experiment: no candidate is looked at - what remains is the kernel's per-wave fixed work)
     const int pe = pb;
 #else
@@ -597,7 +616,12 @@ __global__ __launch_bounds__(256) void k_nn_part(DeviceModel dm, FrameBuffers fb
     }
     int mv[NQ];
 #pragma unroll
-    for (int u = 0; u < NQ; ++u) mv[u] = (active[u] && bi[u] != 0x7fffffff) ? fb.vcid[(size_t)f * V + bi[u]] : -1;
+    for (int u = 0; u < NQ; ++u) {
+        const bool has = active[u] && bi[u] != 0x7fffffff;
+        const bool drop = has && best[u] > g2;         // best[u]: the scan's own minimum, the tie rescan leaves it alone
+        nn_count_gated(fb, f, drop);
+        mv[u] = (has && !drop) ? fb.vcid[(size_t)f * V + bi[u]] : -1;
+    }
     if (pe - pb > NN_ACC_CAP) {        // a part with more candidates than the accumulators below hold: per-match atomics, merged in-wave
 #pragma unroll
         for (int u = 0; u < NQ; ++u) nn_record<1>(fb, ctl, f, V, base, s[u], active[u], 0, mv[u], a0[u], a1[u], a2[u]);
@@ -761,6 +785,7 @@ void launch_nn(avt_ctx* c, int nframes) {
     if (!c->lbs_cleared) {   // stand-alone avt_nn(): no preceding k_lbs cleared the bookkeeping
         (void)hipMemsetAsync(c->fb.cnt + (size_t)c->fb.f0 * V, 0, (size_t)nframes * V * sizeof(int), c->cur_stream);
         (void)hipMemsetAsync(c->fb.fsum + (size_t)c->fb.f0 * 3 * V, 0, (size_t)nframes * 3 * V * sizeof(long long), c->cur_stream);
+        (void)hipMemsetAsync(c->fb.gated + c->fb.f0, 0, (size_t)nframes * sizeof(int), c->cur_stream);
     }
     const int maxN = c->launch_maxN;
     if (maxN <= 0) return;

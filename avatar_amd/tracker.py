@@ -81,10 +81,14 @@ def reinit_state(data, num_joints, num_shape_keys):
 class FrameTracker:
     def __init__(self, ava_opt: "api.AvatarOptimizer", interval=12, frame_icp_iters=3, reinit_icp_iters=6, reinit_cnz=1000,
                  num_threads=4, rtree=None, rtree_interval=2, dist_to_pre_weight=0.001, initial_per_part_cnz=0, initial_icp_iters=None,
-                 render_occlusion=None):
+                 render_occlusion=None, max_corr_dist=None):
         """render_occlusion: True / False sets ava_opt.renderOcclusion (self-occlusion from a face-id render at the optimizer's own
-        intrin and imageSize; not a reference behaviour); None leaves it as it is."""
+        intrin and imageSize; not a reference behaviour); None leaves it as it is.
+        max_corr_dist: a distance or numParts distances sets ava_opt.max_corr_dist (the correspondence gate, api.Context.set_corr_gate;
+        not a reference behaviour); None leaves it as it is."""
         self.opt = ava_opt
+        if max_corr_dist is not None:
+            ava_opt.max_corr_dist = max_corr_dist
         if render_occlusion is not None:
             ava_opt.renderOcclusion = bool(render_occlusion)
         self.ava = ava_opt.ava
@@ -177,10 +181,14 @@ class MultiFrameTracker:
 
     def __init__(self, ctx, num_streams, interval=12, frame_icp_iters=3, reinit_icp_iters=6, reinit_cnz=1000, initial_per_part_cnz=0,
                  initial_icp_iters=None, beta_pose=0.1, beta_shape=1.0, max_iters_per_icp=10, enable_occlusion=True,
-                 function_tolerance=1e-4, render_occlusion=None):
+                 function_tolerance=1e-4, render_occlusion=None, max_corr_dist=None):
         """render_occlusion: None (off), or (intrin, (width, height)): self-occlusion visibility from a face-id render with that camera
-        (api.Context.set_occlusion_render; not a reference behaviour).  `renderOcclusion` holds it; set_render_occlusion changes it."""
+        (api.Context.set_occlusion_render; not a reference behaviour).  `renderOcclusion` holds it; set_render_occlusion changes it.
+        max_corr_dist: None (the context's gate is left as it is), or a distance / numParts distances: the correspondence gate of every
+        stream (api.Context.set_corr_gate; not a reference behaviour).  set_corr_gate changes it; ctx.corr_gate() tells what is in force."""
         self.ctx = ctx
+        if max_corr_dist is not None:
+            self.set_corr_gate(max_corr_dist)
         self.renderOcclusion = None
         if render_occlusion:
             self.set_render_occlusion(render_occlusion)
@@ -215,6 +223,10 @@ class MultiFrameTracker:
             intrin, size = render_occlusion
             self.ctx.set_occlusion_render(size, intrin)
             self.renderOcclusion = (intrin, tuple(size))
+
+    def set_corr_gate(self, max_corr_dist):
+        """None: off; a distance or numParts distances: one gate for all streams.  Takes effect for the following steps."""
+        self.ctx.set_corr_gate(max_corr_dist)
 
     def options(self, icp_iters):
         o = api.Options.reference_defaults()

@@ -1,5 +1,6 @@
 // ark/AvatarOptimizer.h — the reference's `ark::AvatarOptimizer` (include/AvatarOptimizer.h:11-61) on top of the C ABI.
 #pragma once
+#include <limits>
 #include <vector>
 
 #include "Avatar.h"
@@ -31,10 +32,18 @@ class AvatarOptimizer {
             capacity = N > 65536 ? N : 65536;
             ARK_AVT_CHECK(avt_ctx_create(ava.device, ava.model.handle, numParts, partMap.data(), capacity, 1, &ctx));
             occlusionRenderSet = false;
+            gateSet.clear();
         }
         if (renderOcclusion != occlusionRenderSet) {       // the context follows the member (a new context starts with the mode off)
             ARK_AVT_CHECK(avt_set_occlusion_render(ctx, renderOcclusion ? imageSize.width : 0, imageSize.height, intrin.fx, intrin.fy, intrin.cx, intrin.cy));
             occlusionRenderSet = renderOcclusion;
+        }
+        {   // the correspondence gate: per-part values when given, else the one member for every part (a new context starts with it off)
+            const std::vector<double> want = partGates.empty() ? std::vector<double>(1, maxCorrespondenceDist) : partGates;
+            if (want != gateSet && !(gateSet.empty() && want.size() == 1 && want[0] == std::numeric_limits<double>::infinity())) {
+                ARK_AVT_CHECK(avt_set_corr_gate(ctx, (int)want.size(), want.data()));
+                gateSet = want;
+            }
         }
         for (int i = 0; i < J; ++i) r[i] = rotationToQuaternion(ava.r[i]);       // :1250-1254
         avt_options o;
@@ -68,6 +77,15 @@ class AvatarOptimizer {
         return v;
     }
 
+    /** Per-part correspondence gates (numParts distances, +inf = off for that part); an empty vector returns to maxCorrespondenceDist */
+    void setCorrespondenceGate(const std::vector<double>& gates) { partGates = gates; }
+    /** Data points the last search of the last optimize() dropped at the gate (avt_get_gated) */
+    int lastGated() const {
+        int n = 0;
+        ARK_AVT_CHECK(avt_get_gated(ctx, 0, &n));
+        return n;
+    }
+
     /** Rotation representation size */
     static const int ROT_SIZE = 4;
     /** Optimization parameter r */
@@ -85,6 +103,11 @@ class AvatarOptimizer {
      *  of renderFaces(imageSize) of the current cloud at `intrin` (include/avt.h, avt_set_occlusion_render): a body part in front
      *  of another hides it.  Off by default; takes effect at the next optimize(). */
     bool renderOcclusion = false;
+    /** NOT a member of the reference's class, whose findNN keeps the nearest visible model point of a data point's part however far
+     *  away it is: a data point further than this (metres) from that model point gets no correspondence in any ICP iteration, as if
+     *  its part had no visible model point (include/avt.h, avt_set_corr_gate).  +inf (default) = off; no value is offered.  Followed
+     *  before every optimize(); setCorrespondenceGate gives per-part values. */
+    double maxCorrespondenceDist = std::numeric_limits<double>::infinity();
     /** Not a member of the reference's class: the value its optimize() hard-codes as options.function_tolerance
      *  (AvatarOptimizer.cpp:1333) - a step that lowers the objective by no more than this fraction ends the inner iterations
      *  of the ICP iteration; 0 = always maxItersPerICP iterations (include/avt.h, avt_options::function_tolerance) */
@@ -104,5 +127,7 @@ class AvatarOptimizer {
     avt_ctx* ctx = nullptr;
     int capacity = 0;
     bool occlusionRenderSet = false;   // what ctx was last told
+    std::vector<double> partGates;     // setCorrespondenceGate (empty: maxCorrespondenceDist for every part)
+    std::vector<double> gateSet;       // the gate ctx was last told (empty: never told, i.e. off)
 };
 }  // namespace ark

@@ -55,6 +55,7 @@ class FrameTracker {
             ava.update();
         }
         if (renderOcclusion >= 0) avaOpt.renderOcclusion = renderOcclusion != 0;
+        if (maxCorrespondenceDist >= 0) avaOpt.maxCorrespondenceDist = maxCorrespondenceDist;
         avaOpt.optimize(dataCloud, dataPartLabels, icpIters, numThreads);
         ++framesFitted;
         return true;
@@ -75,6 +76,9 @@ class FrameTracker {
     /** not a reference member: 1 / 0 sets avaOpt.renderOcclusion before every fit (self-occlusion from a face-id render with the
      *  optimizer's own intrin and imageSize, AvatarOptimizer.cpp:1369-1385); -1 (default) leaves the optimizer's member alone */
     int renderOcclusion = -1;
+    /** not a reference member: a value >= 0 (+inf = off) sets avaOpt.maxCorrespondenceDist before every fit (the correspondence gate,
+     *  include/avt.h avt_set_corr_gate); negative (default) leaves the optimizer's member alone */
+    double maxCorrespondenceDist = -1.0;
 
     AvatarOptimizer& avaOpt;
     Avatar& ava;

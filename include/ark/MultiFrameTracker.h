@@ -63,6 +63,20 @@ class MultiFrameTracker {
         renderOcclusion = on;
         if (on) { occlusionSize = image_size; occlusionIntrin = intrin; }
     }
+    /** Not a reference behaviour: the correspondence gate of every stream (include/avt.h, avt_set_corr_gate) - one distance for every
+     *  part, or numParts distances; +inf / an empty vector = off.  Takes effect for the following steps; `correspondenceGate` tells
+     *  what is in force (empty: off). */
+    void setCorrespondenceGate(double max_dist) { setCorrespondenceGate(std::vector<double>(1, max_dist)); }
+    void setCorrespondenceGate(const std::vector<double>& gates) {
+        ARK_AVT_CHECK(avt_set_corr_gate(ctx, (int)gates.size(), gates.data()));
+        correspondenceGate = gates;
+    }
+    /** queries the last search of the last step dropped at the gate on stream s (avt_get_gated) */
+    int lastGated(int s) const {
+        int n = 0;
+        ARK_AVT_CHECK(avt_get_gated(ctx, s, &n));
+        return n;
+    }
     /** the visibility flags (numPoints bytes) of the last ICP iteration of the last step on stream s (avt_get_visibility) */
     std::vector<unsigned char> visibility(int s) const {
         std::vector<unsigned char> v((size_t)model.numPoints());
@@ -290,6 +304,7 @@ class MultiFrameTracker {
     bool renderOcclusion = false;                  // read-only: set by setRenderOcclusion, with the camera below
     Size occlusionSize;
     CameraIntrin occlusionIntrin;
+    std::vector<double> correspondenceGate;        // read-only: set by setCorrespondenceGate (empty: off)
     std::vector<int> budgets, reinitStreams;       // of the last step (0 = not fitted)
     // processDepth: per stream the previous centres of mass (demo.cpp:148), the last step's box and post-processed labels
     std::vector<MatrixNX<2>> comPre;

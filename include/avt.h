@@ -186,6 +186,25 @@ int avt_set_occlusion_render(avt_ctx* c, int width, int height, float fx, float 
 int avt_nn(avt_ctx* c, const double* model_cloud_3xV, const unsigned char* visible,
            const double* data_3xN, const int* labels, int N, int* model_idx_out);
 
+/* ---- a maximum correspondence distance per part (NOT a reference behaviour: findNN keeps the nearest visible model point however far
+ * away it is; decided here).  The context holds one gate g[q] >= 0 per part, in metres, +inf allowed and the
+ * default (off).  In every search the context runs afterwards - each ICP iteration of avt_optimize*, the resident and budget calls,
+ * the stand-alone avt_nn - a query of part q whose search found the nearest visible model point m at squared distance d2 (the search's
+ * own minimum: r = d0*d0; r += d1*d1; r += d2*d2, each operation rounded) keeps m iff d2 <= g[q] * g[q] (one double multiplication on
+ * the host); otherwise it is, for everything downstream, a query whose part has no visible model point: -1 in the correspondences,
+ * nothing in the counts and sums, not counted in avt_stats::num_correspondences nor in the rescaling of the priors.  The gate is applied
+ * to the winner and never prunes the search: ties and the choice of m are untouched, and with +inf results are bit for bit those
+ * without the call.  n == 0 or max_dist == NULL: off; n == 1: max_dist[0] for every part; n == num_parts: per part.  Any other n, a NaN
+ * or a negative value is refused and the previous setting stays in force.  The values are uploaded on the context's stream and are not
+ * part of the launch shape: captured graphs keep replaying.  No value is offered: every gate comes from the caller.
+ * avt_get_corr_gate returns the num_parts gates as given (+inf where off).
+ * avt_get_gated: the number of queries of `frame`'s last search that had a nearest visible model point and lost it to the gate; with
+ * it, queries with a valid label and a non-empty visible part == num_correspondences + gated.  Valid where the counts of
+ * avt_debug_nn_sums are (after avt_nn for frame 0, after an optimize call with an ICP iteration), refused otherwise. */
+int avt_set_corr_gate(avt_ctx* c, int n, const double* max_dist);
+int avt_get_corr_gate(avt_ctx* c, double* max_dist_num_parts);
+int avt_get_gated(avt_ctx* c, int frame, int* gated);
+
 /* ---- AvatarOptimizer::optimize() (AvatarOptimizer.cpp:1246-1517), one frame.
  * In/out: p (3), q (4 x J, xyzw), w (K).  The caller converts ava.r <-> q (AvatarOptimizer.cpp:1250-1254,
  * :1494-1496; done by the C++ facade).  stats may be NULL. */

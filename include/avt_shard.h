@@ -18,6 +18,9 @@
  * Rendezvous: rank 0 calls avt_shard_unique_id() and hands the 128 opaque bytes to the other ranks by whatever
  * out-of-band channel the host program has (the torch.distributed store in bench.py, a file or MPI in a C++ host);
  * every rank then calls avt_shard_create().  One shard handle per process / GPU; not thread-safe.
+ *
+ * Per-context settings are not exchanged: the correspondence gate (avt_set_corr_gate), like the render occlusion and the data-term
+ * form, belongs to each rank's own context, and each rank's caller sets it there.  The split itself needs nothing for them.
  */
 #ifndef AVT_SHARD_H_
 #define AVT_SHARD_H_
