@@ -357,6 +357,34 @@ int avt_rforest_sync(avt_rforest* rf) {
     return 0;
 }
 
+int avt_rforest_labels_upload(avt_rforest* rf, int n_images, int rows, int cols, const unsigned char* labels) {
+    return avt_guard("avt_rforest_labels_upload", [&]() -> int { return avt_post_labels_upload(rf, "avt_rforest_labels_upload", n_images, rows, cols, labels); });
+}
+
+int avt_rforest_post_process_resident(avt_rforest* rf, int interval, const int* boxes, double dist_to_pre_weight) {
+    return avt_guard("avt_rforest_post_process_resident", [&]() -> int { return avt_post_resident(rf, "avt_rforest_post_process_resident", interval, boxes, dist_to_pre_weight); });
+}
+
+int avt_rforest_post_process_from_bgsub(avt_rforest* rf, avt_bgsub* bg, int interval, double dist_to_pre_weight) {
+    return avt_guard("avt_rforest_post_process_from_bgsub", [&]() -> int { return avt_post_from_bgsub(rf, bg, "avt_rforest_post_process_from_bgsub", interval, dist_to_pre_weight); });
+}
+
+int avt_rforest_com_pre_set(avt_rforest* rf, int first, int n, const double* com, const unsigned char* valid) {
+    return avt_guard("avt_rforest_com_pre_set", [&]() -> int {
+        if (!rf || rf->device < 0) { avt_set_error("avt_rforest_com_pre_set: null or host-only forest"); return 1; }
+        AVT_HIP(hipSetDevice(rf->device));
+        return avt_post_com_set(&rf->post, rf->stream, rf->num_parts, first, n, com, valid);
+    });
+}
+
+int avt_rforest_com_pre_get(avt_rforest* rf, int first, int n, double* com, unsigned char* valid) {
+    return avt_guard("avt_rforest_com_pre_get", [&]() -> int {
+        if (!rf || rf->device < 0) { avt_set_error("avt_rforest_com_pre_get: null or host-only forest"); return 1; }
+        AVT_HIP(hipSetDevice(rf->device));
+        return avt_post_com_get(&rf->post, rf->stream, rf->num_parts, first, n, com, valid);
+    });
+}
+
 int avt_rforest_score_reset(avt_rforest* rf) {
     if (!rf) { avt_set_error("avt_rforest_score_reset: null forest"); return 1; }
     rf->score_conf.clear();

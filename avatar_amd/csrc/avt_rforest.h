@@ -33,6 +33,7 @@ struct avt_rforest {
     long long score_images = 0, score_pixels = 0;
     DevBuf<unsigned long long> d_score;
     DevBuf<int> d_score_bad;
+    AvtPostState post;                        // avt_rforest_post_process_resident / _from_bgsub: scratch and the per-slot com_pre memory
 };
 
 // distribution form: d_depth is the forest's one resident image, d_out num_parts planes

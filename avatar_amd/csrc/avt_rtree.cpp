@@ -534,6 +534,34 @@ int avt_rtree_labels_download_all(avt_rtree* rt, unsigned char* labels_out) {
     return avt_guard("avt_rtree_labels_download_all", [&]() -> int { return labels_download_all_impl(rt, labels_out); });
 }
 
+int avt_rtree_labels_upload(avt_rtree* rt, int n_images, int rows, int cols, const unsigned char* labels) {
+    return avt_guard("avt_rtree_labels_upload", [&]() -> int { return avt_post_labels_upload(rt, "avt_rtree_labels_upload", n_images, rows, cols, labels); });
+}
+
+int avt_rtree_post_process_resident(avt_rtree* rt, int interval, const int* boxes, double dist_to_pre_weight) {
+    return avt_guard("avt_rtree_post_process_resident", [&]() -> int { return avt_post_resident(rt, "avt_rtree_post_process_resident", interval, boxes, dist_to_pre_weight); });
+}
+
+int avt_rtree_post_process_from_bgsub(avt_rtree* rt, avt_bgsub* bg, int interval, double dist_to_pre_weight) {
+    return avt_guard("avt_rtree_post_process_from_bgsub", [&]() -> int { return avt_post_from_bgsub(rt, bg, "avt_rtree_post_process_from_bgsub", interval, dist_to_pre_weight); });
+}
+
+int avt_rtree_com_pre_set(avt_rtree* rt, int first, int n, const double* com, const unsigned char* valid) {
+    return avt_guard("avt_rtree_com_pre_set", [&]() -> int {
+        if (!rt || rt->device < 0) { avt_set_error("avt_rtree_com_pre_set: null or host-only tree"); return 1; }
+        AVT_HIP(hipSetDevice(rt->device));
+        return avt_post_com_set(&rt->post, rt->stream, rt->num_parts, first, n, com, valid);
+    });
+}
+
+int avt_rtree_com_pre_get(avt_rtree* rt, int first, int n, double* com, unsigned char* valid) {
+    return avt_guard("avt_rtree_com_pre_get", [&]() -> int {
+        if (!rt || rt->device < 0) { avt_set_error("avt_rtree_com_pre_get: null or host-only tree"); return 1; }
+        AVT_HIP(hipSetDevice(rt->device));
+        return avt_post_com_get(&rt->post, rt->stream, rt->num_parts, first, n, com, valid);
+    });
+}
+
 int avt_rtree_post_process(const avt_rtree* rt, unsigned char* image, int rows, int cols, double* com_pre, int com_pre_valid, int interval, int tlx,
                            int tly, int brx, int bry, double dist_to_pre_weight) {
     return avt_guard("avt_rtree_post_process", [&]() -> int { return avt_rtree_post_process_impl(rt, image, rows, cols, com_pre, com_pre_valid, interval, tlx, tly, brx, bry, dist_to_pre_weight); });

@@ -7,6 +7,7 @@
 
 #include "../../include/avt_rtree.h"
 #include "avt_host.h"
+#include "avt_post.h"
 
 // one tree node as the kernel reads it: two 16-byte loads
 struct RtNodeDev {
@@ -36,6 +37,7 @@ struct avt_rtree {
     int n_labels = 0;                         // images d_labels holds (rows x cols each): what avt_rtree_labels_download serves
     DevBuf<int> d_boxes;                      // n x 4 regions of interest of avt_rtree_predict_best_resident_boxes
     DevBuf<unsigned long long> d_tcount;      // trainTransfer's (leaf, part) counts since the last avt_rtree_transfer_finish
+    AvtPostState post;                        // avt_rtree_post_process_resident / _from_bgsub: scratch and the per-slot com_pre memory
 };
 
 int avt_rtree_launch_predict_dist(avt_rtree* rt, int rows, int cols, float* d_out);

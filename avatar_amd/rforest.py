@@ -19,6 +19,8 @@ RFOREST_SYMBOLS = [
     "avt_rforest_images_upload", "avt_rforest_predict_best_resident_boxes", "avt_rforest_predict_best_from_bgsub",
     "avt_rforest_labels_download", "avt_rforest_labels_download_all", "avt_rforest_sync",
     "avt_rforest_score_reset", "avt_rforest_score_images", "avt_rforest_score_rendered", "avt_rforest_score_get",
+    "avt_rforest_labels_upload", "avt_rforest_post_process_resident", "avt_rforest_post_process_from_bgsub",
+    "avt_rforest_com_pre_set", "avt_rforest_com_pre_get",
 ]
 MAX_TREES = 16       # AVT_RFOREST_MAX_TREES
 
@@ -110,6 +112,14 @@ class RForest:
         depth and the boxes on the device: no copy of the depth, no host wait."""
         capi.check(self._lib.avt_rforest_predict_best_from_bgsub(self._h, bg._h, C.c_int(interval), C.c_int(1 if fill_in_gaps else 0)))
         self._shape = (bg._n,) + tuple(bg._shape[:2])
+
+    # ---- postProcess for a batch on the device: the tree's methods over the forest's own entry points ----
+    _PREFIX = "avt_rforest"
+    upload_labels = RTree.upload_labels
+    post_process_resident = RTree.post_process_resident
+    post_process_from_bgsub = RTree.post_process_from_bgsub
+    com_pre_get = RTree.com_pre_get
+    com_pre_set = RTree.com_pre_set
 
     def sync(self):
         capi.check(self._lib.avt_rforest_sync(self._h))

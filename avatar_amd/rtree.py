@@ -15,7 +15,8 @@ RTREE_SYMBOLS = [
     "avt_rtree_create", "avt_rtree_load", "avt_rtree_export", "avt_rtree_destroy", "avt_rtree_info", "avt_rtree_get",
     "avt_rtree_predict_best", "avt_rtree_predict", "avt_rtree_images_upload", "avt_rtree_predict_best_resident", "avt_rtree_labels_download",
     "avt_rtree_sync", "avt_rtree_post_process", "avt_rtree_predict_best_resident_boxes", "avt_rtree_predict_best_from_bgsub",
-    "avt_rtree_labels_download_all",
+    "avt_rtree_labels_download_all", "avt_rtree_labels_upload", "avt_rtree_post_process_resident", "avt_rtree_post_process_from_bgsub",
+    "avt_rtree_com_pre_set", "avt_rtree_com_pre_get",
 ]
 
 
@@ -194,6 +195,49 @@ class RTree:
         serve these images; the tree's own resident images are gone until the next upload_images."""
         capi.check(self._lib.avt_rtree_predict_best_from_bgsub(self._h, bg._h, C.c_int(interval), C.c_int(1 if fill_in_gaps else 0)))
         self._shape = (bg._n,) + tuple(bg._shape[:2])
+
+    # ---- postProcess for a batch on the device (include/avt_rtree.h: components on the interval grid) ----
+    _PREFIX = "avt_rtree"
+
+    def upload_labels(self, labels):
+        """(n, rows, cols) uint8 label images (255 = none) become the images of the last labelling call."""
+        m = np.ascontiguousarray(labels, np.uint8)
+        capi.check(getattr(self._lib, self._PREFIX + "_labels_upload")(self._h, C.c_int(m.shape[0]), C.c_int(m.shape[1]), C.c_int(m.shape[2]), capi.ptr(m, C.c_ubyte)))
+        self._shape = m.shape
+
+    def post_process_resident(self, interval=1, boxes=None, dist_to_pre_weight=0.001):
+        """postProcess in place on the device on every image of the last labelling call, image i inside boxes[i] = (tl.x, tl.y,
+        br.x, br.y), inclusive (None: whole images; br.x == -1: the whole image; tl > br: nothing to do) with memory slot i.
+        The rule is connected components on the interval grid: RTree::postProcess bit for bit at interval 1, a documented
+        difference above it (include/avt_rtree.h)."""
+        b = None if boxes is None else np.ascontiguousarray(boxes, np.int32).reshape(-1, 4)
+        n = getattr(self, "_shape", (0,))[0]
+        if b is not None and n and len(b) != n:
+            raise ValueError(f"post_process_resident: {len(b)} boxes for {n} images")
+        capi.check(getattr(self._lib, self._PREFIX + "_post_process_resident")(self._h, C.c_int(interval), None if b is None else capi.ptr(b, C.c_int),
+                                                                             C.c_double(dist_to_pre_weight)))
+
+    def post_process_from_bgsub(self, bg, interval=1, dist_to_pre_weight=0.001):
+        """post_process_resident behind predict_from_bgsub(bg, ...): every image inside the box `bg`'s last run left on the device."""
+        capi.check(getattr(self._lib, self._PREFIX + "_post_process_from_bgsub")(self._h, bg._h, C.c_int(interval), C.c_double(dist_to_pre_weight)))
+
+    def com_pre_get(self, first=0, n=1):
+        """The memory of slots [first, first + n): (com_pre (n, 2, numParts) float64 as postProcess returns it per image,
+        valid (n,) bool; a slot that is not sized yet reads x = -1, y = 0)."""
+        com = np.empty((n, self.numParts, 2), np.float64)
+        valid = np.empty(n, np.uint8)
+        capi.check(getattr(self._lib, self._PREFIX + "_com_pre_get")(self._h, C.c_int(first), C.c_int(n), capi.dptr(com), capi.ptr(valid, C.c_ubyte)))
+        return np.ascontiguousarray(com.transpose(0, 2, 1)), valid.astype(bool)
+
+    def com_pre_set(self, first, com_pre, valid=None):
+        """Installs com_pre (n, 2, numParts) into the slots from `first` on; valid (n,) bool, None = all sized."""
+        cp = np.asarray(com_pre, np.float64)
+        if cp.ndim != 3 or cp.shape[1:] != (2, self.numParts):
+            raise ValueError("com_pre_set: com_pre must be (n, 2, numParts)")
+        com = np.ascontiguousarray(cp.transpose(0, 2, 1))
+        v = None if valid is None else np.ascontiguousarray(np.asarray(valid, bool), np.uint8)
+        capi.check(getattr(self._lib, self._PREFIX + "_com_pre_set")(self._h, C.c_int(first), C.c_int(len(com)), capi.dptr(com),
+                                                                   None if v is None else capi.ptr(v, C.c_ubyte)))
 
     def sync(self):
         capi.check(self._lib.avt_rtree_sync(self._h))

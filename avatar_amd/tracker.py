@@ -275,9 +275,13 @@ class MultiFrameTracker:
         return fitted
 
     # ---- depth in: the front end of demo.cpp:179-204 for all streams at once ----
-    def attach_front_end(self, bgsub, rtree, rtree_interval=2, dist_to_pre_weight=0.001):
-        """`bgsub`: a bgsub.BGSubtractor holding one background per stream; `rtree`: an rtree.RTree on the same device."""
+    def attach_front_end(self, bgsub, rtree, rtree_interval=2, dist_to_pre_weight=0.001, device_post_process=False):
+        """`bgsub`: a bgsub.BGSubtractor holding one background per stream; `rtree`: an rtree.RTree on the same device.
+        device_post_process: postProcess runs on the device for all streams at once (rtree.post_process_from_bgsub: connected
+        components on the interval grid; the reference's result at rtree_interval 1, a documented difference above it) and
+        comPre is the forest's resident memory, slot s for stream s.  Off, postProcess runs per stream on the host as ever."""
         self.bgsub, self.rtree = bgsub, rtree
+        self.devicePostProcess = bool(device_post_process)
         self.rtreeInterval, self.distToPreWeight = rtree_interval, dist_to_pre_weight
         self.comPre = [None] * self.S                 # demo.cpp:148, per stream
         self.boxes = [None] * self.S                  # ((tl.x, tl.y), (br.x, br.y)) of every stream's last background subtraction
@@ -313,6 +317,8 @@ class MultiFrameTracker:
         """The front end behind the upload, whatever its kind: per stream the post-processed part mask and the box to subsample."""
         self.bgsub.run_resident()
         self.rtree.predict_from_bgsub(self.bgsub, self.rtreeInterval)
+        if getattr(self, "devicePostProcess", False):
+            return self._label_resident_device()
         labels = self.rtree.download_all_labels()
         out = []
         for s in range(self.S):
@@ -328,6 +334,23 @@ class MultiFrameTracker:
                 bbox = (H - 1, W - 1, 0, 0)           # nothing to subsample
             out.append((labels[s], bbox))
         self.labels = labels                          # the step's post-processed part masks (S, H, W)
+        return out
+
+    def _label_resident_device(self):
+        """_label_resident with the post-processing on the device: nothing per stream on the host but the box."""
+        self.rtree.post_process_from_bgsub(self.bgsub, self.rtreeInterval, self.distToPreWeight)
+        labels = self.rtree.download_all_labels()
+        com, _ = self.rtree.com_pre_get(0, self.S)
+        out = []
+        for s in range(self.S):
+            res = self.bgsub.info(s)
+            tl, br = res.topLeft, res.botRight
+            self.boxes[s] = (tl, br)
+            self.comPre[s] = com[s]
+            H, W = labels[s].shape
+            inside = 0 <= tl[0] <= br[0] < W and 0 <= tl[1] <= br[1] < H
+            out.append((labels[s], (tl[1], tl[0], br[1], br[0]) if inside else (H - 1, W - 1, 0, 0)))
+        self.labels = labels
         return out
 
     def posed(self, stream):

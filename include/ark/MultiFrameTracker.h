@@ -164,18 +164,21 @@ class MultiFrameTracker {
 
     /** The front end of processDepth: a BGSubtractor holding one background per stream and a forest on the same device (both
      *  outlive the tracker's use of them); the interval of predictBest / postProcess (demo.cpp:198) and postProcess's weight. */
-    void attachFrontEnd(BGSubtractor& bgsub, RTree& rtree, int rtree_interval = 2, double dist_to_pre_weight = 0.001) {
+    /** devicePostProcess: postProcess runs on the device for all streams at once (RTree::postProcessFromBGSub: connected components
+     *  on the interval grid, the reference's result at rtree_interval 1 and a documented difference above it); comPre[s] is then the
+     *  forest's resident memory of slot s.  Off, postProcess runs per stream on the host as ever. */
+    void attachFrontEnd(BGSubtractor& bgsub, RTree& rtree, int rtree_interval = 2, double dist_to_pre_weight = 0.001, bool devicePostProcess = false) {
         frontBG = &bgsub; frontTree = &rtree; frontForest = nullptr;
-        rtreeInterval = rtree_interval; distToPreWeight = dist_to_pre_weight;
+        rtreeInterval = rtree_interval; distToPreWeight = dist_to_pre_weight; devicePost = devicePostProcess;
         comPre.assign((size_t)S, MatrixNX<2>());
         boxes.assign((size_t)S, {0, 0, 0, 0});
         partMasks.clear();
     }
 
     /** The same front end with a forest of several trees in the tree's place (ark/RForest.h). */
-    void attachFrontEnd(BGSubtractor& bgsub, RForest& rforest, int rtree_interval = 2, double dist_to_pre_weight = 0.001) {
+    void attachFrontEnd(BGSubtractor& bgsub, RForest& rforest, int rtree_interval = 2, double dist_to_pre_weight = 0.001, bool devicePostProcess = false) {
         frontBG = &bgsub; frontTree = nullptr; frontForest = &rforest;
-        rtreeInterval = rtree_interval; distToPreWeight = dist_to_pre_weight;
+        rtreeInterval = rtree_interval; distToPreWeight = dist_to_pre_weight; devicePost = devicePostProcess;
         comPre.assign((size_t)S, MatrixNX<2>());
         boxes.assign((size_t)S, {0, 0, 0, 0});
         partMasks.clear();
@@ -215,8 +218,13 @@ class MultiFrameTracker {
     /** The front end behind the batch run, whatever its source: labels on the device, postProcess per stream; fills partMasks and
      *  boxes and returns every stream's box to subsample. */
     std::vector<Rect> labelBatch() {
-        partMasks = frontTree ? frontTree->predictBestFromBGSub(*frontBG, rtreeInterval) : frontForest->predictBestFromBGSub(*frontBG, rtreeInterval);
+        partMasks = frontTree ? frontTree->predictBestFromBGSub(*frontBG, rtreeInterval, true, !devicePost)
+                              : frontForest->predictBestFromBGSub(*frontBG, rtreeInterval, true, !devicePost);
+        if (devicePost)       // in place on the device, all streams in one launch sequence; the labels come down once, after it
+            partMasks = frontTree ? frontTree->postProcessFromBGSub(*frontBG, rtreeInterval, distToPreWeight)
+                                  : frontForest->postProcessFromBGSub(*frontBG, rtreeInterval, distToPreWeight);
         auto postProcess = [&](Image8& m, MatrixNX<2>& com, Point tl, Point br) {
+            if (devicePost) return;
             if (frontTree) frontTree->postProcess(m, com, rtreeInterval, 1, tl, br, distToPreWeight);
             else frontForest->postProcess(m, com, rtreeInterval, 1, tl, br, distToPreWeight);
         };
@@ -234,6 +242,7 @@ class MultiFrameTracker {
                 postProcess(m, comPre[(size_t)s], Point(0, 0), Point(-1, -1));
                 box.top = m.rows - 1; box.left = m.cols - 1; box.bottom = 0; box.right = 0;       // nothing to subsample
             }
+            if (devicePost) comPre[(size_t)s] = frontTree ? frontTree->comPre(s) : frontForest->comPre(s);
         }
         return out;
     }
@@ -312,6 +321,7 @@ class MultiFrameTracker {
     std::vector<Image8> partMasks;
     int rtreeInterval = 2;
     double distToPreWeight = 0.001;
+    bool devicePost = false;
 
    private:
     std::vector<double> p, q, w;

@@ -111,9 +111,10 @@ public:
 
     /** The labels of every image of bgsub's last runBatch, each inside the box that run found, read from the masked depth on the
      *  device (avt_rforest_predict_best_from_bgsub) */
-    std::vector<Image8> predictBestFromBGSub(BGSubtractor& bgsub, int interval = 1, bool fill_in_gaps = true) {
+    std::vector<Image8> predictBestFromBGSub(BGSubtractor& bgsub, int interval = 1, bool fill_in_gaps = true, bool download = true) {
         if (bgsub.batchSize() <= 0) fatal("predictBestFromBGSub", "the background subtractor has no batch run behind it");
         if (avt_rforest_predict_best_from_bgsub(h_, bgsub.handle(), interval, fill_in_gaps ? 1 : 0) != 0) die("predictBestFromBGSub");
+        if (!download) return {};          // the labels stay on the device (for postProcessFromBGSub)
         return downloadAll(bgsub.batchSize(), bgsub.rows(), bgsub.cols(), "predictBestFromBGSub");
     }
 
@@ -131,6 +132,54 @@ public:
     void postProcess(Image8& image, MatrixNX<2>& com_pre, int interval = 1, int num_threads = 1, Point top_left = Point(0, 0),
                      Point bot_right = Point(-1, -1), double dist_to_pre_weight = 0.001) {
         first_->postProcess(image, com_pre, interval, num_threads, top_left, bot_right, dist_to_pre_weight);
+    }
+
+    // ---- postProcess for a batch on the device (avt_rforest.h: connected components per part on the interval grid; RTree::postProcess
+    // bit for bit at interval 1, a documented difference above it).  Image i of a batch uses memory slot i.
+    /** Label images of one size that another classifier made become the images of the last labelling call */
+    void uploadLabels(const std::vector<Image8>& labels) {
+        if (labels.empty()) fatal("uploadLabels", "need at least one image");
+        const int rows = labels[0].rows, cols = labels[0].cols;
+        std::vector<uint8_t> all;
+        for (const Image8& im : labels) {
+            if (im.rows != rows || im.cols != cols) fatal("uploadLabels", "the images must share one size");
+            all.insert(all.end(), im.a.begin(), im.a.end());
+        }
+        if (avt_rforest_labels_upload(h_, (int)labels.size(), rows, cols, all.data()) != 0) die("uploadLabels");
+        lastN_ = (int)labels.size(); lastRows_ = rows; lastCols_ = cols;
+    }
+
+    /** postProcess on the device, in place on the images of the last labelling call (predictBestBatch, predictBestFromBGSub,
+     *  uploadLabels), image i inside boxes[i] = {tl.x, tl.y, br.x, br.y} (none: whole images; tl > br: nothing to do); returns them */
+    std::vector<Image8> postProcessResident(int interval = 1, const std::vector<std::array<int, 4>>& boxes = {}, double dist_to_pre_weight = 0.001) {
+        if (lastN_ <= 0) fatal("postProcessResident", "no labelled images behind the handle");
+        if (!boxes.empty() && (int)boxes.size() != lastN_) fatal("postProcessResident", "need one box per image, or none");
+        if (avt_rforest_post_process_resident(h_, interval, boxes.empty() ? nullptr : boxes[0].data(), dist_to_pre_weight) != 0) die("postProcessResident");
+        return downloadAll(lastN_, lastRows_, lastCols_, "postProcessResident");
+    }
+
+    /** postProcessResident behind predictBestFromBGSub(bgsub, ...): every image inside the box bgsub's last runBatch left on the
+     *  device */
+    std::vector<Image8> postProcessFromBGSub(BGSubtractor& bgsub, int interval = 1, double dist_to_pre_weight = 0.001) {
+        if (bgsub.batchSize() <= 0) fatal("postProcessFromBGSub", "the background subtractor has no batch run behind it");
+        if (avt_rforest_post_process_from_bgsub(h_, bgsub.handle(), interval, dist_to_pre_weight) != 0) die("postProcessFromBGSub");
+        return downloadAll(bgsub.batchSize(), bgsub.rows(), bgsub.cols(), "postProcessFromBGSub");
+    }
+
+    /** com_pre of memory slot `slot` as postProcess keeps it (2 x numParts); a slot that is not sized yet comes back empty */
+    MatrixNX<2> comPre(int slot) {
+        MatrixNX<2> com;
+        com.resize(2, numParts);
+        unsigned char valid = 0;
+        if (avt_rforest_com_pre_get(h_, slot, 1, com.data(), &valid) != 0) die("comPre");
+        if (!valid) com.a.clear();
+        return com;
+    }
+    /** Installs com_pre into memory slot `slot`; one that is not 2 x numParts makes the slot "not sized yet" */
+    void setComPre(int slot, const MatrixNX<2>& com_pre) {
+        const unsigned char valid = (int)com_pre.cols() == numParts ? 1 : 0;
+        std::vector<double> zero(2 * (size_t)numParts, 0.0);
+        if (avt_rforest_com_pre_set(h_, slot, 1, valid ? com_pre.data() : zero.data(), &valid) != 0) die("setComPre");
     }
 
     // ---- the score: a confusion matrix against ground-truth part masks (avt_rforest.h, THE SCORE)
@@ -235,6 +284,7 @@ private:
     std::vector<Image8> downloadAll(int n, int rows, int cols, const char* what) {
         std::vector<uint8_t> all((size_t)n * rows * cols);
         if (avt_rforest_labels_download_all(h_, all.data()) != 0) die(what);
+        lastN_ = n; lastRows_ = rows; lastCols_ = cols;
         std::vector<Image8> result((size_t)n, Image8(rows, cols));
         for (int i = 0; i < n; ++i) result[(size_t)i].a.assign(all.begin() + (size_t)i * rows * cols, all.begin() + (size_t)(i + 1) * rows * cols);
         return result;
@@ -250,6 +300,7 @@ private:
     avt_rforest* h_ = nullptr;
     std::unique_ptr<RTree> first_;
     int device_ = 0;
+    int lastN_ = 0, lastRows_ = 0, lastCols_ = 0;   // the images of the last labelling call
 };
 
 }  // namespace ark

@@ -106,8 +106,9 @@ public:
     }
 
     /** The labels of every image of bgsub's last runBatch, each inside the box that run found, read from the masked depth on the
-     *  device (demo.cpp:179-204 without the host in between; avt_rtree_predict_best_from_bgsub).  Defined in ark/BGSubtractor.h. */
-    std::vector<Image8> predictBestFromBGSub(BGSubtractor& bgsub, int interval = 1, bool fill_in_gaps = true);
+     *  device (demo.cpp:179-204 without the host in between; avt_rtree_predict_best_from_bgsub).  download = false leaves them
+     *  there (for postProcessFromBGSub) and returns nothing.  Defined in ark/BGSubtractor.h. */
+    std::vector<Image8> predictBestFromBGSub(BGSubtractor& bgsub, int interval = 1, bool fill_in_gaps = true, bool download = true);
 
     /** Predict distribution for all of image: numParts planes of CV_32F (RTree.h:59-61) */
     std::vector<ImageF> predict(const ImageF& depth) {
@@ -219,6 +220,50 @@ public:
             die("postProcess");
     }
 
+    // ---- postProcess for a batch on the device (avt_rtree.h: connected components per part on the interval grid; RTree::postProcess
+    // bit for bit at interval 1, a documented difference above it).  Image i of a batch uses memory slot i.
+    /** Label images of one size that another classifier made become the images of the last labelling call */
+    void uploadLabels(const std::vector<Image8>& labels) {
+        if (labels.empty()) fatal("uploadLabels", "need at least one image");
+        const int rows = labels[0].rows, cols = labels[0].cols;
+        std::vector<uint8_t> all;
+        for (const Image8& im : labels) {
+            if (im.rows != rows || im.cols != cols) fatal("uploadLabels", "the images must share one size");
+            all.insert(all.end(), im.a.begin(), im.a.end());
+        }
+        if (!ensure() || avt_rtree_labels_upload(h_, (int)labels.size(), rows, cols, all.data()) != 0) die("uploadLabels");
+        lastN_ = (int)labels.size(); lastRows_ = rows; lastCols_ = cols;
+    }
+
+    /** postProcess on the device, in place on the images of the last labelling call (predictBestBatch, predictBestFromBGSub,
+     *  uploadLabels), image i inside boxes[i] = {tl.x, tl.y, br.x, br.y} (none: whole images; tl > br: nothing to do); returns them */
+    std::vector<Image8> postProcessResident(int interval = 1, const std::vector<std::array<int, 4>>& boxes = {}, double dist_to_pre_weight = 0.001) {
+        if (lastN_ <= 0) fatal("postProcessResident", "no labelled images behind the handle");
+        if (!boxes.empty() && (int)boxes.size() != lastN_) fatal("postProcessResident", "need one box per image, or none");
+        if (avt_rtree_post_process_resident(h_, interval, boxes.empty() ? nullptr : boxes[0].data(), dist_to_pre_weight) != 0) die("postProcessResident");
+        return downloadAll(lastN_, lastRows_, lastCols_, "postProcessResident");
+    }
+
+    /** postProcessResident behind predictBestFromBGSub(bgsub, ...): every image inside the box bgsub's last runBatch left on the
+     *  device.  Defined in ark/BGSubtractor.h. */
+    std::vector<Image8> postProcessFromBGSub(BGSubtractor& bgsub, int interval = 1, double dist_to_pre_weight = 0.001);
+
+    /** com_pre of memory slot `slot` as postProcess keeps it (2 x numParts); a slot that is not sized yet comes back empty */
+    MatrixNX<2> comPre(int slot) {
+        MatrixNX<2> com;
+        com.resize(2, numParts);
+        unsigned char valid = 0;
+        if (!ensure() || avt_rtree_com_pre_get(h_, slot, 1, com.data(), &valid) != 0) die("comPre");
+        if (!valid) com.a.clear();
+        return com;
+    }
+    /** Installs com_pre into memory slot `slot`; one that is not 2 x numParts makes the slot "not sized yet" */
+    void setComPre(int slot, const MatrixNX<2>& com_pre) {
+        const unsigned char valid = (int)com_pre.cols() == numParts ? 1 : 0;
+        std::vector<double> zero(2 * (size_t)numParts, 0.0);
+        if (!ensure() || avt_rtree_com_pre_set(h_, slot, 1, valid ? com_pre.data() : zero.data(), &valid) != 0) die("setComPre");
+    }
+
     /** The C handle (ark::RForest copies the tree through it); a tree filled in through the public members is uploaded first.
      *  Null when the tree is empty. */
     avt_rtree* handle() { return ensure() ? h_ : nullptr; }
@@ -251,6 +296,7 @@ private:
     std::vector<Image8> downloadAll(int n, int rows, int cols, const char* what) {
         std::vector<uint8_t> all((size_t)n * rows * cols);
         if (avt_rtree_labels_download_all(h_, all.data()) != 0) die(what);
+        lastN_ = n; lastRows_ = rows; lastCols_ = cols;
         std::vector<Image8> result((size_t)n, Image8(rows, cols));
         for (int i = 0; i < n; ++i) result[(size_t)i].a.assign(all.begin() + (size_t)i * rows * cols, all.begin() + (size_t)(i + 1) * rows * cols);
         return result;
@@ -297,6 +343,7 @@ private:
     }
     avt_rtree* h_ = nullptr;
     int device_ = 0;
+    int lastN_ = 0, lastRows_ = 0, lastCols_ = 0;   // the images of the last labelling call
 };
 
 }  // namespace ark

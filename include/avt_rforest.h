@@ -90,6 +90,18 @@ int avt_rforest_labels_download(avt_rforest* rf, int image, unsigned char* label
 int avt_rforest_labels_download_all(avt_rforest* rf, unsigned char* labels_out);
 int avt_rforest_sync(avt_rforest* rf);
 
+/* RTree::postProcess for a batch on the device, as the tree's (avt_rtree.h, RTree.cpp:3422-3449, with the DELIBERATE DIFFERENCE
+ * described there: connected components on the interval grid, the reference's rule bit for bit at interval 1 only), with the
+ * first member's num_parts and part-map type, which is what postProcess depends on. */
+int avt_rforest_labels_upload(avt_rforest* rf, int n_images, int rows, int cols, const unsigned char* labels);
+/* RTree.cpp:3422-3449 in place on the images of the last labelling call; see avt_rtree_post_process_resident and its deliberate difference. */
+int avt_rforest_post_process_resident(avt_rforest* rf, int interval, const int* boxes, double dist_to_pre_weight);
+/* RTree.cpp:3422-3449 inside the device boxes of bg's last run; see avt_rtree_post_process_from_bgsub and its deliberate difference. */
+int avt_rforest_post_process_from_bgsub(avt_rforest* rf, struct avt_bgsub* bg, int interval, double dist_to_pre_weight);
+/* com_pre of RTree.cpp:3422-3449 per image slot; see avt_rtree_com_pre_set / _get and the deliberate difference of the stage they serve. */
+int avt_rforest_com_pre_set(avt_rforest* rf, int first, int n, const double* com, const unsigned char* valid);
+int avt_rforest_com_pre_get(avt_rforest* rf, int first, int n, double* com, unsigned char* valid);
+
 /* THE SCORE above.  The totals start at zero, and score_reset puts them back there. */
 int avt_rforest_score_reset(avt_rforest* rf);
 /* n_images host images of rows x cols: float32 depth and uint8 part masks (255 = none).  They are staged in buffers of the call,

@@ -87,6 +87,41 @@ int avt_rtree_labels_download_all(avt_rtree* rt, unsigned char* labels_out);
 int avt_rtree_post_process(const avt_rtree* rt, unsigned char* image, int rows, int cols, double* com_pre, int com_pre_valid, int interval,
                            int tl_x, int tl_y, int br_x, int br_y, double dist_to_pre_weight);
 
+/* ---- RTree::postProcess for a batch of label images on the device (DESIGN.md par. 8) -----------------------------------
+ * The rule is connected components per part on the interval grid: the grid is the pixels (tl.y + a interval, tl.x + b interval)
+ * inside the box, two grid pixels are neighbours when they are `interval` apart in one axis, a component is a maximal
+ * 4-connected set of equal labels < num_parts.  'Contiguous' part maps keep, per part, the component with the largest score
+ * (size - weight x squared distance of its centre of mass to the slot's previous one, in double, if that is > 0; equal scores:
+ * the component whose first raster pixel comes first); 'disjoint' ones drop components smaller than 0.05 % of the grid.  Then
+ * the grid is up-scaled as the host code does it.
+ * DELIBERATE DIFFERENCE: at interval 1 this is RTree::postProcess (RTree.cpp:3422-3449) and avt_rtree_post_process bit for bit,
+ * labels and com_pre.  Above it, the reference's downward probe reads row r + 1 but records row r + interval (RTree.cpp:176),
+ * which makes its result depend on the scan order; the device stage is the reference with that probe reading row r + interval.
+ * A label that is neither 255 nor < num_parts fails the call (non-zero, with a message); that image and its memory are left as
+ * they were, the other images of the batch are processed.  The host version's silent -128 of values 128..254 is not reproduced.
+ * A box that is empty or (from the device) does not lie inside the image leaves the labels alone and sets every com_pre.x of
+ * its slot to -1 ('contiguous'), what the host code makes of an all-255 image.
+ * Image i of a batch uses memory slot i.  All images run in one launch sequence on the handle's stream; the call then waits for
+ * the stream once to read the images' status words. */
+
+/* n_images x rows x cols label bytes from the host become the images of "the last labelling call" (labels that another
+ * classifier made); the handle has no resident depth of its own afterwards. */
+int avt_rtree_labels_upload(avt_rtree* rt, int n_images, int rows, int cols, const unsigned char* labels);
+/* RTree::postProcess (RTree.cpp:3422-3449; see DELIBERATE DIFFERENCE above) in place on the images of the last labelling call.
+ * boxes: n x 4 host ints tl.x tl.y br.x br.y, inclusive, NULL = whole images; br.x == -1 is the whole image, an empty box
+ * (tl > br) is no error; a box outside the image or a bad interval fails before anything is queued. */
+int avt_rtree_post_process_resident(avt_rtree* rt, int interval, const int* boxes, double dist_to_pre_weight);
+/* RTree::postProcess (RTree.cpp:3422-3449; see DELIBERATE DIFFERENCE above) on the labels of avt_rtree_predict_best_from_bgsub,
+ * every image inside the box that bg's last run left on the device.  Ordered with bg exactly as that labelling is: the tree's
+ * stream waits for the run, bg's next images_upload, run_resident and destroy wait for this stage. */
+int avt_rtree_post_process_from_bgsub(avt_rtree* rt, struct avt_bgsub* bg, int interval, double dist_to_pre_weight);
+/* com_pre of RTree::postProcess (RTree.cpp:3422-3449; the device stage's memory across frames, see DELIBERATE DIFFERENCE above)
+ * for the slots [first, first + n): com is n x num_parts x 2 doubles (x, y per part, the layout of avt_rtree_post_process),
+ * valid n bytes (0 = not sized yet; NULL on set = all sized).  A slot that was never set is not sized and reads as x = -1,
+ * y = 0.  The memory is resident on the device and survives labelling calls and images_upload. */
+int avt_rtree_com_pre_set(avt_rtree* rt, int first, int n, const double* com, const unsigned char* valid);
+int avt_rtree_com_pre_get(avt_rtree* rt, int first, int n, double* com, unsigned char* valid);
+
 #ifdef __cplusplus
 }
 #endif
