@@ -380,6 +380,27 @@ class Context:
         lab = np.ascontiguousarray(np.concatenate([np.asarray(l, np.int32) for l in labels]))
         check(self._lib.avt_frames_upload(self.h, C.c_int(F), dptr(data), iptr(lab), iptr(offs)))
         self._F = F
+        self._N = np.diff(offs)                   # (frame_download)
+
+    def frames_subsample(self, bgsub, forest, intervals, boxes=None, centroid_of=None):
+        """demo.cpp:216-250 on the device (avatar_amd.subsample, include/avt_subsample.h): image i behind `forest` and `bgsub`
+        into frame slot i.  Returns (counts (n, 1 + num_parts), centroid (n, 3), boxes (n, 4)); the frames are pending and
+        nothing is resident until frames_commit."""
+        from . import subsample
+        out = subsample.frames_subsample(self, bgsub, forest, intervals, boxes, centroid_of)
+        self._sub_counts = out[0][:, 0].copy()
+        return out
+
+    def frames_commit(self, keep=None):
+        """The frames of the last frames_subsample become resident, frame i with 0 points where keep[i] is False (None: all kept)."""
+        from . import subsample
+        cnt = getattr(self, "_sub_counts", None)
+        if keep is not None and cnt is not None and len(keep) != len(cnt):
+            raise AvtError(f"frames_commit: {len(keep)} keep flags for {len(cnt)} pending frames")
+        subsample.frames_commit(self, keep)
+        self._F = len(cnt)
+        self._N = cnt.copy() if keep is None else np.where(np.asarray(keep, bool), cnt, 0).astype(np.int32)
+        self._sub_counts = None
 
     def render_frames(self, w, p, R, intrin=None, res_scale=1, painter=False):
         """Synthesise depth frames of posed avatars on the GPU, resident in this context.

@@ -611,7 +611,18 @@ int run_impl(avt_bgsub* bg, int background_index, const float* src, const float*
 int avt_bgsub_last_run(avt_bgsub* bg, avt_bgsub_view* out) {
     if (!bg || !out || bg->n_images <= 0 || !bg->ran) { avt_set_error("avt_bgsub: no run behind the handle (avt_bgsub_run_resident after the last upload)"); return 1; }
     static_assert(sizeof(BgsInfo) % sizeof(int) == 0 && offsetof(BgsInfo, box) == 0, "the boxes are read as ints at a stride of one BgsInfo");
-    *out = avt_bgsub_view{bg->device, bg->n_images, bg->rows, bg->cols, bg->d_depth, (const int*)(BgsInfo*)bg->d_info, (int)(sizeof(BgsInfo) / sizeof(int))};
+    // d_img is read-only to every kernel of a run (k_bgs_local, k_bgs_border, k_bgs_depth take it const; the masked depth goes to
+    // d_depth): the view's XYZ maps are the originals, which is what demo.cpp:245 reads
+    *out = avt_bgsub_view{bg->device, bg->n_images, bg->rows, bg->cols, bg->d_depth, (const int*)(BgsInfo*)bg->d_info, (int)(sizeof(BgsInfo) / sizeof(int)),
+                          bg->d_img};
+    return 0;
+}
+
+int avt_bgsub_resident(avt_bgsub* bg, avt_bgsub_view* out, bool* ran) {
+    if (!bg || !out || bg->n_images <= 0) { avt_set_error("avt_bgsub: no images resident behind the handle (an upload first)"); return 1; }
+    *out = avt_bgsub_view{bg->device, bg->n_images, bg->rows, bg->cols, bg->d_depth, (const int*)(BgsInfo*)bg->d_info, (int)(sizeof(BgsInfo) / sizeof(int)),
+                          bg->d_img};
+    if (ran) *ran = bg->ran;
     return 0;
 }
 

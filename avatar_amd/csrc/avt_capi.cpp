@@ -377,6 +377,7 @@ int set_resident_frames(avt_ctx* c, int nframes, CountOf count_of) {
         if (n > c->fb.max_points) { avt_set_error("frames: a frame has more points than max_points_per_frame"); return 1; }
         mx = std::max(mx, n);
     }
+    c->sub.pending = false;                         // whatever installs frames takes the slots of a pending subsampled batch
     c->have_moments = c->have_records = false;      // new frames: the moments / records of the old correspondences describe nothing resident
     c->results_fresh = false;
     c->nframes = nframes;
@@ -384,6 +385,17 @@ int set_resident_frames(avt_ctx* c, int nframes, CountOf count_of) {
     c->frame_off.assign(nframes + 1, 0);
     for (int f = 0; f < nframes; ++f) { c->frame_N[f] = count_of(f); c->frame_off[f + 1] = c->frame_off[f] + c->frame_N[f]; }
     c->launch_maxN = std::max(mx, std::min(c->fb.max_points, ((mx + 2047) / 2048) * 2048));
+    return 0;
+}
+
+// The closing step of an install: the point counts of the resident frames go into the device control blocks (working copy and
+// start copy), the host waits, and the frames count as resident.
+int publish_frames(avt_ctx* c, int nframes, bool same_shape) {
+    for (AvtFrameCtl* dst : {c->fb.ctl, c->fb.ctl_start})
+        AVT_HIP(hipMemcpy2DAsync(&dst->N, sizeof(AvtFrameCtl), c->frame_N.data(), sizeof(int), sizeof(int), (size_t)nframes, hipMemcpyHostToDevice, c->stream));
+    AVT_HIP(hipStreamSynchronize(c->stream));
+    c->frames_valid = true;
+    if (!same_shape) c->state_valid = false;     // a different number of frames needs a new start state
     return 0;
 }
 
@@ -404,12 +416,7 @@ int install_frames(avt_ctx* c, int nframes, CountOf count_of, const double* data
         AVT_HIP(hipMemcpyAsync(c->fb.data_raw + (size_t)f * c->fb.max_points * 3, data + o * 3, N * 3 * sizeof(double), kind, c->stream));
         AVT_HIP(hipMemcpyAsync(c->fb.labels_raw + (size_t)f * c->fb.max_points, labels + o, N * sizeof(int), kind, c->stream));
     }
-    for (AvtFrameCtl* dst : {c->fb.ctl, c->fb.ctl_start})
-        AVT_HIP(hipMemcpy2DAsync(&dst->N, sizeof(AvtFrameCtl), c->frame_N.data(), sizeof(int), sizeof(int), (size_t)nframes, hipMemcpyHostToDevice, c->stream));
-    AVT_HIP(hipStreamSynchronize(c->stream));
-    c->frames_valid = true;
-    if (!same_shape) c->state_valid = false;     // a different number of frames needs a new start state
-    return 0;
+    return publish_frames(c, nframes, same_shape);
 }
 
 int upload_frames(avt_ctx* c, int nframes, const double* data, const int* labels, const int* offs) {
@@ -572,6 +579,12 @@ int stage_pose(avt_ctx* c, const char* who, int nframes, const double* w, const 
 }
 
 }  // namespace
+
+int avt_internal_commit_frames(avt_ctx* c, int nframes, const int* counts, bool same_shape) {
+    if (set_resident_frames(c, nframes, [&](int f) { return counts[f]; })) return 1;
+    c->frames_valid = false;
+    return publish_frames(c, nframes, same_shape);
+}
 
 // batch split (avt_shard.cpp): frames received into a device buffer become this context's resident frames
 int avt_internal_install_frames(avt_ctx* c, int nframes, const int* counts, const double* data, const int* labels, int device_src) {
@@ -754,6 +767,7 @@ void avt_ctx_destroy(avt_ctx* c) {
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
     { std::lock_guard<std::mutex> graph_lock(g_graph_mutex); for (auto& g : c->graphs) (void)hipGraphExecDestroy(g.exec); }
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
+    if (c->sub.ev_labels) (void)hipEventDestroy(c->sub.ev_labels);
     for (int i = 0; i < AVT_MAX_GROUPS - 1; ++i) {
         if (c->ev_join[i]) (void)hipEventDestroy(c->ev_join[i]);
         if (c->side[i]) (void)hipStreamDestroy(c->side[i]);

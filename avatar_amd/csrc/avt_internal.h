@@ -361,6 +361,19 @@ struct avt_model {
     std::vector<unsigned short> mom_tab16;
 };
 
+// avt_frames_subsample_* (avt_subsample.hip): scratch that only grows, and what a pending batch needs until its commit
+struct AvtSubState {
+    DevBuf<int> block;                  // n x max_chunks: kept pixels of every chunk, then their exclusive scan per image
+    DevBuf<int> in;                     // what a call sends up in one copy: intervals n | centroid flags n | host boxes n x 4
+    DevBuf<double> out;                 // what it brings back in one copy: centroids n x 3 | (as ints) counts n x (1 + parts) | status n | boxes n x 4
+    std::vector<int> h_in;              // ... their host sides, alive until the call's one wait
+    std::vector<double> h_out;
+    std::vector<int> counts;            // count[i][0] of the pending batch
+    hipEvent_t ev_labels = nullptr;     // recorded on the forest handle's stream: the context's stream waits for the labels
+    bool pending = false;               // a subsample call succeeded and no frames were installed since
+    int prev_nframes = -1;              // frames resident when the (first) pending batch was written, -1: none (install_frames' same_shape)
+};
+
 struct avt_ctx {
     // every member starts null / zero / false unless it says otherwise: avt_ctx_destroy copes with a partially built context
     int device = 0;
@@ -420,6 +433,7 @@ struct avt_ctx {
     int occ_w = 0, occ_h = 0;
     float occ_fx = 0, occ_fy = 0, occ_cx = 0, occ_cy = 0;
     DevBuf<int> occ_faces, occ_order, occ_rank; DevBuf<float> occ_fkey, occ_proj; DevBuf<unsigned char> occ_front;
+    AvtSubState sub;                    // avt_frames_subsample_*
 };
 
 void avt_set_error(const std::string& s);
@@ -450,6 +464,9 @@ void launch_solve(avt_ctx* c, int nframes, int mode, int seq = 0 /* which solve 
 void launch_pack_results(avt_ctx* c, int nframes);               // the result records of the resident frames, when no closing k_lbs launch wrote them
 // a device fault that has been reported is cleared and the result records, which still carry its word, are stale (avt_capi.cpp)
 int avt_internal_clear_faults(avt_ctx* c);
+// frames whose points already lie in the slots become resident with counts[f] points (avt_frames_subsample_commit): the
+// bookkeeping and control-block writes of avt_frames_upload without its copies (avt_capi.cpp)
+int avt_internal_commit_frames(avt_ctx* c, int nframes, const int* counts, bool same_shape);
 // per-frame ICP budgets (avt_optimize_resident_budgets) and per-frame state installs (avt_state_upload_frames)
 #define AVT_BUDGET_CHUNK 248
 struct AvtBudgetChunk { int f0, n; int b[AVT_BUDGET_CHUNK]; };        // a kernel argument (1 KB)

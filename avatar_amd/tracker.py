@@ -51,15 +51,20 @@ def subsample_depth(depth, intrin, part_mask, bbox, interval, num_parts):
     return _subsample(points_at, part_mask, bbox, interval, num_parts)
 
 
-def frame_decision(tr, labels, num_parts):
+def frame_decision(tr, labels, num_parts=None, counts=None):
     """The per-frame policy of one stream (demo.cpp:225-265, live-demo.cpp:376-418) on the subsampled labels: returns
     (fit, ICP iterations, reinitialise); fit False means tracking is lost (nothing is fitted, the next fitted frame reinitialises).
-    `tr` carries the stream's policy and state under FrameTracker's attribute names; reinit / firstTime are updated."""
+    `tr` carries the stream's policy and state under FrameTracker's attribute names; reinit / firstTime are updated.
+    counts: instead of the labels (then None), the frame's row of the device subsampling's table (api.Context.frames_subsample):
+    [points, points of part 0, points of part 1, ...] - the policy reads nothing else of a frame."""
+    if counts is not None:
+        n, part_counts = int(counts[0]), (lambda: np.asarray(counts[1:]))
+    else:
+        n, part_counts = len(labels), (lambda: np.bincount(labels, minlength=num_parts))
     part_missing = False                          # live-demo.cpp:376-380: the first fit wants every body part seen
     if tr.firstTime and tr.initialPerPartCnz > 0:
-        part_cnz = np.bincount(labels, minlength=num_parts)
-        part_missing = part_cnz.min() < max(1, tr.initialPerPartCnz // (tr.interval * tr.interval))
-    if len(labels) == 0 or part_missing or len(labels) < tr.reinitCnz // (tr.interval * tr.interval):   # an empty frame is never fitted
+        part_missing = part_counts().min() < max(1, tr.initialPerPartCnz // (tr.interval * tr.interval))
+    if n == 0 or part_missing or n < tr.reinitCnz // (tr.interval * tr.interval):   # an empty frame is never fitted
         tr.reinit = True
         return False, 0, False
     if not tr.reinit:
@@ -259,8 +264,12 @@ class MultiFrameTracker:
         self.last_budgets, self.last_reinit = budgets.copy(), list(reinit)
         if not any(fitted):
             return fitted
+        self.ctx.frames_upload(datas, labels)
+        return self._fit_resident(fitted, budgets, reinit)
+
+    def _fit_resident(self, fitted, budgets, reinit):
+        """_fit behind the frame install: start states, the batched fit, one download of all states."""
         ctx = self.ctx
-        ctx.frames_upload(datas, labels)
         if not self.state_resident:
             ctx.state_upload(self.p, self.q, self.w)
             self.state_resident = True
@@ -275,13 +284,20 @@ class MultiFrameTracker:
         return fitted
 
     # ---- depth in: the front end of demo.cpp:179-204 for all streams at once ----
-    def attach_front_end(self, bgsub, rtree, rtree_interval=2, dist_to_pre_weight=0.001, device_post_process=False):
+    def attach_front_end(self, bgsub, rtree, rtree_interval=2, dist_to_pre_weight=0.001, device_post_process=False, device_subsample=False):
         """`bgsub`: a bgsub.BGSubtractor holding one background per stream; `rtree`: an rtree.RTree on the same device.
         device_post_process: postProcess runs on the device for all streams at once (rtree.post_process_from_bgsub: connected
         components on the interval grid; the reference's result at rtree_interval 1, a documented difference above it) and
-        comPre is the forest's resident memory, slot s for stream s.  Off, postProcess runs per stream on the host as ever."""
+        comPre is the forest's resident memory, slot s for stream s.  Off, postProcess runs per stream on the host as ever.
+        device_subsample (needs device_post_process): the subsampling and the frame install run on the device too
+        (api.Context.frames_subsample / frames_commit): no label image comes down and no cloud goes up; the same frames, budgets
+        and states as without it.  `labels` is then None after a step and download_labels() fetches the masks on request."""
+        if device_subsample and not device_post_process:
+            raise ValueError("MultiFrameTracker.attach_front_end: device_subsample needs device_post_process=True")
         self.bgsub, self.rtree = bgsub, rtree
         self.devicePostProcess = bool(device_post_process)
+        self.deviceSubsample = bool(device_subsample)
+        self._stepped = False                         # a depth-in step has run: the front end holds its batch (fit_score)
         self.rtreeInterval, self.distToPreWeight = rtree_interval, dist_to_pre_weight
         self.comPre = [None] * self.S                 # demo.cpp:148, per stream
         self.boxes = [None] * self.S                  # ((tl.x, tl.y), (br.x, br.y)) of every stream's last background subtraction
@@ -295,6 +311,8 @@ class MultiFrameTracker:
         mask: it goes through postProcess on the whole image (every comPre x becomes -1) and is lost in process()."""
         self._front_end("process_depth", len(images))
         self.bgsub.upload(images)
+        if self.deviceSubsample:
+            return self._fit_device()
         return self.process([(images[s], mask, bbox) for s, (mask, bbox) in enumerate(self._label_resident())])
 
     def process_depth_images(self, depths, intrins):
@@ -304,6 +322,8 @@ class MultiFrameTracker:
         self._front_end("process_depth_images", len(depths))
         k = intrin_array(intrins, self.S)
         self.bgsub.upload_depth(depths, k)
+        if self.deviceSubsample:
+            return self._fit_device()
         return self._fit([subsample_depth(depths[s], k[s], mask, bbox, self.streams[s].interval, self.numParts)
                           for s, (mask, bbox) in enumerate(self._label_resident())])
 
@@ -334,6 +354,7 @@ class MultiFrameTracker:
                 bbox = (H - 1, W - 1, 0, 0)           # nothing to subsample
             out.append((labels[s], bbox))
         self.labels = labels                          # the step's post-processed part masks (S, H, W)
+        self._stepped = True
         return out
 
     def _label_resident_device(self):
@@ -351,7 +372,45 @@ class MultiFrameTracker:
             inside = 0 <= tl[0] <= br[0] < W and 0 <= tl[1] <= br[1] < H
             out.append((labels[s], (tl[1], tl[0], br[1], br[0]) if inside else (H - 1, W - 1, 0, 0)))
         self.labels = labels
+        self._stepped = True
         return out
+
+    def _fit_device(self):
+        """A depth-in step behind the upload with everything up to the fit on the device: labelling, post-processing,
+        subsampling into the context's frame slots (the centroids of the streams that may reinitialise come back with the
+        counts), the policy on the counts, the commit with the lost streams as empty frames, then _fit's tail."""
+        self.bgsub.run_resident()
+        self.rtree.predict_from_bgsub(self.bgsub, self.rtreeInterval)
+        self.rtree.post_process_from_bgsub(self.bgsub, self.rtreeInterval, self.distToPreWeight)
+        self.bgsub.info(0)                            # the one read of the subtractor's fault word (bgsub.info raises on it)
+        ctx = self.ctx
+        counts, centroid, boxes = ctx.frames_subsample(self.bgsub, self.rtree, [st.interval for st in self.streams], None,
+                                                       [st.reinit for st in self.streams])
+        com, _ = self.rtree.com_pre_get(0, self.S)
+        self.labels, self._stepped = None, True
+        budgets, reinit, fitted = np.zeros(self.S, np.int32), [], []
+        for s in range(self.S):
+            self.boxes[s] = ((int(boxes[s, 0]), int(boxes[s, 1])), (int(boxes[s, 2]), int(boxes[s, 3])))
+            self.comPre[s] = com[s]
+            fit, icp_iters, re = frame_decision(self.streams[s], None, self.numParts, counts=counts[s])
+            fitted.append(fit)
+            budgets[s] = icp_iters if fit else 0
+            if re:
+                reinit.append(s)
+                p, r, w = reinit_state(centroid[s][None], self.J, self.K)     # (the mean of one row is the row)
+                self.p[s], self.q[s], self.w[s] = p, api.rot_to_quat(r), w
+        self.last_budgets, self.last_reinit = budgets.copy(), list(reinit)
+        if not any(fitted):
+            return fitted
+        ctx.frames_commit(fitted)
+        return self._fit_resident(fitted, budgets, reinit)
+
+    def download_labels(self):
+        """The post-processed part masks (S, H, W) of the last depth-in step: `labels` where the step brought them down, one
+        download where it did not (device_subsample)."""
+        if not getattr(self, "_stepped", False):
+            raise RuntimeError("MultiFrameTracker.download_labels: no step behind the front end (process_depth or process_depth_images)")
+        return self.labels if self.labels is not None else self.rtree.download_all_labels()
 
     def posed(self, stream):
         """(cloud (V,3), jointPos (J,3), jointTrans (J,12)) of the stream's last fit (one download; avt_get_posed)."""
@@ -373,7 +432,7 @@ class MultiFrameTracker:
         from . import fitscore, render
         if getattr(self, "bgsub", None) is None:
             raise RuntimeError("MultiFrameTracker.fit_score: no front end attached (attach_front_end)")
-        if self.labels is None:
+        if not getattr(self, "_stepped", False):
             raise RuntimeError("MultiFrameTracker.fit_score: no step behind the front end (process_depth or process_depth_images)")
         if not self.state_resident:
             raise RuntimeError("MultiFrameTracker.fit_score: no stream has been fitted yet")

@@ -11,12 +11,19 @@
 // RTree::predictBestFromBGSub on the masked depth where it lies on the device, one download of all labels, postProcess per stream
 // on the host (a sequential flood fill, as in the reference), then process() with the caller's XYZ maps.  processDepthImages() is
 // the same from depth images and one camera per stream (BGSubtractor::runBatchDepth, ark::subsampleFrameDepth): no XYZ map on the host.
+//
+// With deviceSubsample (attachFrontEnd; needs devicePostProcess) both run everything up to the fit on the device: the labels are
+// post-processed where they lie, avt_frames_subsample_* writes every stream's kept points into the context's frame slots and brings
+// back a table of counts (and the centroids of the streams that may reinitialise), the policy runs on the counts, and
+// avt_frames_subsample_commit makes the frames resident, a lost stream as an empty frame.  No label image comes down and no cloud
+// goes up; frames, budgets and states are those of the host path, bit for bit.  partMasks stays empty: downloadPartMasks() fetches.
 #pragma once
 #include <algorithm>
 #include <cstdint>
 #include <vector>
 
 #include "../avt_render.h"
+#include "../avt_subsample.h"
 #include "AvatarOptimizer.h"
 #include "BGSubtractor.h"
 #include "FitScore.h"
@@ -134,6 +141,11 @@ class MultiFrameTracker {
             std::copy(labels[(size_t)s].begin(), labels[(size_t)s].begin() + (long)cnz[(size_t)s], lab.begin() + offs[(size_t)s]);
         }
         ARK_AVT_CHECK(avt_frames_upload(ctx, S, data.data(), lab.data(), offs.data()));
+        fitResident(fitted);
+    }
+
+    /** fit() behind the frame install: start states, the batched fit, one download of all states */
+    void fitResident(const std::vector<int>& fitted) {
         if (!stateResident) {
             ARK_AVT_CHECK(avt_state_upload(ctx, S, p.data(), q.data(), w.data()));
             stateResident = true;
@@ -166,8 +178,12 @@ class MultiFrameTracker {
      *  outlive the tracker's use of them); the interval of predictBest / postProcess (demo.cpp:198) and postProcess's weight. */
     /** devicePostProcess: postProcess runs on the device for all streams at once (RTree::postProcessFromBGSub: connected components
      *  on the interval grid, the reference's result at rtree_interval 1 and a documented difference above it); comPre[s] is then the
-     *  forest's resident memory of slot s.  Off, postProcess runs per stream on the host as ever. */
-    void attachFrontEnd(BGSubtractor& bgsub, RTree& rtree, int rtree_interval = 2, double dist_to_pre_weight = 0.001, bool devicePostProcess = false) {
+     *  forest's resident memory of slot s.  Off, postProcess runs per stream on the host as ever.
+     *  deviceSubsample (needs devicePostProcess): the subsampling and the frame install run on the device too (avt_subsample.h). */
+    void attachFrontEnd(BGSubtractor& bgsub, RTree& rtree, int rtree_interval = 2, double dist_to_pre_weight = 0.001, bool devicePostProcess = false,
+                        bool deviceSubsample = false) {
+        if (deviceSubsample && !devicePostProcess) { std::fprintf(stderr, "MultiFrameTracker::attachFrontEnd: deviceSubsample needs devicePostProcess\n"); std::exit(1); }
+        deviceSub = deviceSubsample;
         frontBG = &bgsub; frontTree = &rtree; frontForest = nullptr;
         rtreeInterval = rtree_interval; distToPreWeight = dist_to_pre_weight; devicePost = devicePostProcess;
         comPre.assign((size_t)S, MatrixNX<2>());
@@ -176,7 +192,10 @@ class MultiFrameTracker {
     }
 
     /** The same front end with a forest of several trees in the tree's place (ark/RForest.h). */
-    void attachFrontEnd(BGSubtractor& bgsub, RForest& rforest, int rtree_interval = 2, double dist_to_pre_weight = 0.001, bool devicePostProcess = false) {
+    void attachFrontEnd(BGSubtractor& bgsub, RForest& rforest, int rtree_interval = 2, double dist_to_pre_weight = 0.001, bool devicePostProcess = false,
+                        bool deviceSubsample = false) {
+        if (deviceSubsample && !devicePostProcess) { std::fprintf(stderr, "MultiFrameTracker::attachFrontEnd: deviceSubsample needs devicePostProcess\n"); std::exit(1); }
+        deviceSub = deviceSubsample;
         frontBG = &bgsub; frontTree = nullptr; frontForest = &rforest;
         rtreeInterval = rtree_interval; distToPreWeight = dist_to_pre_weight; devicePost = devicePostProcess;
         comPre.assign((size_t)S, MatrixNX<2>());
@@ -192,6 +211,7 @@ class MultiFrameTracker {
         if (!frontBG || (!frontTree && !frontForest)) { std::fprintf(stderr, "MultiFrameTracker::processDepth: no front end attached\n"); std::exit(1); }
         if ((int)images.size() != S) { std::fprintf(stderr, "MultiFrameTracker: %d images for %d streams\n", (int)images.size(), S); std::exit(1); }
         frontBG->runBatch(images);
+        if (deviceSub) { fitDevice(fitted); return; }
         const std::vector<Rect> box = labelBatch();
         std::vector<Frame> frames((size_t)S);
         for (int s = 0; s < S; ++s) frames[(size_t)s] = {images[(size_t)s].data(), partMasks[(size_t)s].data(), partMasks[(size_t)s].cols, partMasks[(size_t)s].rows, box[(size_t)s]};
@@ -207,6 +227,7 @@ class MultiFrameTracker {
             std::exit(1);
         }
         frontBG->runBatchDepth(depths, intrins);
+        if (deviceSub) { fitDevice(fitted); return; }
         const std::vector<Rect> box = labelBatch();
         fit([&](int s, int interval) {
             return subsampleFrameDepth(depths[(size_t)s].data(), intrins[intrins.size() == 1 ? 0 : (size_t)s], partMasks[(size_t)s].data(),
@@ -215,6 +236,56 @@ class MultiFrameTracker {
     }
 
    private:
+    /** A depth-in step behind the batch run with everything up to the fit on the device (demo.cpp:196-265 for all streams) */
+    void fitDevice(std::vector<int>& fitted) {
+        if (frontTree) {
+            frontTree->predictBestFromBGSub(*frontBG, rtreeInterval, true, false);
+            ARK_AVT_CHECK(avt_rtree_post_process_from_bgsub(frontTree->handle(), frontBG->handle(), rtreeInterval, distToPreWeight));
+        } else {
+            frontForest->predictBestFromBGSub(*frontBG, rtreeInterval, true, false);
+            ARK_AVT_CHECK(avt_rforest_post_process_from_bgsub(frontForest->handle(), frontBG->handle(), rtreeInterval, distToPreWeight));
+        }
+        (void)frontBG->batchInfo(0);                   // the one read of the subtractor's fault word
+        std::vector<int> iv((size_t)S), counts((size_t)S * (1 + (size_t)numParts)), used(4 * (size_t)S);
+        std::vector<unsigned char> want((size_t)S), keep((size_t)S, 0);
+        std::vector<double> cen(3 * (size_t)S, 0.0);
+        for (int s = 0; s < S; ++s) { iv[(size_t)s] = streams[(size_t)s].interval; want[(size_t)s] = streams[(size_t)s].reinit ? 1 : 0; }
+        if (frontTree)
+            ARK_AVT_CHECK(avt_frames_subsample_rtree(ctx, frontTree->handle(), frontBG->handle(), nullptr, iv.data(), want.data(), counts.data(), cen.data(), used.data()));
+        else
+            ARK_AVT_CHECK(avt_frames_subsample_rforest(ctx, frontForest->handle(), frontBG->handle(), nullptr, iv.data(), want.data(), counts.data(), cen.data(), used.data()));
+        partMasks.clear();
+        fitted.assign((size_t)S, 0);
+        budgets.assign((size_t)S, 0);
+        reinitStreams.clear();
+        std::vector<Matrix3d> r((size_t)J);
+        std::vector<double> wz((size_t)K, 0.0);
+        CloudType one;
+        one.resize(3, 1);
+        for (int s = 0; s < S; ++s) {
+            for (int c = 0; c < 4; ++c) boxes[(size_t)s][(size_t)c] = used[4 * (size_t)s + c];
+            comPre[(size_t)s] = frontTree ? frontTree->comPre(s) : frontForest->comPre(s);
+            int icp = 0;
+            bool re = false;
+            if (!frameDecision(streams[(size_t)s], &counts[(size_t)s * (1 + (size_t)numParts)], numParts, icp, re)) continue;
+            fitted[(size_t)s] = keep[(size_t)s] = 1;
+            budgets[(size_t)s] = icp;
+            if (re) {
+                reinitStreams.push_back(s);
+                for (int c = 0; c < 3; ++c) one(c, 0) = cen[3 * (size_t)s + c];      // (the centroid of one point is the point)
+                reinitState(one, 1, &p[3 * (size_t)s], wz, r);
+                std::copy(wz.begin(), wz.end(), w.begin() + (size_t)K * s);
+                for (int j = 0; j < J; ++j) {
+                    const Quaterniond qq = rotationToQuaternion(r[(size_t)j]);
+                    for (int c = 0; c < 4; ++c) q[((size_t)s * J + j) * 4 + c] = qq.c[c];
+                }
+            }
+        }
+        if (std::find(fitted.begin(), fitted.end(), 1) == fitted.end()) return;
+        ARK_AVT_CHECK(avt_frames_subsample_commit(ctx, keep.data()));
+        fitResident(fitted);
+    }
+
     /** The front end behind the batch run, whatever its source: labels on the device, postProcess per stream; fills partMasks and
      *  boxes and returns every stream's box to subsample. */
     std::vector<Rect> labelBatch() {
@@ -248,6 +319,19 @@ class MultiFrameTracker {
     }
 
    public:
+    /** The post-processed part masks of the last depth-in step: partMasks where the step brought them down, one download where
+     *  it did not (deviceSubsample); partMasks holds them afterwards. */
+    const std::vector<Image8>& downloadPartMasks() {
+        if (!partMasks.empty() || !frontBG || frontBG->batchSize() <= 0) return partMasks;
+        const int n = frontBG->batchSize(), rows = frontBG->rows(), cols = frontBG->cols();
+        std::vector<std::uint8_t> all((size_t)n * rows * cols);
+        if (frontTree) ARK_AVT_CHECK(avt_rtree_labels_download_all(frontTree->handle(), all.data()));
+        else ARK_AVT_CHECK(avt_rforest_labels_download_all(frontForest->handle(), all.data()));
+        partMasks.assign((size_t)n, Image8(rows, cols));
+        for (int i = 0; i < n; ++i) std::copy(all.begin() + (size_t)i * rows * cols, all.begin() + (size_t)(i + 1) * rows * cols, partMasks[(size_t)i].data());
+        return partMasks;
+    }
+
     /** ava.cloud (3 x V), jointPos (3 x J), jointTrans (12 x J) of stream s's last fit; any pointer may be null (avt_get_posed) */
     void posed(int s, double* cloud_3xV, double* joint_pos_3xJ = nullptr, double* joint_trans_12xJ = nullptr) {
         ARK_AVT_CHECK(avt_get_posed(ctx, s, cloud_3xV, joint_pos_3xJ, joint_trans_12xJ));
@@ -322,6 +406,7 @@ class MultiFrameTracker {
     int rtreeInterval = 2;
     double distToPreWeight = 0.001;
     bool devicePost = false;
+    bool deviceSub = false;                        // read-only: set by attachFrontEnd
 
    private:
     std::vector<double> p, q, w;

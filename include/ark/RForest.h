@@ -269,6 +269,9 @@ public:
     int partMapType = 0;
     int totalNodes = 0, totalLeafs = 0;
 
+    /** The C handle (MultiFrameTracker's device subsampling, avt_subsample.h) */
+    avt_rforest* handle() const { return h_; }
+
 private:
     void build(const std::vector<RTree*>& trees) {
         std::vector<const avt_rtree*> hs;

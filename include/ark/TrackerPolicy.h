@@ -70,14 +70,27 @@ inline size_t subsampleFrameDepth(const float* depth, const CameraIntrin& intrin
  *  :379-383 - demo.cpp:225 only skips the frame, the documented deviation FrameTracker keeps); else sets the ICP iterations and
  *  whether the stream reinitialises (demo.cpp:252-265, live-demo.cpp:417-418). */
 template <class T>
+bool frameDecision(T& tr, const int* countRow, int numParts, int& icpIters, bool& reinitNow);
+
+template <class T>
 bool frameDecision(T& tr, const VectorXi& labels, size_t cnz, int numParts, int& icpIters, bool& reinitNow) {
+    std::vector<int> row((size_t)numParts + 1, 0);
+    row[0] = (int)cnz;
+    if (tr.firstTime && tr.initialPerPartCnz > 0)      // the only reader of the per-part counts
+        for (size_t i = 0; i < cnz; ++i) ++row[1 + (size_t)labels[i]];
+    return frameDecision(tr, row.data(), numParts, icpIters, reinitNow);
+}
+
+/** The same decision on the frame's row of the device subsampling's table (avt_subsample.h): countRow[0] points in all,
+ *  countRow[1 + q] of part q - the policy reads nothing else of a frame. */
+template <class T>
+bool frameDecision(T& tr, const int* countRow, int numParts, int& icpIters, bool& reinitNow) {
+    const size_t cnz = (size_t)countRow[0];
     // An EMPTY frame is never fitted whatever reinitCnz says: the reinitialisation centroid divides by cnz.
     bool part_missing = false;       // live-demo.cpp:376-380: the FIRST fit wants every body part seen (initialPerPartCnz pixels at interval 1)
     if (tr.firstTime && tr.initialPerPartCnz > 0) {
-        std::vector<size_t> partCnz((size_t)numParts, 0);
-        for (size_t i = 0; i < cnz; ++i) ++partCnz[(size_t)labels[i]];
-        size_t mn = partCnz.empty() ? 0 : partCnz[0];
-        for (size_t v : partCnz) mn = v < mn ? v : mn;
+        size_t mn = numParts > 0 ? (size_t)countRow[1] : 0;
+        for (int q = 0; q < numParts; ++q) mn = (size_t)countRow[1 + q] < mn ? (size_t)countRow[1 + q] : mn;
         const int need = tr.initialPerPartCnz / (tr.interval * tr.interval);
         part_missing = mn < (size_t)(need > 1 ? need : 1);
     }
