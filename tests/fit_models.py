@@ -215,30 +215,36 @@ def state_distance(a, b):
     return max(float(np.abs(np.asarray(x, np.float64).ravel() - np.asarray(y, np.float64).ravel()).max()) if np.size(x) else 0.0 for x, y in zip(a, b))
 
 
-def study(case):
-    """dict of the case: model, om (OracleModel), frame, and at the start state with the oracle's correspondences of the first ICP iteration:
-    corr, H, g (with the betas, aggregate = 1), A = H + lambda0 D, cond, delta_ld / pivots / pred (fit_restatement.lm_step_ld), target =
-    retract(start, delta_ld), bound = 64 cond(A) 2^-53 max|delta_ld|, step1 (the oracle's one-iteration run), e_oracle (its distance from target)."""
-    if case in _STUDY:
-        return _STUDY[case]
+def study_frame(m, om, fr):
+    """What study() holds of a case, for any model m (om: its OracleModel) and frame fr of it."""
     import fit_restatement as fr_
-    from oracle import oracle as orc
-    m = case_model(case)
-    om = orc.OracleModel(m)
-    fr = case_frame(case, om)
     p0, q0, w0 = fr["start"]
     opt1 = options(fr, icp_iters=1, max_iters_per_icp=1)
     step1 = om.optimize(fr["part_map"], fr["num_parts"], fr["data"], fr["labels"], opt1, p0, q0, w0, aggregate=1)
     cost, g, H, _ = om.evaluate(p0, q0, w0, step1["corr"], fr["data"], fr["betas"][0], fr["betas"][1], aggregate=1)
     lam = opt1.lm_lambda0
     A = H + lam * np.diag(np.diag(H))
-    s = dict(case=case, model=m, om=om, frame=fr, corr=step1["corr"], H=H, g=g, cost=cost, lam=lam, A=A, step1=step1)
+    s = dict(model=m, om=om, frame=fr, corr=step1["corr"], H=H, g=g, cost=cost, lam=lam, A=A, step1=step1)
     if (np.diag(H) > 0).all():
         s["cond"] = float(np.linalg.cond(A))
         delta, piv, pred = fr_.lm_step_ld(H, g, lam)
         s.update(delta_ld=delta, pivots=piv, pred=pred, target=om.retract(p0, q0, w0, delta))
         s["bound"] = 64.0 * s["cond"] * 2.0 ** -53 * float(np.abs(delta).max())
         s["e_oracle"] = state_distance((step1["p"], step1["q"], step1["w"]), s["target"])
+    return s
+
+
+def study(case):
+    """dict of the case: model, om (OracleModel), frame, and at the start state with the oracle's correspondences of the first ICP iteration:
+    corr, H, g (with the betas, aggregate = 1), A = H + lambda0 D, cond, delta_ld / pivots / pred (fit_restatement.lm_step_ld), target =
+    retract(start, delta_ld), bound = 64 cond(A) 2^-53 max|delta_ld|, step1 (the oracle's one-iteration run), e_oracle (its distance from target)."""
+    if case in _STUDY:
+        return _STUDY[case]
+    from oracle import oracle as orc
+    m = case_model(case)
+    om = orc.OracleModel(m)
+    s = study_frame(m, om, case_frame(case, om))
+    s["case"] = case
     _STUDY[case] = s
     return s
 
@@ -263,24 +269,35 @@ def lambda_conditioning(case):
     the factor by 6 u^2 times that.  A fit whose last steps shave 1e-6 off the cost has kappa ~ 1e6: its lambda says more about the last bits
     of the cost than about the kernels."""
     s = study(case)
-    fr, om = s["frame"], s["om"]
+    r = replay_fit(s["om"], s["frame"])
+    return r["lam"], r["kappa"]
+
+
+def replay_fit(om, fr):
+    """lambda_conditioning's replay for any frame fr of om's model: dict(lam, kappa, acc (1 accepted / 0 rejected / -1 not factorable, per GN
+    iteration), states (the start and the state behind every accepted step), icp_states (the state each ICP iteration's correspondences are
+    searched at), comps ((minimising mixture component at the current point, at the trial point) per factorable GN iteration; -1 without a prior))."""
     bp, bs = fr["betas"]
     opt = options(fr, icp_iters=2, max_iters_per_icp=4)
     p, q, w = (np.array(x, np.float64) for x in fr["start"])
     lam, nu, kappa = opt.lm_lambda0, opt.lm_up, 0.0
+    acc, states, icp_states, comps = [], [(p, q, w)], [], []
     for icp in range(opt.icp_iters):
+        icp_states.append((p, q, w))
         corr = om.optimize(fr["part_map"], fr["num_parts"], fr["data"], fr["labels"], options(fr, icp_iters=1, max_iters_per_icp=0), p, q, w, aggregate=1)["corr"]
-        c, g, H, _ = om.evaluate(p, q, w, corr, fr["data"], bp, bs, aggregate=1)
+        c, g, H, comp = om.evaluate(p, q, w, corr, fr["data"], bp, bs, aggregate=1)
         for it in range(opt.max_iters_per_icp):
             D = np.diag(H)
             try:
                 L = np.linalg.cholesky(H + lam * np.diag(D))
             except np.linalg.LinAlgError:
                 lam = min(lam * nu, opt.lm_lambda_max); nu *= 2.0
+                acc.append(-1)
                 continue
             d = -np.linalg.solve(L.T, np.linalg.solve(L, g))
             p2, q2, w2 = om.retract(p, q, w, d)
-            c2, g2, H2, _ = om.evaluate(p2, q2, w2, corr, fr["data"], bp, bs, aggregate=1)
+            c2, g2, H2, comp2 = om.evaluate(p2, q2, w2, corr, fr["data"], bp, bs, aggregate=1)
+            comps.append((comp, comp2))
             if c2 < c:
                 pred = 0.5 * float((d * (lam * D * d - g)).sum())
                 rho = (c - c2) / pred
@@ -291,9 +308,12 @@ def lambda_conditioning(case):
                 lam = min(max(lam * max(opt.lm_down, f), opt.lm_lambda_min), opt.lm_lambda_max)
                 nu = opt.lm_up
                 done = opt.function_tolerance > 0.0 and (c - c2) <= opt.function_tolerance * c
-                p, q, w, c, g, H = p2, q2, w2, c2, g2, H2
+                p, q, w, c, g, H, comp = p2, q2, w2, c2, g2, H2, comp2
+                acc.append(1)
+                states.append((p, q, w))
                 if done:
                     break
             else:
                 lam = min(lam * nu, opt.lm_lambda_max); nu *= 2.0
-    return lam, kappa
+                acc.append(0)
+    return dict(lam=lam, kappa=kappa, acc=acc, states=states, icp_states=icp_states, comps=comps)
