@@ -318,6 +318,47 @@ class Context:
         check(self._lib.avt_get_gated(self.h, C.c_int(frame), C.byref(n)))
         return int(n.value)
 
+    def set_corr_trim(self, quantile=None, factor=1.0, floor=0.0, min_matches=1):
+        """avt_set_corr_trim: trimmed ICP for every search this context runs from now on.  quantile None: off (the default).  Else per
+        part (scalars: every part alike; sequences of num_parts values: per part, factor +inf = off for that part) a match is kept iff
+        its squared distance d2 <= max(factor^2 * t, floor^2), t the ceil(quantile * n)-th smallest d2 of the n matches the search left
+        the part in this frame; a part with fewer than min_matches matches is left alone.  A trimmed query gets no correspondence (-1),
+        like a gated one.  Not a reference behaviour; no value is offered."""
+        if quantile is None:
+            check(self._lib.avt_set_corr_trim(self.h, C.c_int(0), None, None, None, C.c_int(1)))
+            return
+        n = max(np.size(quantile), np.size(factor), np.size(floor))
+        arrs = []
+        for v in (quantile, factor, floor):
+            a = np.atleast_1d(np.asarray(v, np.float64)).reshape(-1)
+            arrs.append(np.ascontiguousarray(np.full(n, a[0]) if len(a) == 1 else a))
+        if any(len(a) != n for a in arrs):
+            raise ValueError("set_corr_trim: quantile, factor and floor must be scalars or sequences of one length")
+        check(self._lib.avt_set_corr_trim(self.h, C.c_int(n), dptr(arrs[0]), dptr(arrs[1]), dptr(arrs[2]), C.c_int(int(min_matches))))
+
+    def corr_trim(self):
+        """The trim settings in force (avt_get_corr_trim): (quantile, factor, floor) float64 (num_parts,) each - factor +inf where a part
+        is off - and min_matches."""
+        r, k, f = np.empty(self.num_parts), np.empty(self.num_parts), np.empty(self.num_parts)
+        mm = C.c_int()
+        check(self._lib.avt_get_corr_trim(self.h, dptr(r), dptr(k), dptr(f), C.byref(mm)))
+        return r, k, f, int(mm.value)
+
+    def trimmed(self, frame=0, per_part=False):
+        """How many matches `frame`'s last search lost to the trim (avt_get_trimmed); per_part: (total, int32 (num_parts,)).  Valid where
+        gated is."""
+        n = C.c_int()
+        pp = np.zeros(self.num_parts, np.int32)
+        check(self._lib.avt_get_trimmed(self.h, C.c_int(frame), C.byref(n), iptr(pp)))
+        return (int(n.value), pp) if per_part else int(n.value)
+
+    def trim_thresholds(self, frame=0):
+        """The thresholds T on d2 that `frame`'s last search used, float64 (num_parts,), +inf where it could drop nothing
+        (avt_get_trim_thresholds)."""
+        out = np.empty(self.num_parts)
+        check(self._lib.avt_get_trim_thresholds(self.h, C.c_int(frame), dptr(out)))
+        return out
+
     def nn(self, model_cloud, visible, data, labels):
         mc = np.ascontiguousarray(model_cloud, np.float64); vis = np.ascontiguousarray(visible, np.uint8)
         data = np.ascontiguousarray(data, np.float64); labels = np.ascontiguousarray(labels, np.int32)
@@ -662,7 +703,11 @@ class AvatarOptimizer:
 
     max_corr_dist (default +inf = off) is NOT a reference member either: a data point further than this from the nearest visible model
     point of its part gets no correspondence (avt_set_corr_gate, include/avt.h); a sequence of numParts values gates per part
-    (set_correspondence_gate).  Followed before every fit; last_gated() tells how many points the last fit's last search dropped."""
+    (set_correspondence_gate).  Followed before every fit; last_gated() tells how many points the last fit's last search dropped.
+
+    trimQuantile / trimFactor / trimFloor / trimMinMatches (default trimFactor +inf = off) are NOT reference members: trimmed ICP
+    (avt_set_corr_trim, include/avt.h) - a scalar or numParts values each.  Followed before every fit; last_trimmed() tells how many
+    matches the last fit's last search took back."""
 
     ROT_SIZE = 4
 
@@ -680,6 +725,8 @@ class AvatarOptimizer:
         self._occ_applied = None                           # what the context was last told (avt_set_occlusion_render)
         self.max_corr_dist = math.inf                      # not a reference member: the correspondence gate (avt_set_corr_gate), off
         self._gate_applied = None                          # what the context was last told
+        self.trimQuantile, self.trimFactor, self.trimFloor, self.trimMinMatches = 1.0, math.inf, 0.0, 1   # not reference members: trimmed ICP (avt_set_corr_trim), off
+        self._trim_applied = None
         self.functionTolerance = 1e-4                      # not a member of the reference's class: what its optimize() hard-codes at AvatarOptimizer.cpp:1333 (0 = no early exit)
         self.r = np.zeros((J, 4)); self.r[:, 3] = 1.0      # quaternions (x,y,z,w), :25
         self.ctx = Context(ava.model, self.numParts, self.partMap, max_points, 1)
@@ -718,10 +765,25 @@ class AvatarOptimizer:
             self.ctx.set_corr_gate(None if want == (math.inf,) else want)
             self._gate_applied = want
 
+    def last_trimmed(self):
+        """Matches the last search of the last optimize() lost to the trim (Context.trimmed)."""
+        return self.ctx.trimmed(0)
+
+    def _apply_corr_trim(self):
+        tup = lambda v: tuple(float(x) for x in np.atleast_1d(v))
+        want = (tup(self.trimQuantile), tup(self.trimFactor), tup(self.trimFloor), int(self.trimMinMatches))
+        if want != self._trim_applied:
+            if all(k == math.inf for k in want[1]):
+                self.ctx.set_corr_trim(None)
+            else:
+                self.ctx.set_corr_trim(self.trimQuantile, self.trimFactor, self.trimFloor, self.trimMinMatches)
+            self._trim_applied = want
+
     def optimize(self, data_cloud, data_part_labels, icp_iters=1, num_threads=4):
         ava = self.ava
         self._apply_render_occlusion()
         self._apply_corr_gate()
+        self._apply_corr_trim()
         self.r = rot_to_quat(ava.r)                                              # :1250-1254
         if icp_iters >= 1:      # one call, one synchronisation: the fit and the outputs of the update() the launch sequence ends with (:1497)
             ava.p, self.r, ava.w, self.last_stats, ava.cloud, ava.jointPos, ava.jointTrans = self.ctx.optimize_posed(

@@ -249,6 +249,10 @@ SIGNATURES = {
     "avt_set_corr_gate": [_vp, C.c_int, c_double_p],
     "avt_get_corr_gate": [_vp, c_double_p],
     "avt_get_gated": [_vp, C.c_int, c_int_p],
+    "avt_set_corr_trim": [_vp, C.c_int, c_double_p, c_double_p, c_double_p, C.c_int],
+    "avt_get_corr_trim": [_vp, c_double_p, c_double_p, c_double_p, c_int_p],
+    "avt_get_trimmed": [_vp, C.c_int, c_int_p, c_int_p],
+    "avt_get_trim_thresholds": [_vp, C.c_int, c_double_p],
     "avt_debug_trace": [_vp, C.c_int, c_double_p],
     "avt_debug_mfma_count": [_vp, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)],
     "avt_debug_nn_sums": [_vp, C.c_int, c_int_p, C.POINTER(C.c_longlong), c_double_p],

@@ -188,7 +188,7 @@ void enqueue_optimize(avt_ctx* c, const avt_options* o, int f0, int nf, hipStrea
     if (hold) launch_budget_hold(c, nf, budget, c->budget_hold, 0, false, 2);      // ... and its skinning
     for (int icp = 0; icp < o->icp_iters; ++icp) {
         { ProfScope ps(c, AVT_K_VISIBILITY); launch_visibility(c, nf, o->enable_occlusion, fuse_bucket && icp == 0); }
-        { ProfScope ps(c, AVT_K_NN); launch_nn(c, nf); }
+        { ProfScope ps(c, AVT_K_NN); launch_nn(c, nf); if (c->trim_on) launch_trim(c, nf); }
         if (c->fb.use_moments) {
             // Moment form (avt_moments.hip): the correspondences' sufficient statistics once per ICP iteration, then every GN iteration
             // assembles its normal equations from them - no Jacobian rows, no partial tiles, no reduction.
@@ -286,6 +286,7 @@ int run_optimize(avt_ctx* c, const avt_options* o, const int* budget = nullptr) 
     if (check_optimize(c, o)) return 1;
     if (sync_params(c, o)) return 1;
     c->ran_max_iters = o->max_iters_per_icp;
+    if (o->icp_iters > 0) c->trim_last = c->trim_on;      // (no ICP iteration: no search, the last one's counts stand)
     // Large batches run as several frame groups: the latency-bound single-workgroup-per-frame kernels of one group
     // (k_solve, k_finalize, k_reduce) overlap the throughput kernels (k_eval, k_nn) of the others on separate streams.
     // The instrumented (profiling) path keeps the SAME groups and launch shapes and runs them one after the other on
@@ -312,8 +313,9 @@ int run_optimize(avt_ctx* c, const avt_options* o, const int* budget = nullptr) 
     // only enqueue, so the lock is held for microseconds.
     std::lock_guard<std::mutex> graph_lock(g_graph_mutex);
     char key[200];
-    snprintf(key, sizeof key, "%d|%d|%d|%d|%d|%d|%d|%d|%dx%d%s", nf, ngroups, c->fb.G, c->launch_maxN, o->icp_iters, o->max_iters_per_icp, o->enable_occlusion, c->fb.use_moments,
-             c->occ_w, c->occ_w > 0 ? c->occ_h : 0, budget ? "|budgets" : "");      // (the budgets themselves live in device memory: a changing pattern replays the same graph)
+    snprintf(key, sizeof key, "%d|%d|%d|%d|%d|%d|%d|%d|%dx%d%s%s", nf, ngroups, c->fb.G, c->launch_maxN, o->icp_iters, o->max_iters_per_icp, o->enable_occlusion, c->fb.use_moments,
+             c->occ_w, c->occ_w > 0 ? c->occ_h : 0, budget ? "|budgets" : "",      // (the budgets themselves live in device memory: a changing pattern replays the same graph)
+             c->trim_on ? "|trim" : "");                                            // (one launch more per search; its settings live in device memory too)
     avt_ctx::GraphEntry* hit = nullptr;
     for (auto& e : c->graphs) if (e.key == key) { hit = &e; break; }
     if (!hit) {
@@ -835,6 +837,8 @@ int avt_nn(avt_ctx* c, const double* model_cloud, const unsigned char* visible, 
         AVT_HIP(hipMemcpyAsync(c->fb.pcy, py.data(), V * sizeof(double), hipMemcpyHostToDevice, c->stream));
         AVT_HIP(hipMemcpyAsync(c->fb.pcz, pz.data(), V * sizeof(double), hipMemcpyHostToDevice, c->stream));
         AVT_HIP(hipMemcpyAsync(c->fb.visible, visible, (size_t)V, hipMemcpyHostToDevice, c->stream));
+        // k_trim forms a match's distance from the cloud by vertex id (inside optimize() k_lbs wrote it beside the part-sorted copy)
+        if (c->trim_on) AVT_HIP(hipMemcpyAsync(c->fb.cloud, model_cloud, (size_t)3 * V * sizeof(double), hipMemcpyHostToDevice, c->stream));
         std::unique_ptr<unsigned char[]> vs;
         if (c->tun.nn_force_vis) {      // the fused shape reads the flags in part-sorted order (inside optimize(): k_lbs / k_visibility keep them)
             vs.reset(new unsigned char[V]);
@@ -846,7 +850,8 @@ int avt_nn(avt_ctx* c, const double* model_cloud, const unsigned char* visible, 
         ctl.N = N;
         AVT_HIP(hipMemcpyAsync(c->fb.ctl, &ctl, sizeof(ctl), hipMemcpyHostToDevice, c->stream));
         { ProfScope ps(c, AVT_K_BUCKET); launch_bucket(c, 1, true); }
-        { ProfScope ps(c, AVT_K_NN); launch_nn(c, 1); }
+        { ProfScope ps(c, AVT_K_NN); launch_nn(c, 1); if (c->trim_on) launch_trim(c, 1); }
+        c->trim_last = c->trim_on;
         if (check_launch("k_nn")) return 1;
         AVT_HIP(hipMemcpyAsync(out, c->fb.corr, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         AVT_HIP(hipStreamSynchronize(c->stream));
@@ -1315,6 +1320,114 @@ int avt_get_gated(avt_ctx* c, int frame, int* gated) {
         if (!after_nn && !after_opt) { avt_set_error("avt_get_gated: neither a stand-alone avt_nn (frame 0) nor an optimize call with an ICP iteration has run last"); return 1; }
         AVT_HIP(hipSetDevice(c->device));
         AVT_HIP(hipMemcpyAsync(gated, c->fb.gated + frame, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        AVT_HIP(hipStreamSynchronize(c->stream));
+        return 0;
+    });
+}
+
+// ---- trimmed ICP (avt_trim.hip) ----
+int avt_set_corr_trim(avt_ctx* c, int n, const double* quantile, const double* factor, const double* floor_dist, int min_matches) {
+    return avt_guard("avt_set_corr_trim", [&]() -> int {
+        if (!c) { avt_set_error("avt_set_corr_trim: null context"); return 1; }
+        const int np = c->dm.d.num_parts;
+        const double inf = std::numeric_limits<double>::infinity();
+        if (!quantile || !factor || !floor_dist) {
+            if (n != 0 && (quantile || factor || floor_dist)) { avt_set_error("avt_set_corr_trim: quantile, factor and floor_dist go together (all NULL: off)"); return 1; }
+            n = 0;
+        }
+        if (n != 0 && n != 1 && n != np) {
+            avt_set_error("avt_set_corr_trim: " + std::to_string(n) + " values; 0 (off), 1 (every part) or num_parts = " + std::to_string(np) + " wanted");
+            return 1;
+        }
+        if (n > 0 && min_matches < 1) { avt_set_error("avt_set_corr_trim: min_matches = " + std::to_string(min_matches) + "; >= 1 wanted (values are per part: 1 or num_parts = " + std::to_string(np) + ")"); return 1; }
+        for (int i = 0; i < n; ++i) {
+            const double r = quantile[i], k = factor[i], fl = floor_dist[i];
+            // (a NaN fails every comparison)
+            const bool ok = r > 0.0 && r <= 1.0 && k >= 0.0 && (k == inf || k * k < inf) && fl >= 0.0 && fl < inf;
+            if (!ok) {
+                avt_set_error("avt_set_corr_trim: value " + std::to_string(i) + " of the 1 or num_parts = " + std::to_string(np) +
+                              " is refused (quantile in (0, 1]; factor >= 0 with a finite square, or +inf; floor_dist >= 0 and finite; no NaN)");
+                return 1;
+            }
+        }
+        std::vector<double> rho((size_t)np, 1.0), kap((size_t)np, inf), flo((size_t)np, 0.0), set((size_t)3 * np + 1);
+        for (int q = 0; q < np && n > 0; ++q) { const int i = n == 1 ? 0 : q; rho[(size_t)q] = quantile[i]; kap[(size_t)q] = factor[i]; flo[(size_t)q] = floor_dist[i]; }
+        bool on = false;
+        for (int q = 0; q < np; ++q) {
+            set[(size_t)q] = rho[(size_t)q];
+            set[(size_t)np + q] = kap[(size_t)q] * kap[(size_t)q];
+            set[(size_t)2 * np + q] = flo[(size_t)q] * flo[(size_t)q];
+            on = on || kap[(size_t)q] < inf;
+        }
+        const int mm = n > 0 ? min_matches : 1;
+        set[(size_t)3 * np] = (double)mm;
+        if (on) {
+            AVT_HIP(hipSetDevice(c->device));
+            if (!c->trim_set.p) {      // the first time trimming is enabled
+                const size_t fn = (size_t)c->fb.max_frames * np;
+                if (c->trim_set.reserve(set.size()) || c->trim_thr.reserve(fn) || c->trim_count.reserve(fn)) return 1;
+                c->trim_set_host.clear();
+            }
+            if (set != c->trim_set_host) {
+                AVT_HIP(hipStreamSynchronize(c->stream));      // (nothing queued reads trim_set_host any more)
+                c->trim_set_host = set;
+                // on the context's stream, behind every search already queued; not part of the launch shape
+                AVT_HIP(hipMemcpyAsync(c->trim_set.p, c->trim_set_host.data(), set.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+                AVT_HIP(hipStreamSynchronize(c->stream));
+            }
+        }
+        c->trim_rho = rho; c->trim_kappa = kap; c->trim_floor = flo; c->trim_min_matches = mm; c->trim_on = on;
+        return 0;
+    });
+}
+
+int avt_get_corr_trim(avt_ctx* c, double* quantile, double* factor, double* floor_dist, int* min_matches) {
+    if (!c) { avt_set_error("avt_get_corr_trim: null context"); return 1; }
+    const size_t np = (size_t)c->dm.d.num_parts;
+    const bool never = c->trim_rho.empty();      // never set: off
+    for (size_t q = 0; q < np; ++q) {
+        if (quantile) quantile[q] = never ? 1.0 : c->trim_rho[q];
+        if (factor) factor[q] = never ? std::numeric_limits<double>::infinity() : c->trim_kappa[q];
+        if (floor_dist) floor_dist[q] = never ? 0.0 : c->trim_floor[q];
+    }
+    if (min_matches) *min_matches = c->trim_min_matches;
+    return 0;
+}
+
+// where the counts of avt_get_gated are valid, those of the trim are
+static int trim_search_ran(avt_ctx* c, const char* who, int frame) {
+    if (frame < 0 || frame >= c->fb.max_frames) { avt_set_error(std::string(who) + ": bad argument"); return 1; }
+    const bool after_nn = c->nn_sums_frame0 && !c->frames_valid && frame == 0;
+    const bool after_opt = c->frames_valid && c->ran_icp_iters > 0 && frame < c->nframes;
+    if (!after_nn && !after_opt) { avt_set_error(std::string(who) + ": neither a stand-alone avt_nn (frame 0) nor an optimize call with an ICP iteration has run last"); return 1; }
+    return 0;
+}
+
+int avt_get_trimmed(avt_ctx* c, int frame, int* total, int* per_part) {
+    return avt_guard("avt_get_trimmed", [&]() -> int {
+        if (!c || !total) { avt_set_error("avt_get_trimmed: null argument"); return 1; }
+        if (trim_search_ran(c, "avt_get_trimmed", frame)) return 1;
+        const int np = c->dm.d.num_parts;
+        std::vector<int> n((size_t)np, 0);
+        if (c->trim_last) {      // (a search without trimming dropped nothing, whatever an earlier one left in the block)
+            AVT_HIP(hipSetDevice(c->device));
+            AVT_HIP(hipMemcpyAsync(n.data(), c->trim_count.p + (size_t)frame * np, (size_t)np * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+            AVT_HIP(hipStreamSynchronize(c->stream));
+        }
+        *total = 0;
+        for (int q = 0; q < np; ++q) { *total += n[(size_t)q]; if (per_part) per_part[q] = n[(size_t)q]; }
+        return 0;
+    });
+}
+
+int avt_get_trim_thresholds(avt_ctx* c, int frame, double* T) {
+    return avt_guard("avt_get_trim_thresholds", [&]() -> int {
+        if (!c || !T) { avt_set_error("avt_get_trim_thresholds: null argument"); return 1; }
+        if (trim_search_ran(c, "avt_get_trim_thresholds", frame)) return 1;
+        const int np = c->dm.d.num_parts;
+        if (!c->trim_last) { std::fill(T, T + np, std::numeric_limits<double>::infinity()); return 0; }
+        AVT_HIP(hipSetDevice(c->device));
+        AVT_HIP(hipMemcpyAsync(T, c->trim_thr.p + (size_t)frame * np, (size_t)np * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         AVT_HIP(hipStreamSynchronize(c->stream));
         return 0;
     });

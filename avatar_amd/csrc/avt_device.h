@@ -24,6 +24,13 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+// round-to-nearest-even of x (|x| < 2^51) as an integer: the low mantissa bits of x + 1.5*2^52 (what __double2ll_rn
+// returns, in two instructions instead of a conversion sequence)
+__device__ __forceinline__ long long rint_to_ll(double x) {
+    const double C = 6755399441055744.0;
+    return __double_as_longlong(x + C) - __double_as_longlong(C);
+}
+
 // Eigen-style quaternion (x,y,z,w) -> row-major 3x3 (Quaternion::toRotationMatrix closed form)
 __device__ __forceinline__ void quat_to_rot(const double* q, double* R) {
     const double tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2];

@@ -198,6 +198,7 @@ struct AvtSolveSnap {
 // FrameBuffers::fault bits
 #define AVT_FAULT_NOT_RESIDENT 2u   // (batch split) the owning rank's context did not hold the frame when the results were gathered
 #define AVT_FAULT_RIDE_TIMEOUT 1u   // a solver role of a riding k_solve launch gave up waiting for the reduction workgroups of its launch
+#define AVT_FAULT_TRIM 4u           // a k_trim workgroup met a state it could not vouch for (avt_trim.hip) and took nothing back
 
 #define AVT_TRY_DONE 2
 struct AvtRunParams {
@@ -346,6 +347,21 @@ struct FrameBuffers {
     int* gated;           // [max_frames] queries of the frame's last search that had a nearest visible model point and lost it to the gate
 };
 
+// What k_trim (avt_trim.hip, avt_set_corr_trim) is handed: a small block of its own, so that FrameBuffers and with it every other
+// kernel's argument layout stay where they are.  The settings live in device memory (a changed value replays the same captured graph).
+struct AvtTrimArgs {
+    const int* part_off; const int* dorig;
+    const double* dx; const double* dy; const double* dz;
+    const double* cloud;          // the model points the search read (FrameBuffers::cloud)
+    int* corr; int* corr_sorted; int* cnt; long long* fsum;
+    const AvtFrameCtl* ctl;
+    unsigned* fault;
+    const double* set;            // [3 num_parts + 1] quantile rho | factor squared k2 (+inf: part not trimmed) | floor squared f2 | min_matches
+    int* trimmed;                 // [max_frames][num_parts] matches the frame's last search lost to the trim, per part
+    double* thr;                  // [max_frames][num_parts] the thresholds T it used (+inf: nothing could be dropped)
+    int f0, num_parts, V, max_points;
+};
+
 struct avt_model {
     AvtDims d;
     // host copies (used by avt_ctx_create to build the device model and by accessors)
@@ -405,6 +421,14 @@ struct avt_ctx {
     unsigned long long graph_clock = 0;
     AvtRunParams params_host = {};      // what fb.params currently holds
     std::vector<double> gate_host, gate2_host;   // the gates as avt_set_corr_gate was given them (num_parts, +inf = off) and what fb.gate2 holds
+    // avt_set_corr_trim: the settings as given (num_parts each; factor +inf = that part is off, the default), whether any part is on,
+    // what trim_set holds, and whether the last search of the context ran with trimming on (else it dropped nothing, whatever
+    // trim_count still holds).  The three device blocks are allocated the first time trimming is enabled: 3 num_parts + 1 doubles and
+    // max_frames x num_parts x 12 bytes.
+    std::vector<double> trim_rho, trim_kappa, trim_floor, trim_set_host;
+    int trim_min_matches = 1;
+    bool trim_on = false, trim_last = false;
+    DevBuf<double> trim_set, trim_thr; DevBuf<int> trim_count;
     bool params_valid = false;
     bool frames_valid = false, state_valid = false;   // resident frames / start state usable by avt_optimize_resident
     bool nn_sums_frame0 = false;        // a stand-alone avt_nn has left its counts and sums in frame slot 0 (avt_debug_nn_sums)
@@ -454,6 +478,7 @@ void launch_visibility_render(avt_ctx* c, int nframes, bool with_bucket_scatter)
 void launch_bucket(avt_ctx* c, int nframes, bool clear_after);
 void launch_state_reset(avt_ctx* c, int nframes);
 void launch_nn(avt_ctx* c, int nframes);
+void launch_trim(avt_ctx* c, int nframes);                // avt_trim.hip: behind launch_nn when c->trim_on
 void launch_finalize(avt_ctx* c, int nframes);
 void launch_eval(avt_ctx* c, int nframes, bool cost_only = false, int next_seq = 0 /* which solve of the ICP iteration follows (riding shapes) */);
 int avt_solve_nspec(const avt_ctx* c, int nframes);       // speculative solver workgroups per frame of the k_solve launch that follows an evaluation (0: none)

@@ -36,13 +36,6 @@
 #endif
 
 
-// round-to-nearest-even of x (|x| < 2^51) as an integer: the low mantissa bits of x + 1.5*2^52 (what __double2ll_rn
-// returns, in two instructions instead of a conversion sequence)
-__device__ __forceinline__ long long rint_to_ll(double x) {
-    const double C = 6755399441055744.0;
-    return __double_as_longlong(x + C) - __double_as_longlong(C);
-}
-
 // ---- the correspondence gate (avt_set_corr_gate).  Applied to the WINNER of a search, after the scan: a query whose
 // exact minimum squared distance d2 exceeds g2 = gate * gate of its part loses its match and is from here on a query whose part has no
 // visible model point.  g2 = +inf (the default) makes the test false for every d2, NaN included: nothing changes.  It is never a search

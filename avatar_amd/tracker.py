@@ -86,12 +86,16 @@ def reinit_state(data, num_joints, num_shape_keys):
 class FrameTracker:
     def __init__(self, ava_opt: "api.AvatarOptimizer", interval=12, frame_icp_iters=3, reinit_icp_iters=6, reinit_cnz=1000,
                  num_threads=4, rtree=None, rtree_interval=2, dist_to_pre_weight=0.001, initial_per_part_cnz=0, initial_icp_iters=None,
-                 render_occlusion=None, max_corr_dist=None):
+                 render_occlusion=None, max_corr_dist=None, corr_trim=None):
         """render_occlusion: True / False sets ava_opt.renderOcclusion (self-occlusion from a face-id render at the optimizer's own
         intrin and imageSize; not a reference behaviour); None leaves it as it is.
         max_corr_dist: a distance or numParts distances sets ava_opt.max_corr_dist (the correspondence gate, api.Context.set_corr_gate;
-        not a reference behaviour); None leaves it as it is."""
+        not a reference behaviour); None leaves it as it is.
+        corr_trim: (quantile, factor, floor, min_matches) sets ava_opt.trimQuantile / trimFactor / trimFloor / trimMinMatches (trimmed
+        ICP, api.Context.set_corr_trim; not a reference behaviour); None leaves them as they are."""
         self.opt = ava_opt
+        if corr_trim is not None:
+            ava_opt.trimQuantile, ava_opt.trimFactor, ava_opt.trimFloor, ava_opt.trimMinMatches = corr_trim
         if max_corr_dist is not None:
             ava_opt.max_corr_dist = max_corr_dist
         if render_occlusion is not None:
@@ -186,12 +190,17 @@ class MultiFrameTracker:
 
     def __init__(self, ctx, num_streams, interval=12, frame_icp_iters=3, reinit_icp_iters=6, reinit_cnz=1000, initial_per_part_cnz=0,
                  initial_icp_iters=None, beta_pose=0.1, beta_shape=1.0, max_iters_per_icp=10, enable_occlusion=True,
-                 function_tolerance=1e-4, render_occlusion=None, max_corr_dist=None):
+                 function_tolerance=1e-4, render_occlusion=None, max_corr_dist=None, corr_trim=None):
         """render_occlusion: None (off), or (intrin, (width, height)): self-occlusion visibility from a face-id render with that camera
         (api.Context.set_occlusion_render; not a reference behaviour).  `renderOcclusion` holds it; set_render_occlusion changes it.
         max_corr_dist: None (the context's gate is left as it is), or a distance / numParts distances: the correspondence gate of every
-        stream (api.Context.set_corr_gate; not a reference behaviour).  set_corr_gate changes it; ctx.corr_gate() tells what is in force."""
+        stream (api.Context.set_corr_gate; not a reference behaviour).  set_corr_gate changes it; ctx.corr_gate() tells what is in force.
+        corr_trim: None (the context's trim settings are left as they are), or (quantile, factor, floor, min_matches): trimmed ICP on
+        every stream (api.Context.set_corr_trim; not a reference behaviour).  set_corr_trim changes it; ctx.corr_trim() tells what is
+        in force."""
         self.ctx = ctx
+        if corr_trim is not None:
+            self.set_corr_trim(*corr_trim)
         if max_corr_dist is not None:
             self.set_corr_gate(max_corr_dist)
         self.renderOcclusion = None
@@ -232,6 +241,10 @@ class MultiFrameTracker:
     def set_corr_gate(self, max_corr_dist):
         """None: off; a distance or numParts distances: one gate for all streams.  Takes effect for the following steps."""
         self.ctx.set_corr_gate(max_corr_dist)
+
+    def set_corr_trim(self, quantile=None, factor=1.0, floor=0.0, min_matches=1):
+        """quantile None: off; else one setting for all streams (api.Context.set_corr_trim).  Takes effect for the following steps."""
+        self.ctx.set_corr_trim(quantile, factor, floor, min_matches)
 
     def options(self, icp_iters):
         o = api.Options.reference_defaults()

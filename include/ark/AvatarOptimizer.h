@@ -33,6 +33,7 @@ class AvatarOptimizer {
             ARK_AVT_CHECK(avt_ctx_create(ava.device, ava.model.handle, numParts, partMap.data(), capacity, 1, &ctx));
             occlusionRenderSet = false;
             gateSet.clear();
+            trimSet.clear();
         }
         if (renderOcclusion != occlusionRenderSet) {       // the context follows the member (a new context starts with the mode off)
             ARK_AVT_CHECK(avt_set_occlusion_render(ctx, renderOcclusion ? imageSize.width : 0, imageSize.height, intrin.fx, intrin.fy, intrin.cx, intrin.cy));
@@ -43,6 +44,14 @@ class AvatarOptimizer {
             if (want != gateSet && !(gateSet.empty() && want.size() == 1 && want[0] == std::numeric_limits<double>::infinity())) {
                 ARK_AVT_CHECK(avt_set_corr_gate(ctx, (int)want.size(), want.data()));
                 gateSet = want;
+            }
+        }
+        {   // trimmed ICP: the four members for every part (a new context starts with it off)
+            const std::vector<double> want = {trimQuantile, trimFactor, trimFloor, (double)trimMinMatches};
+            if (want != trimSet && !(trimSet.empty() && trimFactor == std::numeric_limits<double>::infinity())) {
+                if (trimFactor == std::numeric_limits<double>::infinity()) ARK_AVT_CHECK(avt_set_corr_trim(ctx, 0, nullptr, nullptr, nullptr, 1));
+                else ARK_AVT_CHECK(avt_set_corr_trim(ctx, 1, &trimQuantile, &trimFactor, &trimFloor, trimMinMatches));
+                trimSet = want;
             }
         }
         for (int i = 0; i < J; ++i) r[i] = rotationToQuaternion(ava.r[i]);       // :1250-1254
@@ -86,6 +95,13 @@ class AvatarOptimizer {
         return n;
     }
 
+    /** Matches the last search of the last optimize() lost to the trim (avt_get_trimmed) */
+    int lastTrimmed() const {
+        int n = 0;
+        ARK_AVT_CHECK(avt_get_trimmed(ctx, 0, &n, nullptr));
+        return n;
+    }
+
     /** Rotation representation size */
     static const int ROT_SIZE = 4;
     /** Optimization parameter r */
@@ -108,6 +124,14 @@ class AvatarOptimizer {
      *  its part had no visible model point (include/avt.h, avt_set_corr_gate).  +inf (default) = off; no value is offered.  Followed
      *  before every optimize(); setCorrespondenceGate gives per-part values. */
     double maxCorrespondenceDist = std::numeric_limits<double>::infinity();
+    /** NOT members of the reference's class: trimmed ICP (include/avt.h, avt_set_corr_trim).  After every search, per part, a match is
+     *  kept iff its squared distance d2 <= max(trimFactor^2 * t, trimFloor^2), t the ceil(trimQuantile * n)-th smallest d2 of the part's
+     *  n matches in this frame; a part with fewer than trimMinMatches matches is left alone.  trimFactor +inf (default) = off; no value
+     *  is offered.  Followed before every optimize(). */
+    double trimQuantile = 1.0;
+    double trimFactor = std::numeric_limits<double>::infinity();
+    double trimFloor = 0.0;
+    int trimMinMatches = 1;
     /** Not a member of the reference's class: the value its optimize() hard-codes as options.function_tolerance
      *  (AvatarOptimizer.cpp:1333) - a step that lowers the objective by no more than this fraction ends the inner iterations
      *  of the ICP iteration; 0 = always maxItersPerICP iterations (include/avt.h, avt_options::function_tolerance) */
@@ -129,5 +153,6 @@ class AvatarOptimizer {
     bool occlusionRenderSet = false;   // what ctx was last told
     std::vector<double> partGates;     // setCorrespondenceGate (empty: maxCorrespondenceDist for every part)
     std::vector<double> gateSet;       // the gate ctx was last told (empty: never told, i.e. off)
+    std::vector<double> trimSet;       // the trim settings ctx was last told (empty: never told, i.e. off)
 };
 }  // namespace ark

@@ -56,6 +56,7 @@ class FrameTracker {
         }
         if (renderOcclusion >= 0) avaOpt.renderOcclusion = renderOcclusion != 0;
         if (maxCorrespondenceDist >= 0) avaOpt.maxCorrespondenceDist = maxCorrespondenceDist;
+        if (trimFactor >= 0) { avaOpt.trimQuantile = trimQuantile; avaOpt.trimFactor = trimFactor; avaOpt.trimFloor = trimFloor; avaOpt.trimMinMatches = trimMinMatches; }
         avaOpt.optimize(dataCloud, dataPartLabels, icpIters, numThreads);
         ++framesFitted;
         return true;
@@ -79,6 +80,10 @@ class FrameTracker {
     /** not a reference member: a value >= 0 (+inf = off) sets avaOpt.maxCorrespondenceDist before every fit (the correspondence gate,
      *  include/avt.h avt_set_corr_gate); negative (default) leaves the optimizer's member alone */
     double maxCorrespondenceDist = -1.0;
+    /** not reference members: a trimFactor >= 0 (+inf = off) sets avaOpt.trimQuantile / trimFactor / trimFloor / trimMinMatches before
+     *  every fit (trimmed ICP, include/avt.h avt_set_corr_trim); negative (default) leaves the optimizer's members alone */
+    double trimQuantile = 1.0, trimFactor = -1.0, trimFloor = 0.0;
+    int trimMinMatches = 1;
 
     AvatarOptimizer& avaOpt;
     Avatar& ava;

@@ -78,6 +78,18 @@ class MultiFrameTracker {
         ARK_AVT_CHECK(avt_set_corr_gate(ctx, (int)gates.size(), gates.data()));
         correspondenceGate = gates;
     }
+    /** Not a reference behaviour: trimmed ICP on every stream (include/avt.h, avt_set_corr_trim), every part alike; a factor of +inf
+     *  turns it off.  Takes effect for the following steps. */
+    void setCorrespondenceTrim(double quantile, double factor, double floor_dist = 0.0, int min_matches = 1) {
+        if (factor == std::numeric_limits<double>::infinity()) ARK_AVT_CHECK(avt_set_corr_trim(ctx, 0, nullptr, nullptr, nullptr, 1));
+        else ARK_AVT_CHECK(avt_set_corr_trim(ctx, 1, &quantile, &factor, &floor_dist, min_matches));
+    }
+    /** matches the last search of the last step lost to the trim on stream s (avt_get_trimmed) */
+    int lastTrimmed(int s) const {
+        int n = 0;
+        ARK_AVT_CHECK(avt_get_trimmed(ctx, s, &n, nullptr));
+        return n;
+    }
     /** queries the last search of the last step dropped at the gate on stream s (avt_get_gated) */
     int lastGated(int s) const {
         int n = 0;

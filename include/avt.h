@@ -205,6 +205,32 @@ int avt_set_corr_gate(avt_ctx* c, int n, const double* max_dist);
 int avt_get_corr_gate(avt_ctx* c, double* max_dist_num_parts);
 int avt_get_gated(avt_ctx* c, int frame, int* gated);
 
+/* ---- trimmed ICP: a gate per part from the frame's own match distances (NOT a reference behaviour, and there is no reference
+ * interface: findNN keeps every nearest visible model point; decided here).  The context holds per part q a
+ * quantile rho[q] in (0, 1], a factor kappa[q] >= 0 (finite, or +inf: the part is not trimmed - the default) and a floor floor[q] >= 0
+ * in metres, and one min_matches >= 1.  On the host k2 = kappa * kappa and f2 = floor * floor, one double multiplication each.  After
+ * every search the context runs - each ICP iteration of avt_optimize*, the resident and budget calls, the stand-alone avt_nn - and
+ * after the fixed gate above, per frame and per part with a finite kappa: n = the part's queries that hold a match; n == 0 or
+ * n < min_matches: nothing is dropped and the threshold is +inf.  Else k = (int)ceil(rho * (double)n) clamped to [1, n], t = the k-th
+ * smallest (1-based) squared distance of those matches - the search's own expression r = d0*d0; r += d1*d1; r += d2*d2, each operation
+ * rounded, ordered by the 64-bit pattern -, T = max(k2 * t, f2), and a match is kept iff d2 <= T.  A trimmed query is, like a gated
+ * one, a query whose part has no visible model point: -1 in the correspondences, taken back exactly from the integer counts and sums,
+ * not in avt_stats::num_correspondences nor in the rescaling of the priors; queries with a valid label and a non-empty visible part ==
+ * num_correspondences + gated + trimmed.  With every factor +inf nothing is launched and results are bit for bit those without the
+ * call.
+ * avt_set_corr_trim: n == 0 or NULL arrays: off; n == 1: every part alike; n == num_parts: per part.  Refused, the previous setting
+ * staying in force: any other n, a NaN, a quantile outside (0, 1], a negative factor or floor, a finite factor whose square is not
+ * finite, a floor that is not finite, min_matches < 1.  The values live in device memory and are not part of the launch shape; only
+ * on / off is.  No value is offered and nothing sets trimming by default.
+ * avt_get_corr_trim: the settings in force, num_parts values each (any pointer may be NULL); a part that is off reads factor +inf.
+ * avt_get_trimmed: matches `frame`'s last search lost to the trim, in total and (per_part not NULL) per part; avt_get_trim_thresholds:
+ * the num_parts thresholds T that search used (+inf where it could drop nothing).  Both are valid where avt_get_gated is and refused
+ * otherwise; after a search that ran with trimming off they read 0 and +inf. */
+int avt_set_corr_trim(avt_ctx* c, int n, const double* quantile, const double* factor, const double* floor_dist, int min_matches);
+int avt_get_corr_trim(avt_ctx* c, double* quantile_np, double* factor_np, double* floor_np, int* min_matches);
+int avt_get_trimmed(avt_ctx* c, int frame, int* total, int* per_part_or_NULL);
+int avt_get_trim_thresholds(avt_ctx* c, int frame, double* T_num_parts);
+
 /* ---- AvatarOptimizer::optimize() (AvatarOptimizer.cpp:1246-1517), one frame.
  * In/out: p (3), q (4 x J, xyzw), w (K).  The caller converts ava.r <-> q (AvatarOptimizer.cpp:1250-1254,
  * :1494-1496; done by the C++ facade).  stats may be NULL. */
