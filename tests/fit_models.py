@@ -133,8 +133,9 @@ def _quats(rng, J, s):
     return q
 
 
-def fit_model(J, K, tree, ncomps=0, seed=0):
-    key = (J, K, tree, ncomps, seed)
+def fit_model(J, K, tree, ncomps=0, seed=0, per_joint=PER_JOINT):
+    """per_joint: vertices per joint (the table's rows keep PER_JOINT; tests/data_term_cases.py asks for more)"""
+    key = (J, K, tree, ncomps, seed) if per_joint == PER_JOINT else (J, K, tree, ncomps, seed, per_joint)
     if key in _CACHE:
         return _CACHE[key]
     rng = np.random.default_rng([20261019, J, K, seed])
@@ -143,12 +144,12 @@ def fit_model(J, K, tree, ncomps=0, seed=0):
     for j in range(1, J):
         d = rng.standard_normal(3)
         jpos[j] = jpos[parent[j]] + 0.25 * d / np.linalg.norm(d)
-    V = PER_JOINT * J
+    V = per_joint * J
     vt = np.zeros((V, 3))
     rows, cols, vals = [], [], []
     for j in range(J):
-        for i in range(PER_JOINT):
-            v = j * PER_JOINT + i
+        for i in range(per_joint):
+            v = j * per_joint + i
             vt[v] = jpos[j] + 0.12 * rng.standard_normal(3)
             if parent[j] >= 0 and i % 3 == 0:           # shared with the parent
                 a = rng.uniform(0.6, 0.9)
@@ -158,7 +159,7 @@ def fit_model(J, K, tree, ncomps=0, seed=0):
     W = sp.csr_matrix((np.array(vals), (np.array(rows), np.array(cols))), shape=(V, J))
     Jr = np.zeros((J, V))
     for j in range(J):
-        Jr[j, j * PER_JOINT:(j + 1) * PER_JOINT] = 1.0 / PER_JOINT
+        Jr[j, j * per_joint:(j + 1) * per_joint] = 1.0 / per_joint
     faces = rng.integers(0, V, (max(1, V // 2), 3))      # unused: the fits run with enable_occlusion = 0
     m = dict(v_template=vt, f=faces, kintree_table=np.stack([parent, np.arange(J)]), J_regressor=Jr, weights=W,
              shapedirs=rng.normal(0.0, 0.02, (V, 3, K)))
@@ -273,12 +274,12 @@ def lambda_conditioning(case):
     return r["lam"], r["kappa"]
 
 
-def replay_fit(om, fr):
-    """lambda_conditioning's replay for any frame fr of om's model: dict(lam, kappa, acc (1 accepted / 0 rejected / -1 not factorable, per GN
+def replay_fit(om, fr, max_iters_per_icp=4):
+    """lambda_conditioning's replay for any frame fr of om's model (2 ICP x max_iters_per_icp GN iterations): dict(lam, kappa, acc (1 accepted / 0 rejected / -1 not factorable, per GN
     iteration), states (the start and the state behind every accepted step), icp_states (the state each ICP iteration's correspondences are
     searched at), comps ((minimising mixture component at the current point, at the trial point) per factorable GN iteration; -1 without a prior))."""
     bp, bs = fr["betas"]
-    opt = options(fr, icp_iters=2, max_iters_per_icp=4)
+    opt = options(fr, icp_iters=2, max_iters_per_icp=max_iters_per_icp)
     p, q, w = (np.array(x, np.float64) for x in fr["start"])
     lam, nu, kappa = opt.lm_lambda0, opt.lm_up, 0.0
     acc, states, icp_states, comps = [], [(p, q, w)], [], []
