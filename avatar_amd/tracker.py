@@ -456,6 +456,29 @@ class MultiFrameTracker:
         r = render.render_streams(self, streams, size, intrin, render.DEPTH | render.PART_MASK, part_map, download=False)
         return sc.score_rendered_from_bgsub(r, self.bgsub, streams, fitscore.DEFAULT_TOL if tol is None else tol, stride)
 
+    def pose_error(self, streams, truth_clouds, truth_joints, part_map=None):
+        """How far the last fit of the given streams is from the truth (avatar_amd.poseerror: PVE, MPJPE and the Procrustes-aligned
+        forms, in metres): the estimate side is read from the context on the device, the truth side is given, truth_clouds
+        (len(streams), V, 3) and truth_joints (len(streams), J, 3).  Parts are numParts parts over the main joints through
+        `part_map` (None: the joint itself, which needs numParts >= J).  Returns what poseerror.PoseError.get returns, with the
+        figures of poseerror.metrics under "metrics".  Nothing calls this by default and no threshold is offered."""
+        from . import poseerror
+        if not self.state_resident:
+            raise RuntimeError("MultiFrameTracker.pose_error: no stream has been fitted yet")
+        streams = [int(s) for s in streams]
+        key = None if part_map is None else tuple(int(x) for x in part_map)
+        pe = getattr(self, "_pose_scorer", None)
+        if pe is None or pe.max_pairs < len(streams) or self._pose_scorer_key != key:
+            pe = self._pose_scorer = poseerror.PoseError.for_model(self.ctx.model, self.numParts, part_map, max(self.S, len(streams)),
+                                                                   getattr(self.ctx, "device", 0))
+            self._pose_scorer_key = key
+        pe.from_context(poseerror.ESTIMATE, self.ctx, streams)
+        pe.upload(poseerror.TRUTH, truth_clouds, truth_joints)
+        pe.run()
+        out = pe.get()
+        out["metrics"] = pe.metrics(out)
+        return out
+
     def rotations(self, stream):
         """The stream's joint rotations (J,3,3), as FrameTracker's Avatar.r holds them."""
         return api.quat_to_rot(self.q[stream])

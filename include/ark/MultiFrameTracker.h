@@ -27,6 +27,7 @@
 #include "AvatarOptimizer.h"
 #include "BGSubtractor.h"
 #include "FitScore.h"
+#include "PoseError.h"
 #include "RForest.h"
 #include "RTree.h"
 #include "TrackerPolicy.h"
@@ -53,8 +54,10 @@ class MultiFrameTracker {
         for (int s = 0; s < S; ++s) for (int j = 0; j < J; ++j) q[((size_t)s * J + j) * 4 + 3] = 1.0;
         ARK_AVT_CHECK(avt_ctx_create(device, model.handle, num_parts, part_map.data(), max_points_per_frame, num_streams, &ctx));
         device_ = device;
+        partMap_ = part_map;
     }
     ~MultiFrameTracker() {
+        delete poseScorer;
         delete scorer;
         avt_renderer_destroy(rend);
         if (ctx) avt_ctx_destroy(ctx);
@@ -391,6 +394,23 @@ class MultiFrameTracker {
         return scorer->scoreRenderedFromBGSub(rend, frontBG->handle(), stream_ids, tol, stride);
     }
 
+    /** How far the last fit of the given streams is from the truth (ark/PoseError.h: PVE, MPJPE and the Procrustes-aligned
+     *  forms): the estimate side is read from the context on the device, the truth side is given, one cloud (3 x V) and one set
+     *  of joints (3 x J) per stream of stream_ids, back to back.  Parts are the tracker's own (its part map over the main joints).
+     *  One PoseErrorResult per stream; derive() gives the figures.  Nothing calls this by default and no threshold is offered. */
+    std::vector<PoseErrorResult> poseError(const std::vector<int>& stream_ids, const std::vector<double>& truth_clouds, const std::vector<double>& truth_joints) {
+        const size_t n = stream_ids.size();
+        if (n == 0 || truth_clouds.size() != n * 3 * (size_t)model.numPoints() || truth_joints.size() != n * 3 * (size_t)J || !stateResident) {
+            std::fprintf(stderr, "MultiFrameTracker::poseError: needs a fitted step and one truth cloud (3 x V) and joint set (3 x J) per stream\n");
+            std::exit(1);
+        }
+        if (!poseScorer) poseScorer = new PoseError(model.handle, numParts, partMap_, S, device_);
+        poseScorer->fromContext(AVT_POSEERR_ESTIMATE, ctx, (int)n, stream_ids);
+        poseScorer->upload(AVT_POSEERR_TRUTH, (int)n, truth_clouds.data(), truth_joints.data());
+        poseScorer->run();
+        return poseScorer->get();
+    }
+
     const double* pos(int s) const { return &p[3 * (size_t)s]; }
     const double* shape(int s) const { return &w[(size_t)K * s]; }
     const double* quats(int s) const { return &q[4 * (size_t)J * s]; }           // J quaternions (x, y, z, w)
@@ -436,6 +456,8 @@ class MultiFrameTracker {
     int rendW = 0, rendH = 0;
     CameraIntrin rendIntrin;
     FitScorer* scorer = nullptr;                   // fitScore(): created on first use
+    PoseError* poseScorer = nullptr;               // poseError(): created on first use
+    std::vector<int> partMap_;
     bool stateResident = false;
     std::vector<CloudType> clouds;
     std::vector<VectorXi> labels;
