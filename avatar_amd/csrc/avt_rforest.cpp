@@ -1,33 +1,25 @@
 // avt_rforest.cpp — host side of the forest of several trees (include/avt_rforest.h): validation of the members against each
-// other, the packed device image (one node array with rebased links, one leaf table), image staging and the resident forms,
-// argument for argument what avt_rtree.cpp does for one tree.
+// other, the packed device image (one node array with rebased links, one leaf table) and the score.  Image staging and the
+// resident forms are the labelling handle's (avt_label.cpp), as for one tree.
 #include "avt_rforest.h"
 
 #include <algorithm>
 #include <string>
 
-#include "avt_bgsub_internal.h"
 #include "avt_internal.h"
 #include "avt_rtree_train.h"
 
 namespace {
 
-const char* const kHostOnly = "rforest: created host-only (device < 0): inference needs a GPU";
+const AvtLabelNames kForest = {"rforest", "avt_rforest", "forest"};
+const char* const kHostOnly = "rforest: created host-only (device < 0): inference needs a GPU";      // the score's own checks
+const int kMaxImages = 65535;     // blockIdx.z is the image
 
-int roi_ok(int rows, int cols, int interval, int& tlx, int& tly, int& brx, int& bry) {
-    if (brx == -1) { brx = cols - 1; bry = rows - 1; }
-    if (rows <= 0 || cols <= 0 || interval <= 0 || tlx < 0 || tly < 0 || brx >= cols || bry >= rows || tlx > brx || tly > bry || rows >= 32768 ||
-        cols >= 32768) {
-        avt_set_error("rforest: bad image size, interval or region of interest");
-        return 1;
-    }
-    return 0;
+// the launches behind the shared image side (avt_label.cpp)
+int launch_boxes(AvtLabelHandle* h, const float* d_depth, const int* d_boxes, int box_stride, int n_images, int rows, int cols, int interval, int fill) {
+    return avt_rforest_launch_predict(static_cast<avt_rforest*>(h), d_depth, d_boxes, box_stride, n_images, rows, cols, interval, 0, 0, 0, 0, fill);
 }
-
-int batch_ok(int n_images) {      // blockIdx.z is the image
-    if (n_images > 65535) { avt_set_error("rforest: at most 65535 images per call"); return 1; }
-    return 0;
-}
+int launch_dist(AvtLabelHandle* h, int rows, int cols, float* d_out) { return avt_rforest_launch_predict_dist(static_cast<avt_rforest*>(h), rows, cols, d_out); }
 
 // every tree's nodes behind each other, links rebased; a leaf's rnode is its row in the forest's one table
 int pack(avt_rforest* rf, const avt_rtree* const* trees) {
@@ -63,13 +55,6 @@ int upload_forest(avt_rforest* rf) {
     return 0;
 }
 
-int reserve_images(avt_rforest* rf, size_t pixels) {
-    if (rf->device < 0) { avt_set_error(kHostOnly); return 1; }
-    if (pixels <= rf->d_depth.cap && pixels <= rf->d_labels.cap) return 0;
-    AVT_HIP(hipSetDevice(rf->device));
-    return rf->d_depth.reserve(pixels) || rf->d_labels.reserve(pixels);
-}
-
 int create_impl(const avt_rtree* const* trees, int n_trees, int device, avt_rforest** out) {
     if (!trees || !out) { avt_set_error("avt_rforest_create: null argument"); return 1; }
     if (n_trees < 1 || n_trees > AVT_RFOREST_MAX_TREES) {
@@ -97,104 +82,16 @@ int create_impl(const avt_rtree* const* trees, int n_trees, int device, avt_rfor
     return 0;
 }
 
-int images_upload_impl(avt_rforest* rf, int n_images, int rows, int cols, const float* depth) {
-    if (!rf || !depth || n_images <= 0 || rows <= 0 || cols <= 0) { avt_set_error("avt_rforest_images_upload: bad arguments"); return 1; }
-    if (batch_ok(n_images)) return 1;
-    const size_t pixels = (size_t)n_images * rows * cols;
-    if (reserve_images(rf, pixels)) return 1;
-    AVT_HIP(hipSetDevice(rf->device));
-    AVT_HIP(hipMemcpyAsync(rf->d_depth, depth, pixels * sizeof(float), hipMemcpyHostToDevice, rf->stream));
-    rf->n_images = rf->n_labels = n_images; rf->rows = rows; rf->cols = cols;
-    return 0;
-}
-
-int labels_download_impl(avt_rforest* rf, int image, unsigned char* out) {
-    if (!rf || !out || image < 0 || image >= rf->n_labels) { avt_set_error("avt_rforest_labels_download: bad arguments"); return 1; }
-    const size_t px = (size_t)rf->rows * rf->cols;
-    AVT_HIP(hipMemcpyAsync(out, rf->d_labels + px * image, px, hipMemcpyDeviceToHost, rf->stream));
-    AVT_HIP(hipStreamSynchronize(rf->stream));
-    return 0;
-}
-
-int labels_download_all_impl(avt_rforest* rf, unsigned char* out) {
-    if (!rf || !out || rf->n_labels <= 0) { avt_set_error("avt_rforest_labels_download_all: bad arguments or no labelled images"); return 1; }
-    AVT_HIP(hipMemcpyAsync(out, rf->d_labels, (size_t)rf->n_labels * rf->rows * rf->cols, hipMemcpyDeviceToHost, rf->stream));
-    AVT_HIP(hipStreamSynchronize(rf->stream));
-    return 0;
-}
-
 int predict_best_impl(avt_rforest* rf, const float* depth, int rows, int cols, int interval, int tlx, int tly, int brx, int bry, int fill,
                       unsigned char* labels_out) {
     if (!rf || !depth || !labels_out) { avt_set_error("avt_rforest_predict_best: null argument"); return 1; }
-    if (roi_ok(rows, cols, interval, tlx, tly, brx, bry)) return 1;
-    if (images_upload_impl(rf, 1, rows, cols, depth)) return 1;
+    if (avt_label_roi_ok(kForest, rows, cols, interval, tlx, tly, brx, bry)) return 1;
+    if (avt_label_images_upload(rf, kForest, kMaxImages, 1, rows, cols, depth)) return 1;
     if (avt_rforest_launch_predict(rf, rf->d_depth, nullptr, 0, 1, rows, cols, interval, tlx, tly, brx, bry, fill)) {
         avt_set_error("rforest: kernel launch failed");
         return 1;
     }
-    return labels_download_impl(rf, 0, labels_out);
-}
-
-int predict_impl(avt_rforest* rf, const float* depth, int rows, int cols, float* dist_out) {
-    if (!rf || !depth || !dist_out || rows <= 0 || cols <= 0) { avt_set_error("avt_rforest_predict: bad arguments"); return 1; }
-    if (rows >= 32768 || cols >= 32768) { avt_set_error("rforest: bad image size, interval or region of interest"); return 1; }
-    if (images_upload_impl(rf, 1, rows, cols, depth)) return 1;
-    const size_t n = (size_t)rf->num_parts * rows * cols;
-    DevBuf<float> d_out;
-    if (d_out.reserve(n)) return 1;
-    int rc = avt_rforest_launch_predict_dist(rf, rows, cols, d_out);
-    if (rc) avt_set_error("rforest: kernel launch failed");
-    if (!rc && hipMemcpyAsync(dist_out, d_out, n * sizeof(float), hipMemcpyDeviceToHost, rf->stream) != hipSuccess) { avt_set_error("rforest: download failed"); rc = 1; }
-    if (hipStreamSynchronize(rf->stream) != hipSuccess && !rc) { avt_set_error("rforest: stream failed"); rc = 1; }   // on every path, before d_out goes
-    return rc;
-}
-
-int predict_best_resident_boxes_impl(avt_rforest* rf, int interval, const int* boxes, int fill) {
-    if (!rf || !boxes) { avt_set_error("avt_rforest_predict_best_resident_boxes: null argument"); return 1; }
-    if (rf->device < 0) { avt_set_error(kHostOnly); return 1; }
-    if (rf->n_images <= 0) { avt_set_error("avt_rforest_predict_best_resident_boxes: no images resident"); return 1; }
-    const int n = rf->n_images, rows = rf->rows, cols = rf->cols;
-    // everything is checked before anything is queued: after a failure the labels of the previous call are still there
-    std::vector<int> b(boxes, boxes + 4 * (size_t)n);
-    for (int i = 0; i < n; ++i) {
-        int* q = &b[4 * (size_t)i];
-        if (q[2] == -1) { q[2] = cols - 1; q[3] = rows - 1; }
-        if (q[0] > q[2] || q[1] > q[3]) continue;          // an empty box: that image stays 255 (a lost stream does not fail the batch)
-        if (roi_ok(rows, cols, interval, q[0], q[1], q[2], q[3])) return 1;
-    }
-    int tlx = 0, tly = 0, brx = -1, bry = -1;
-    if (roi_ok(rows, cols, interval, tlx, tly, brx, bry)) return 1;     // the interval and the image size, when every box is empty
-    AVT_HIP(hipSetDevice(rf->device));
-    if (rf->d_boxes.reserve(4 * (size_t)n)) return 1;
-    AVT_HIP(hipMemcpyAsync(rf->d_boxes, b.data(), b.size() * sizeof(int), hipMemcpyHostToDevice, rf->stream));
-    AVT_HIP(hipStreamSynchronize(rf->stream));             // `b` is on this stack frame
-    if (avt_rforest_launch_predict(rf, rf->d_depth, rf->d_boxes, 4, n, rows, cols, interval, 0, 0, 0, 0, fill)) {
-        avt_set_error("rforest: kernel launch failed");
-        return 1;
-    }
-    return 0;
-}
-
-int predict_best_from_bgsub_impl(avt_rforest* rf, avt_bgsub* bg, int interval, int fill) {
-    if (!rf) { avt_set_error("avt_rforest_predict_best_from_bgsub: null forest"); return 1; }
-    if (rf->device < 0) { avt_set_error(kHostOnly); return 1; }
-    if (!bg) { avt_set_error("avt_rforest_predict_best_from_bgsub: null background subtractor"); return 1; }
-    avt_bgsub_view v;
-    if (avt_bgsub_last_run(bg, &v)) return 1;
-    if (v.device != rf->device) { avt_set_error("avt_rforest_predict_best_from_bgsub: the forest and the background subtractor are on different devices"); return 1; }
-    int tlx = 0, tly = 0, brx = -1, bry = -1;
-    if (roi_ok(v.rows, v.cols, interval, tlx, tly, brx, bry) || batch_ok(v.n_images)) return 1;
-    AVT_HIP(hipSetDevice(rf->device));
-    const size_t pixels = (size_t)v.n_images * v.rows * v.cols;
-    if (rf->d_labels.reserve(pixels)) return 1;
-    // the labels are these images' from here on, and the forest has no resident depth of its own until the next images_upload
-    rf->n_images = 0; rf->n_labels = v.n_images; rf->rows = v.rows; rf->cols = v.cols;
-    // the forest's stream waits for the run; bg's next upload / run / destroy waits for the labelling.  No copy, no host wait.
-    if (avt_bgsub_reader_begin(bg, rf->stream)) return 1;
-    const int rc = avt_rforest_launch_predict(rf, v.d_depth, v.d_boxes, v.box_stride, v.n_images, v.rows, v.cols, interval, 0, 0, 0, 0, fill);
-    if (avt_bgsub_reader_end(bg, rf->stream)) return 1;    // also after a failed launch: the memset may be queued
-    if (rc) { avt_set_error("rforest: kernel launch failed"); return 1; }
-    return 0;
+    return avt_label_labels_download(rf, kForest, 0, labels_out);
 }
 
 // ---- the score (include/avt_rforest.h): a call counts into the scratch matrix and is committed only when no label was refused
@@ -304,9 +201,7 @@ int avt_rforest_create(const avt_rtree* const* trees, int n_trees, int device, a
 
 void avt_rforest_destroy(avt_rforest* rf) {
     if (!rf) return;
-    // the buffers go with `delete`, after the stream: it is drained first, so nothing is queued on them either way
-    if (rf->stream) (void)hipStreamSynchronize(rf->stream);
-    if (rf->stream) (void)hipStreamDestroy(rf->stream);
+    avt_label_teardown(rf);
     delete rf;
 }
 
@@ -322,7 +217,7 @@ int avt_rforest_info(const avt_rforest* rf, int* n_trees, int* num_parts, int* p
 }
 
 int avt_rforest_predict(avt_rforest* rf, const float* depth, int rows, int cols, float* dist_out) {
-    return avt_guard("avt_rforest_predict", [&]() -> int { return predict_impl(rf, depth, rows, cols, dist_out); });
+    return avt_guard("avt_rforest_predict", [&]() -> int { return avt_label_predict_dist(rf, kForest, true, depth, rows, cols, dist_out, launch_dist); });
 }
 
 int avt_rforest_predict_best(avt_rforest* rf, const float* depth, int rows, int cols, int interval, int tlx, int tly, int brx, int bry, int fill,
@@ -331,31 +226,26 @@ int avt_rforest_predict_best(avt_rforest* rf, const float* depth, int rows, int 
 }
 
 int avt_rforest_images_upload(avt_rforest* rf, int n_images, int rows, int cols, const float* depth) {
-    return avt_guard("avt_rforest_images_upload", [&]() -> int { return images_upload_impl(rf, n_images, rows, cols, depth); });
+    return avt_guard("avt_rforest_images_upload", [&]() -> int { return avt_label_images_upload(rf, kForest, kMaxImages, n_images, rows, cols, depth); });
 }
 
 int avt_rforest_predict_best_resident_boxes(avt_rforest* rf, int interval, const int* boxes, int fill) {
-    return avt_guard("avt_rforest_predict_best_resident_boxes", [&]() -> int { return predict_best_resident_boxes_impl(rf, interval, boxes, fill); });
+    return avt_guard("avt_rforest_predict_best_resident_boxes", [&]() -> int { return avt_label_predict_resident_boxes(rf, kForest, interval, boxes, fill, launch_boxes); });
 }
 
 int avt_rforest_predict_best_from_bgsub(avt_rforest* rf, avt_bgsub* bg, int interval, int fill) {
-    return avt_guard("avt_rforest_predict_best_from_bgsub", [&]() -> int { return predict_best_from_bgsub_impl(rf, bg, interval, fill); });
+    return avt_guard("avt_rforest_predict_best_from_bgsub", [&]() -> int { return avt_label_predict_from_bgsub(rf, kForest, kMaxImages, bg, interval, fill, launch_boxes); });
 }
 
 int avt_rforest_labels_download(avt_rforest* rf, int image, unsigned char* labels_out) {
-    return avt_guard("avt_rforest_labels_download", [&]() -> int { return labels_download_impl(rf, image, labels_out); });
+    return avt_guard("avt_rforest_labels_download", [&]() -> int { return avt_label_labels_download(rf, kForest, image, labels_out); });
 }
 
 int avt_rforest_labels_download_all(avt_rforest* rf, unsigned char* labels_out) {
-    return avt_guard("avt_rforest_labels_download_all", [&]() -> int { return labels_download_all_impl(rf, labels_out); });
+    return avt_guard("avt_rforest_labels_download_all", [&]() -> int { return avt_label_labels_download_all(rf, kForest, labels_out); });
 }
 
-int avt_rforest_sync(avt_rforest* rf) {
-    if (!rf) { avt_set_error("avt_rforest_sync: null forest"); return 1; }
-    if (rf->device < 0) { avt_set_error(kHostOnly); return 1; }
-    AVT_HIP(hipStreamSynchronize(rf->stream));
-    return 0;
-}
+int avt_rforest_sync(avt_rforest* rf) { return avt_label_sync(rf, kForest, true); }      // refuses a host-only forest
 
 int avt_rforest_labels_upload(avt_rforest* rf, int n_images, int rows, int cols, const unsigned char* labels) {
     return avt_guard("avt_rforest_labels_upload", [&]() -> int { return avt_post_labels_upload(rf, "avt_rforest_labels_upload", n_images, rows, cols, labels); });
@@ -370,19 +260,11 @@ int avt_rforest_post_process_from_bgsub(avt_rforest* rf, avt_bgsub* bg, int inte
 }
 
 int avt_rforest_com_pre_set(avt_rforest* rf, int first, int n, const double* com, const unsigned char* valid) {
-    return avt_guard("avt_rforest_com_pre_set", [&]() -> int {
-        if (!rf || rf->device < 0) { avt_set_error("avt_rforest_com_pre_set: null or host-only forest"); return 1; }
-        AVT_HIP(hipSetDevice(rf->device));
-        return avt_post_com_set(&rf->post, rf->stream, rf->num_parts, first, n, com, valid);
-    });
+    return avt_guard("avt_rforest_com_pre_set", [&]() -> int { return avt_label_com_pre_set(rf, kForest, first, n, com, valid); });
 }
 
 int avt_rforest_com_pre_get(avt_rforest* rf, int first, int n, double* com, unsigned char* valid) {
-    return avt_guard("avt_rforest_com_pre_get", [&]() -> int {
-        if (!rf || rf->device < 0) { avt_set_error("avt_rforest_com_pre_get: null or host-only forest"); return 1; }
-        AVT_HIP(hipSetDevice(rf->device));
-        return avt_post_com_get(&rf->post, rf->stream, rf->num_parts, first, n, com, valid);
-    });
+    return avt_guard("avt_rforest_com_pre_get", [&]() -> int { return avt_label_com_pre_get(rf, kForest, first, n, com, valid); });
 }
 
 int avt_rforest_score_reset(avt_rforest* rf) {

@@ -10,10 +10,16 @@
 #include <limits>
 #include <map>
 
-#include "avt_bgsub_internal.h"
 #include "avt_internal.h"
 
 namespace {
+
+const AvtLabelNames kTree = {"rtree", "avt_rtree", "tree"};
+// the launches behind the shared image side (avt_label.cpp)
+int launch_boxes(AvtLabelHandle* h, const float* d_depth, const int* d_boxes, int box_stride, int n_images, int rows, int cols, int interval, int fill) {
+    return avt_rtree_launch_predict_boxes(static_cast<avt_rtree*>(h), d_depth, d_boxes, box_stride, n_images, rows, cols, interval, fill);
+}
+int launch_dist(AvtLabelHandle* h, int rows, int cols, float* d_out) { return avt_rtree_launch_predict_dist(static_cast<avt_rtree*>(h), rows, cols, d_out); }
 
 template <class T> bool get(std::istream& is, T& v) { is.read(reinterpret_cast<char*>(&v), sizeof(T)); return (bool)is; }
 template <class T> void put(std::ostream& os, T v) { os.write(reinterpret_cast<char*>(&v), sizeof(T)); }
@@ -72,13 +78,6 @@ int upload_tree(avt_rtree* rt) {
     return 0;
 }
 
-int reserve_images(avt_rtree* rt, size_t pixels) {
-    if (rt->device < 0) { avt_set_error("rtree: created host-only (device < 0): inference needs a GPU"); return 1; }
-    if (pixels <= rt->d_depth.cap && pixels <= rt->d_labels.cap) return 0;   // each on its own: a failed allocation leaves that buffer empty
-    AVT_HIP(hipSetDevice(rt->device));
-    return rt->d_depth.reserve(pixels) || rt->d_labels.reserve(pixels);
-}
-
 bool parse_part_map(std::istream& is, std::vector<int>& result, int& type) {   // RTree::readPartMap, RTree.cpp:3465-3509
     std::string tok;
     if (!(is >> tok) || tok != "partmap") return false;
@@ -99,16 +98,6 @@ bool parse_part_map(std::istream& is, std::vector<int>& result, int& type) {   /
         result[src[a]] = dst[b];
     }
     return true;
-}
-
-int roi_ok(int rows, int cols, int interval, int& tlx, int& tly, int& brx, int& bry) {
-    if (brx == -1) { brx = cols - 1; bry = rows - 1; }
-    if (rows <= 0 || cols <= 0 || interval <= 0 || tlx < 0 || tly < 0 || brx >= cols || bry >= rows || tlx > brx || tly > bry || rows >= 32768 ||
-        cols >= 32768) {
-        avt_set_error("rtree: bad image size, interval or region of interest");
-        return 1;
-    }
-    return 0;
 }
 
 // ---- post-processing (host, sequential: the scan order defines which component wins) -----------------------------
@@ -297,9 +286,7 @@ static int avt_rtree_export_impl(const avt_rtree* rt, const char* path) {
 
 void avt_rtree_destroy(avt_rtree* rt) {
     if (!rt) return;
-    // the buffers go with `delete`, after the stream: it is drained first, so nothing is queued on them either way
-    if (rt->stream) (void)hipStreamSynchronize(rt->stream);
-    if (rt->stream) (void)hipStreamDestroy(rt->stream);
+    avt_label_teardown(rt);
     delete rt;
 }
 
@@ -323,118 +310,27 @@ int avt_rtree_get(const avt_rtree* rt, float* feature, int* links, float* leaf_d
     return 0;
 }
 
-static int avt_rtree_images_upload_impl(avt_rtree* rt, int n_images, int rows, int cols, const float* depth) {
-    if (!rt || !depth || n_images <= 0 || rows <= 0 || cols <= 0) { avt_set_error("avt_rtree_images_upload: bad arguments"); return 1; }
-    const size_t pixels = (size_t)n_images * rows * cols;
-    if (reserve_images(rt, pixels)) return 1;
-    AVT_HIP(hipSetDevice(rt->device));
-    AVT_HIP(hipMemcpyAsync(rt->d_depth, depth, pixels * sizeof(float), hipMemcpyHostToDevice, rt->stream));
-    rt->n_images = rt->n_labels = n_images; rt->rows = rows; rt->cols = cols;
-    return 0;
-}
-
 int avt_rtree_predict_best_resident(avt_rtree* rt, int interval, int tlx, int tly, int brx, int bry, int fill) {
     if (!rt || rt->n_images <= 0) { avt_set_error("avt_rtree_predict_best_resident: no images resident"); return 1; }
-    if (roi_ok(rt->rows, rt->cols, interval, tlx, tly, brx, bry)) return 1;
+    if (avt_label_roi_ok(kTree, rt->rows, rt->cols, interval, tlx, tly, brx, bry)) return 1;
     AVT_HIP(hipSetDevice(rt->device));
     if (avt_rtree_launch_predict(rt, rt->n_images, rt->rows, rt->cols, interval, tlx, tly, brx, bry, fill)) { avt_set_error("rtree: kernel launch failed"); return 1; }
-    return 0;
-}
-
-static const char* const kHostOnly = "rtree: created host-only (device < 0): inference needs a GPU";
-
-static int predict_best_resident_boxes_impl(avt_rtree* rt, int interval, const int* boxes, int fill) {
-    if (!rt || !boxes) { avt_set_error("avt_rtree_predict_best_resident_boxes: null argument"); return 1; }
-    if (rt->device < 0) { avt_set_error(kHostOnly); return 1; }
-    if (rt->n_images <= 0) { avt_set_error("avt_rtree_predict_best_resident_boxes: no images resident"); return 1; }
-    const int n = rt->n_images, rows = rt->rows, cols = rt->cols;
-    // everything is checked before anything is queued: after a failure the labels of the previous call are still there
-    std::vector<int> b(boxes, boxes + 4 * (size_t)n);
-    for (int i = 0; i < n; ++i) {
-        int* q = &b[4 * (size_t)i];
-        if (q[2] == -1) { q[2] = cols - 1; q[3] = rows - 1; }
-        if (q[0] > q[2] || q[1] > q[3]) continue;          // an empty box: that image stays 255 (a lost stream does not fail the batch)
-        if (roi_ok(rows, cols, interval, q[0], q[1], q[2], q[3])) return 1;
-    }
-    int tlx = 0, tly = 0, brx = -1, bry = -1;
-    if (roi_ok(rows, cols, interval, tlx, tly, brx, bry)) return 1;     // the interval and the image size, when every box is empty
-    AVT_HIP(hipSetDevice(rt->device));
-    if (rt->d_boxes.reserve(4 * (size_t)n)) return 1;
-    AVT_HIP(hipMemcpyAsync(rt->d_boxes, b.data(), b.size() * sizeof(int), hipMemcpyHostToDevice, rt->stream));
-    AVT_HIP(hipStreamSynchronize(rt->stream));             // `b` is on this stack frame
-    if (avt_rtree_launch_predict_boxes(rt, rt->d_depth, rt->d_boxes, 4, n, rows, cols, interval, fill)) { avt_set_error("rtree: kernel launch failed"); return 1; }
-    return 0;
-}
-
-static int predict_best_from_bgsub_impl(avt_rtree* rt, avt_bgsub* bg, int interval, int fill) {
-    if (!rt) { avt_set_error("avt_rtree_predict_best_from_bgsub: null tree"); return 1; }
-    if (rt->device < 0) { avt_set_error(kHostOnly); return 1; }
-    if (!bg) { avt_set_error("avt_rtree_predict_best_from_bgsub: null background subtractor"); return 1; }
-    avt_bgsub_view v;
-    if (avt_bgsub_last_run(bg, &v)) return 1;
-    if (v.device != rt->device) { avt_set_error("avt_rtree_predict_best_from_bgsub: the tree and the background subtractor are on different devices"); return 1; }
-    int tlx = 0, tly = 0, brx = -1, bry = -1;
-    if (roi_ok(v.rows, v.cols, interval, tlx, tly, brx, bry)) return 1;
-    AVT_HIP(hipSetDevice(rt->device));
-    const size_t pixels = (size_t)v.n_images * v.rows * v.cols;
-    if (rt->d_labels.reserve(pixels)) return 1;
-    // the labels are these images' from here on, and the tree has no resident depth of its own until the next images_upload
-    rt->n_images = 0; rt->n_labels = v.n_images; rt->rows = v.rows; rt->cols = v.cols;
-    // the tree's stream waits for the run; bg's next upload / run / destroy waits for the labelling.  No copy, no host wait.
-    if (avt_bgsub_reader_begin(bg, rt->stream)) return 1;
-    const int rc = avt_rtree_launch_predict_boxes(rt, v.d_depth, v.d_boxes, v.box_stride, v.n_images, v.rows, v.cols, interval, fill);
-    if (avt_bgsub_reader_end(bg, rt->stream)) return 1;    // also after a failed launch: the memset may be queued
-    if (rc) { avt_set_error("rtree: kernel launch failed"); return 1; }
-    return 0;
-}
-
-static int labels_download_all_impl(avt_rtree* rt, unsigned char* out) {
-    if (!rt || !out || rt->n_labels <= 0) { avt_set_error("avt_rtree_labels_download_all: bad arguments or no labelled images"); return 1; }
-    AVT_HIP(hipMemcpyAsync(out, rt->d_labels, (size_t)rt->n_labels * rt->rows * rt->cols, hipMemcpyDeviceToHost, rt->stream));
-    AVT_HIP(hipStreamSynchronize(rt->stream));
-    return 0;
-}
-
-int avt_rtree_labels_download(avt_rtree* rt, int image, unsigned char* out) {
-    if (!rt || !out || image < 0 || image >= rt->n_labels) { avt_set_error("avt_rtree_labels_download: bad arguments"); return 1; }
-    const size_t px = (size_t)rt->rows * rt->cols;
-    AVT_HIP(hipMemcpyAsync(out, rt->d_labels + px * image, px, hipMemcpyDeviceToHost, rt->stream));
-    AVT_HIP(hipStreamSynchronize(rt->stream));
-    return 0;
-}
-
-int avt_rtree_sync(avt_rtree* rt) {
-    if (!rt) { avt_set_error("avt_rtree_sync: null tree"); return 1; }
-    AVT_HIP(hipStreamSynchronize(rt->stream));
     return 0;
 }
 
 static int avt_rtree_predict_best_impl(avt_rtree* rt, const float* depth, int rows, int cols, int interval, int tlx, int tly, int brx, int bry, int fill,
                            unsigned char* labels_out) {
     if (!rt || !depth || !labels_out) { avt_set_error("avt_rtree_predict_best: null argument"); return 1; }
-    if (roi_ok(rows, cols, interval, tlx, tly, brx, bry)) return 1;
-    if (avt_rtree_images_upload(rt, 1, rows, cols, depth)) return 1;
+    if (avt_label_roi_ok(kTree, rows, cols, interval, tlx, tly, brx, bry)) return 1;
+    if (avt_label_images_upload(rt, kTree, 0, 1, rows, cols, depth)) return 1;
     if (avt_rtree_launch_predict(rt, 1, rows, cols, interval, tlx, tly, brx, bry, fill)) { avt_set_error("rtree: kernel launch failed"); return 1; }
-    return avt_rtree_labels_download(rt, 0, labels_out);
-}
-
-static int avt_rtree_predict_impl(avt_rtree* rt, const float* depth, int rows, int cols, float* dist_out) {
-    if (!rt || !depth || !dist_out || rows <= 0 || cols <= 0) { avt_set_error("avt_rtree_predict: bad arguments"); return 1; }
-    if (avt_rtree_images_upload(rt, 1, rows, cols, depth)) return 1;
-    const size_t n = (size_t)rt->num_parts * rows * cols;
-    DevBuf<float> d_out;
-    if (d_out.reserve(n)) return 1;
-    int rc = avt_rtree_launch_predict_dist(rt, rows, cols, d_out);
-    if (rc) avt_set_error("rtree: kernel launch failed");
-    if (!rc && hipMemcpyAsync(dist_out, d_out, n * sizeof(float), hipMemcpyDeviceToHost, rt->stream) != hipSuccess) { avt_set_error("rtree: download failed"); rc = 1; }
-    if (hipStreamSynchronize(rt->stream) != hipSuccess && !rc) { avt_set_error("rtree: stream failed"); rc = 1; }   // on every path, before d_out goes
-    return rc;
+    return avt_label_labels_download(rt, kTree, 0, labels_out);
 }
 
 static int avt_rtree_post_process_impl(const avt_rtree* rt, unsigned char* image, int rows, int cols, double* com_pre, int com_pre_valid, int interval, int tlx,
                            int tly, int brx, int bry, double dist_to_pre_weight) {
     if (!rt || !image || !com_pre) { avt_set_error("avt_rtree_post_process: null argument"); return 1; }
-    if (roi_ok(rows, cols, interval, tlx, tly, brx, bry)) return 1;
+    if (avt_label_roi_ok(kTree, rows, cols, interval, tlx, tly, brx, bry)) return 1;
     const int np = rt->num_parts;
     if (!com_pre_valid)                               // the resize branch of RTree.cpp:3431-3435
         for (int i = 0; i < np; ++i) { com_pre[2 * i] = -1.; com_pre[2 * i + 1] = 0.; }
@@ -510,7 +406,7 @@ int avt_rtree_export(const avt_rtree* rt, const char* path) {
 }
 
 int avt_rtree_images_upload(avt_rtree* rt, int n_images, int rows, int cols, const float* depth) {
-    return avt_guard("avt_rtree_images_upload", [&]() -> int { return avt_rtree_images_upload_impl(rt, n_images, rows, cols, depth); });
+    return avt_guard("avt_rtree_images_upload", [&]() -> int { return avt_label_images_upload(rt, kTree, 0, n_images, rows, cols, depth); });
 }
 
 int avt_rtree_predict_best(avt_rtree* rt, const float* depth, int rows, int cols, int interval, int tlx, int tly, int brx, int bry, int fill,
@@ -519,19 +415,19 @@ int avt_rtree_predict_best(avt_rtree* rt, const float* depth, int rows, int cols
 }
 
 int avt_rtree_predict(avt_rtree* rt, const float* depth, int rows, int cols, float* dist_out) {
-    return avt_guard("avt_rtree_predict", [&]() -> int { return avt_rtree_predict_impl(rt, depth, rows, cols, dist_out); });
+    return avt_guard("avt_rtree_predict", [&]() -> int { return avt_label_predict_dist(rt, kTree, false, depth, rows, cols, dist_out, launch_dist); });
 }
 
 int avt_rtree_predict_best_resident_boxes(avt_rtree* rt, int interval, const int* boxes, int fill) {
-    return avt_guard("avt_rtree_predict_best_resident_boxes", [&]() -> int { return predict_best_resident_boxes_impl(rt, interval, boxes, fill); });
+    return avt_guard("avt_rtree_predict_best_resident_boxes", [&]() -> int { return avt_label_predict_resident_boxes(rt, kTree, interval, boxes, fill, launch_boxes); });
 }
 
 int avt_rtree_predict_best_from_bgsub(avt_rtree* rt, avt_bgsub* bg, int interval, int fill) {
-    return avt_guard("avt_rtree_predict_best_from_bgsub", [&]() -> int { return predict_best_from_bgsub_impl(rt, bg, interval, fill); });
+    return avt_guard("avt_rtree_predict_best_from_bgsub", [&]() -> int { return avt_label_predict_from_bgsub(rt, kTree, 0, bg, interval, fill, launch_boxes); });
 }
 
 int avt_rtree_labels_download_all(avt_rtree* rt, unsigned char* labels_out) {
-    return avt_guard("avt_rtree_labels_download_all", [&]() -> int { return labels_download_all_impl(rt, labels_out); });
+    return avt_guard("avt_rtree_labels_download_all", [&]() -> int { return avt_label_labels_download_all(rt, kTree, labels_out); });
 }
 
 int avt_rtree_labels_upload(avt_rtree* rt, int n_images, int rows, int cols, const unsigned char* labels) {
@@ -547,20 +443,17 @@ int avt_rtree_post_process_from_bgsub(avt_rtree* rt, avt_bgsub* bg, int interval
 }
 
 int avt_rtree_com_pre_set(avt_rtree* rt, int first, int n, const double* com, const unsigned char* valid) {
-    return avt_guard("avt_rtree_com_pre_set", [&]() -> int {
-        if (!rt || rt->device < 0) { avt_set_error("avt_rtree_com_pre_set: null or host-only tree"); return 1; }
-        AVT_HIP(hipSetDevice(rt->device));
-        return avt_post_com_set(&rt->post, rt->stream, rt->num_parts, first, n, com, valid);
-    });
+    return avt_guard("avt_rtree_com_pre_set", [&]() -> int { return avt_label_com_pre_set(rt, kTree, first, n, com, valid); });
 }
 
 int avt_rtree_com_pre_get(avt_rtree* rt, int first, int n, double* com, unsigned char* valid) {
-    return avt_guard("avt_rtree_com_pre_get", [&]() -> int {
-        if (!rt || rt->device < 0) { avt_set_error("avt_rtree_com_pre_get: null or host-only tree"); return 1; }
-        AVT_HIP(hipSetDevice(rt->device));
-        return avt_post_com_get(&rt->post, rt->stream, rt->num_parts, first, n, com, valid);
-    });
+    return avt_guard("avt_rtree_com_pre_get", [&]() -> int { return avt_label_com_pre_get(rt, kTree, first, n, com, valid); });
 }
+
+// no guard: nothing in these two allocates or throws
+int avt_rtree_labels_download(avt_rtree* rt, int image, unsigned char* out) { return avt_label_labels_download(rt, kTree, image, out); }
+
+int avt_rtree_sync(avt_rtree* rt) { return avt_label_sync(rt, kTree, false); }      // (a host-only tree has no stream: the null stream's wait)
 
 int avt_rtree_post_process(const avt_rtree* rt, unsigned char* image, int rows, int cols, double* com_pre, int com_pre_valid, int interval, int tlx,
                            int tly, int brx, int bry, double dist_to_pre_weight) {

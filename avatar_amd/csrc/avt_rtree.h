@@ -7,7 +7,7 @@
 
 #include "../../include/avt_rtree.h"
 #include "avt_host.h"
-#include "avt_post.h"
+#include "avt_label.h"
 
 // one tree node as the kernel reads it: two 16-byte loads
 struct RtNodeDev {
@@ -18,26 +18,15 @@ struct RtNodeDev {
     int leaf;       // 1: leaf
 };
 
-struct avt_rtree {
-    int device = 0;
-    int num_parts = 0;
+struct avt_rtree : AvtLabelHandle {
     std::vector<float> feature;      // n x 5
     std::vector<int> links;          // n x 3
     std::vector<float> leaf_data;    // nl x num_parts
     std::vector<unsigned char> leaf_best;
-    std::vector<int> part_map;
-    int part_map_type = 0;
     // device
-    hipStream_t stream = nullptr;
     DevBuf<RtNodeDev> d_nodes;
     DevBuf<float> d_leaf;            // [n_leafs][num_parts] distributions
-    DevBuf<float> d_depth;           // the resident images and their labels: one capacity, in pixels
-    DevBuf<unsigned char> d_labels;
-    int n_images = 0, rows = 0, cols = 0;     // n_images: resident depth images of the tree's own (0 after a hand-over from bgsub)
-    int n_labels = 0;                         // images d_labels holds (rows x cols each): what avt_rtree_labels_download serves
-    DevBuf<int> d_boxes;                      // n x 4 regions of interest of avt_rtree_predict_best_resident_boxes
     DevBuf<unsigned long long> d_tcount;      // trainTransfer's (leaf, part) counts since the last avt_rtree_transfer_finish
-    AvtPostState post;                        // avt_rtree_post_process_resident / _from_bgsub: scratch and the per-slot com_pre memory
 };
 
 int avt_rtree_launch_predict_dist(avt_rtree* rt, int rows, int cols, float* d_out);

@@ -187,9 +187,8 @@ int grow_scratch(avt_ctx* c, size_t n_block, size_t n_in, size_t n_out) {
     return st.block.reserve(n_block) || st.in.reserve(n_in) || st.out.reserve(n_out);
 }
 
-// a forest handle H (avt_rtree, avt_rforest): device, stream, d_labels, n_labels, rows, cols
-template <class H>
-int subsample_impl(avt_ctx* c, H* h, avt_bgsub* bg, const char* who, const int* boxes, const int* intervals, const unsigned char* want_centroid,
+// h: the labelling handle (avt_label.h) of a tree or a forest
+int subsample_impl(avt_ctx* c, AvtLabelHandle* h, avt_bgsub* bg, const char* who, const int* boxes, const int* intervals, const unsigned char* want_centroid,
                    int* counts_out, double* centroid_out, int* boxes_out) {
     const std::string w(who);
     if (!c) { avt_set_error(w + ": null context"); return 1; }

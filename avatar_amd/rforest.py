@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
+from .labelhandle import LabelHandle
 from .rtree import RTree
 
 RFOREST_SYMBOLS = [
@@ -25,9 +26,11 @@ RFOREST_SYMBOLS = [
 MAX_TREES = 16       # AVT_RFOREST_MAX_TREES
 
 
-class RForest:
+class RForest(LabelHandle):
     """`trees_or_paths`: rtree.RTree objects and / or tree files, in forest order.  The forest copies the trees; `self.trees`
-    keeps the members (host-only copies for paths) for postProcess and for inspection."""
+    keeps the members (host-only copies for paths) for postProcess and for inspection.  Inference, the resident batch and the
+    device post-processing are LabelHandle's."""
+    _PREFIX = "avt_rforest"
 
     def __init__(self, trees_or_paths, device: int = 0):
         self._lib = capi.load_library()
@@ -66,73 +69,9 @@ class RForest:
         return cls([RTree.trainFromAvatar(model, intrin, image_size, *args, seed=(seed + t) % (1 << 64), device=device, **kw)
                     for t in range(_count(n_trees))], device)
 
-    def __del__(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.avt_rforest_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def predictBest(self, depth, num_threads=0, interval=1, top_left=(0, 0), bot_right=(-1, -1), fill_in_gaps=True):
-        """RTree::predictBest's walk per tree (RTree.cpp:3184-3262), labels from the summed distributions; points are (x, y)."""
-        d = np.ascontiguousarray(depth, np.float32)
-        out = np.empty(d.shape, np.uint8)
-        capi.check(self._lib.avt_rforest_predict_best(self._h, capi.ptr(d, C.c_float), C.c_int(d.shape[0]), C.c_int(d.shape[1]), C.c_int(interval),
-                                                      C.c_int(top_left[0]), C.c_int(top_left[1]), C.c_int(bot_right[0]), C.c_int(bot_right[1]),
-                                                      C.c_int(1 if fill_in_gaps else 0), capi.ptr(out, C.c_ubyte)))
-        return out
-
-    def predict(self, depth):
-        """(numParts, H, W) float32: the trees' distributions added in tree order (0 where depth <= 0); not divided by the
-        number of trees (rtree-run-dataset.cpp:124-138)."""
-        d = np.ascontiguousarray(depth, np.float32)
-        out = np.empty((self.numParts,) + d.shape, np.float32)
-        capi.check(self._lib.avt_rforest_predict(self._h, capi.ptr(d, C.c_float), C.c_int(d.shape[0]), C.c_int(d.shape[1]), capi.ptr(out, C.c_float)))
-        return out
-
     def postProcess(self, image, com_pre=None, interval=1, num_threads=1, top_left=(0, 0), bot_right=(-1, -1), dist_to_pre_weight=0.001):
         """RTree::postProcess through the first member tree: host code that depends on numParts and the part-map type only."""
         return self.trees[0].postProcess(image, com_pre, interval, num_threads, top_left, bot_right, dist_to_pre_weight)
-
-    # ---- resident batch ----
-    def upload_images(self, depth_stack):
-        d = np.ascontiguousarray(depth_stack, np.float32)
-        capi.check(self._lib.avt_rforest_images_upload(self._h, C.c_int(d.shape[0]), C.c_int(d.shape[1]), C.c_int(d.shape[2]), capi.ptr(d, C.c_float)))
-        self._shape = d.shape
-
-    def predict_resident_boxes(self, interval, boxes, fill_in_gaps=True):
-        """The resident images, image i inside boxes[i] = (tl.x, tl.y, br.x, br.y), inclusive: br.x == -1 is the whole image, an
-        empty box (tl > br) leaves its image all 255."""
-        b = np.ascontiguousarray(boxes, np.int32).reshape(-1, 4)
-        n = getattr(self, "_shape", (0,))[0]
-        if n and len(b) != n:
-            raise ValueError(f"RForest.predict_resident_boxes: {len(b)} boxes for {n} resident images")
-        capi.check(self._lib.avt_rforest_predict_best_resident_boxes(self._h, C.c_int(interval), capi.ptr(b, C.c_int), C.c_int(1 if fill_in_gaps else 0)))
-
-    def predict_from_bgsub(self, bg, interval, fill_in_gaps=True):
-        """Labels every image of `bg`'s (bgsub.BGSubtractor) last run_resident inside the box that run found, reading the masked
-        depth and the boxes on the device: no copy of the depth, no host wait."""
-        capi.check(self._lib.avt_rforest_predict_best_from_bgsub(self._h, bg._h, C.c_int(interval), C.c_int(1 if fill_in_gaps else 0)))
-        self._shape = (bg._n,) + tuple(bg._shape[:2])
-
-    # ---- postProcess for a batch on the device: the tree's methods over the forest's own entry points ----
-    _PREFIX = "avt_rforest"
-    upload_labels = RTree.upload_labels
-    post_process_resident = RTree.post_process_resident
-    post_process_from_bgsub = RTree.post_process_from_bgsub
-    com_pre_get = RTree.com_pre_get
-    com_pre_set = RTree.com_pre_set
-
-    def sync(self):
-        capi.check(self._lib.avt_rforest_sync(self._h))
-
-    def download_all_labels(self):
-        out = np.empty(self._shape, np.uint8)
-        capi.check(self._lib.avt_rforest_labels_download_all(self._h, capi.ptr(out, C.c_ubyte)))
-        return out
-
-    def download_labels(self, image):
-        out = np.empty(self._shape[1:], np.uint8)
-        capi.check(self._lib.avt_rforest_labels_download(self._h, C.c_int(image), capi.ptr(out, C.c_ubyte)))
-        return out
 
     # ---- the score: a confusion matrix against ground-truth part masks (include/avt_rforest.h, THE SCORE) ----
     def score_reset(self):

@@ -206,16 +206,18 @@ private:
     ImageF maskedDepth_;
 };
 
-inline std::vector<Image8> RTree::predictBestFromBGSub(BGSubtractor& bgsub, int interval, bool fill_in_gaps, bool download) {
+template <class D, class Api>
+inline std::vector<Image8> LabelHandle<D, Api>::predictBestFromBGSub(BGSubtractor& bgsub, int interval, bool fill_in_gaps, bool download) {
     if (bgsub.batchSize() <= 0) fatal("predictBestFromBGSub", "the background subtractor has no batch run behind it");
-    if (!ensure() || avt_rtree_predict_best_from_bgsub(h_, bgsub.handle(), interval, fill_in_gaps ? 1 : 0) != 0) die("predictBestFromBGSub");
+    if (!self().ensure() || Api::predict_best_from_bgsub(h_, bgsub.handle(), interval, fill_in_gaps ? 1 : 0) != 0) die("predictBestFromBGSub");
     if (!download) return {};
     return downloadAll(bgsub.batchSize(), bgsub.rows(), bgsub.cols(), "predictBestFromBGSub");
 }
 
-inline std::vector<Image8> RTree::postProcessFromBGSub(BGSubtractor& bgsub, int interval, double dist_to_pre_weight) {
+template <class D, class Api>
+inline std::vector<Image8> LabelHandle<D, Api>::postProcessFromBGSub(BGSubtractor& bgsub, int interval, double dist_to_pre_weight) {
     if (bgsub.batchSize() <= 0) fatal("postProcessFromBGSub", "the background subtractor has no batch run behind it");
-    if (!ensure() || avt_rtree_post_process_from_bgsub(h_, bgsub.handle(), interval, dist_to_pre_weight) != 0) die("postProcessFromBGSub");
+    if (!self().ensure() || Api::post_process_from_bgsub(h_, bgsub.handle(), interval, dist_to_pre_weight) != 0) die("postProcessFromBGSub");
     return downloadAll(bgsub.batchSize(), bgsub.rows(), bgsub.cols(), "postProcessFromBGSub");
 }
 

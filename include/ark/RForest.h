@@ -1,9 +1,9 @@
 // ark/RForest.h — several trained ark::RTree run as one forest, over the C ABI of avt_rforest.h: what the reference's tools do
 // with any number of models (rtree-run-dataset.cpp:98-159): RTree::predict per model, the distributions added in model order
 // in float32, the arg-max per pixel (the first part whose sum exceeds a running best that starts at 0; 255 when none does).
-// The members are ark::RTree's inference side (predictBest, predictBestBatch, predictBestFromBGSub, predict, postProcess,
-// numParts, partMap, partMapType), so a forest stands where a tree stands (MultiFrameTracker::attachFrontEnd).  As with
-// ark::RTree a failure is fatal (message + exit).
+// The members are ark::RTree's inference side (LabelHandle's predictBest, predictBestBatch, predictBestFromBGSub, predict and the
+// device postProcess; postProcess, numParts, partMap, partMapType), so a forest stands where a tree stands
+// (MultiFrameTracker::attachFrontEnd).  As with ark::RTree a failure is fatal (message + exit).
 //
 // The score (avt_rforest.h, THE SCORE) is what rtree-run-dataset leaves to the eye: the forest's arg-max against ground-truth
 // part masks as a (numParts + 1)^2 confusion matrix of 64-bit counts, accumulated on the GPU (scoreReset, score, scoreRendered,
@@ -65,7 +65,26 @@ struct ForestScore {
     }
 };
 
-class RForest {
+/** The C handle's type, the class name of the FATAL lines and the entry points of a forest, for LabelHandle */
+struct RForestApi {
+    typedef avt_rforest Handle;
+    static constexpr const char* name = "RForest";
+    static constexpr auto predict_best = avt_rforest_predict_best;
+    static constexpr auto predict = avt_rforest_predict;
+    static constexpr auto images_upload = avt_rforest_images_upload;
+    static constexpr auto predict_best_resident_boxes = avt_rforest_predict_best_resident_boxes;
+    static constexpr auto predict_best_from_bgsub = avt_rforest_predict_best_from_bgsub;
+    static constexpr auto labels_download_all = avt_rforest_labels_download_all;
+    static constexpr auto labels_upload = avt_rforest_labels_upload;
+    static constexpr auto post_process_resident = avt_rforest_post_process_resident;
+    static constexpr auto post_process_from_bgsub = avt_rforest_post_process_from_bgsub;
+    static constexpr auto com_pre_get = avt_rforest_com_pre_get;
+    static constexpr auto com_pre_set = avt_rforest_com_pre_set;
+};
+
+class RForest : public LabelHandle<RForest, RForestApi> {
+    friend class LabelHandle<RForest, RForestApi>;      // ensure()
+
 public:
     /** Load the trees from files, in forest order (rtree-run-dataset.cpp:98-104) */
     explicit RForest(const std::vector<std::string>& paths, int device = 0) : device_(device) {
@@ -83,103 +102,10 @@ public:
     RForest(const RForest&) = delete;
     RForest& operator=(const RForest&) = delete;
 
-    /** RTree::predictBest's walk per tree (RTree.cpp:3184-3262), labels from the summed distributions; num_threads is ignored */
-    Image8 predictBest(const ImageF& depth, int /*num_threads*/, int interval = 1, Point top_left = Point(0, 0), Point bot_right = Point(-1, -1),
-                       bool fill_in_gaps = true) {
-        Image8 result(depth.rows, depth.cols, 255);
-        if (avt_rforest_predict_best(h_, depth.data(), depth.rows, depth.cols, interval, top_left.x, top_left.y, bot_right.x, bot_right.y,
-                                     fill_in_gaps ? 1 : 0, result.data()) != 0)
-            die("predictBest");
-        return result;
-    }
-
-    /** predictBest for a batch of same-size images, image i inside boxes[i] = {tl.x, tl.y, br.x, br.y} (RTree::predictBestBatch) */
-    std::vector<Image8> predictBestBatch(const std::vector<ImageF>& depths, int interval, const std::vector<std::array<int, 4>>& boxes,
-                                         bool fill_in_gaps = true) {
-        if (depths.empty() || depths.size() != boxes.size()) fatal("predictBestBatch", "need one box per depth image, at least one");
-        const int rows = depths[0].rows, cols = depths[0].cols;
-        std::vector<float> d;
-        for (const ImageF& im : depths) {
-            if (im.rows != rows || im.cols != cols) fatal("predictBestBatch", "the images must share one size");
-            d.insert(d.end(), im.a.begin(), im.a.end());
-        }
-        if (avt_rforest_images_upload(h_, (int)depths.size(), rows, cols, d.data()) != 0 ||
-            avt_rforest_predict_best_resident_boxes(h_, interval, boxes[0].data(), fill_in_gaps ? 1 : 0) != 0)
-            die("predictBestBatch");
-        return downloadAll((int)depths.size(), rows, cols, "predictBestBatch");
-    }
-
-    /** The labels of every image of bgsub's last runBatch, each inside the box that run found, read from the masked depth on the
-     *  device (avt_rforest_predict_best_from_bgsub) */
-    std::vector<Image8> predictBestFromBGSub(BGSubtractor& bgsub, int interval = 1, bool fill_in_gaps = true, bool download = true) {
-        if (bgsub.batchSize() <= 0) fatal("predictBestFromBGSub", "the background subtractor has no batch run behind it");
-        if (avt_rforest_predict_best_from_bgsub(h_, bgsub.handle(), interval, fill_in_gaps ? 1 : 0) != 0) die("predictBestFromBGSub");
-        if (!download) return {};          // the labels stay on the device (for postProcessFromBGSub)
-        return downloadAll(bgsub.batchSize(), bgsub.rows(), bgsub.cols(), "predictBestFromBGSub");
-    }
-
-    /** numParts planes of summed distributions, not divided by the number of trees (rtree-run-dataset.cpp:124-138) */
-    std::vector<ImageF> predict(const ImageF& depth) {
-        const size_t px = (size_t)depth.rows * depth.cols;
-        std::vector<float> all((size_t)numParts * px);
-        if (avt_rforest_predict(h_, depth.data(), depth.rows, depth.cols, all.data()) != 0) die("predict");
-        std::vector<ImageF> result(numParts, ImageF(depth.rows, depth.cols));
-        for (int i = 0; i < numParts; ++i) result[i].a.assign(all.begin() + (size_t)i * px, all.begin() + (size_t)(i + 1) * px);
-        return result;
-    }
-
     /** RTree::postProcess (RTree.h:150-166) through the first member tree: host code that reads numParts and the part-map type */
     void postProcess(Image8& image, MatrixNX<2>& com_pre, int interval = 1, int num_threads = 1, Point top_left = Point(0, 0),
                      Point bot_right = Point(-1, -1), double dist_to_pre_weight = 0.001) {
         first_->postProcess(image, com_pre, interval, num_threads, top_left, bot_right, dist_to_pre_weight);
-    }
-
-    // ---- postProcess for a batch on the device (avt_rforest.h: connected components per part on the interval grid; RTree::postProcess
-    // bit for bit at interval 1, a documented difference above it).  Image i of a batch uses memory slot i.
-    /** Label images of one size that another classifier made become the images of the last labelling call */
-    void uploadLabels(const std::vector<Image8>& labels) {
-        if (labels.empty()) fatal("uploadLabels", "need at least one image");
-        const int rows = labels[0].rows, cols = labels[0].cols;
-        std::vector<uint8_t> all;
-        for (const Image8& im : labels) {
-            if (im.rows != rows || im.cols != cols) fatal("uploadLabels", "the images must share one size");
-            all.insert(all.end(), im.a.begin(), im.a.end());
-        }
-        if (avt_rforest_labels_upload(h_, (int)labels.size(), rows, cols, all.data()) != 0) die("uploadLabels");
-        lastN_ = (int)labels.size(); lastRows_ = rows; lastCols_ = cols;
-    }
-
-    /** postProcess on the device, in place on the images of the last labelling call (predictBestBatch, predictBestFromBGSub,
-     *  uploadLabels), image i inside boxes[i] = {tl.x, tl.y, br.x, br.y} (none: whole images; tl > br: nothing to do); returns them */
-    std::vector<Image8> postProcessResident(int interval = 1, const std::vector<std::array<int, 4>>& boxes = {}, double dist_to_pre_weight = 0.001) {
-        if (lastN_ <= 0) fatal("postProcessResident", "no labelled images behind the handle");
-        if (!boxes.empty() && (int)boxes.size() != lastN_) fatal("postProcessResident", "need one box per image, or none");
-        if (avt_rforest_post_process_resident(h_, interval, boxes.empty() ? nullptr : boxes[0].data(), dist_to_pre_weight) != 0) die("postProcessResident");
-        return downloadAll(lastN_, lastRows_, lastCols_, "postProcessResident");
-    }
-
-    /** postProcessResident behind predictBestFromBGSub(bgsub, ...): every image inside the box bgsub's last runBatch left on the
-     *  device */
-    std::vector<Image8> postProcessFromBGSub(BGSubtractor& bgsub, int interval = 1, double dist_to_pre_weight = 0.001) {
-        if (bgsub.batchSize() <= 0) fatal("postProcessFromBGSub", "the background subtractor has no batch run behind it");
-        if (avt_rforest_post_process_from_bgsub(h_, bgsub.handle(), interval, dist_to_pre_weight) != 0) die("postProcessFromBGSub");
-        return downloadAll(bgsub.batchSize(), bgsub.rows(), bgsub.cols(), "postProcessFromBGSub");
-    }
-
-    /** com_pre of memory slot `slot` as postProcess keeps it (2 x numParts); a slot that is not sized yet comes back empty */
-    MatrixNX<2> comPre(int slot) {
-        MatrixNX<2> com;
-        com.resize(2, numParts);
-        unsigned char valid = 0;
-        if (avt_rforest_com_pre_get(h_, slot, 1, com.data(), &valid) != 0) die("comPre");
-        if (!valid) com.a.clear();
-        return com;
-    }
-    /** Installs com_pre into memory slot `slot`; one that is not 2 x numParts makes the slot "not sized yet" */
-    void setComPre(int slot, const MatrixNX<2>& com_pre) {
-        const unsigned char valid = (int)com_pre.cols() == numParts ? 1 : 0;
-        std::vector<double> zero(2 * (size_t)numParts, 0.0);
-        if (avt_rforest_com_pre_set(h_, slot, 1, valid ? com_pre.data() : zero.data(), &valid) != 0) die("setComPre");
     }
 
     // ---- the score: a confusion matrix against ground-truth part masks (avt_rforest.h, THE SCORE)
@@ -284,26 +210,9 @@ private:
         first_.reset(new RTree(numParts, -1));
         first_->nodes = trees[0]->nodes; first_->leafData = trees[0]->leafData; first_->partMap = partMap; first_->partMapType = partMapType;
     }
-    std::vector<Image8> downloadAll(int n, int rows, int cols, const char* what) {
-        std::vector<uint8_t> all((size_t)n * rows * cols);
-        if (avt_rforest_labels_download_all(h_, all.data()) != 0) die(what);
-        lastN_ = n; lastRows_ = rows; lastCols_ = cols;
-        std::vector<Image8> result((size_t)n, Image8(rows, cols));
-        for (int i = 0; i < n; ++i) result[(size_t)i].a.assign(all.begin() + (size_t)i * rows * cols, all.begin() + (size_t)(i + 1) * rows * cols);
-        return result;
-    }
-    [[noreturn]] void fatal(const char* what, const char* why) {
-        std::fprintf(stderr, "FATAL: RForest::%s: %s\n", what, why);
-        std::exit(1);
-    }
-    [[noreturn]] void die(const char* what) {
-        std::fprintf(stderr, "FATAL: RForest::%s: %s\n", what, avt_last_error());
-        std::exit(1);
-    }
-    avt_rforest* h_ = nullptr;
+    bool ensure() { return true; }      // the constructors made the handle
     std::unique_ptr<RTree> first_;
     int device_ = 0;
-    int lastN_ = 0, lastRows_ = 0, lastCols_ = 0;   // the images of the last labelling call
 };
 
 }  // namespace ark

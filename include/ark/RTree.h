@@ -1,7 +1,7 @@
 // ark/RTree.h — the reference's `ark::RTree` (include/RTree.h:12-184) re-created over the C ABI of avt_rtree.h:
 // same class name, member names, defaults and call protocol for the inference side (loadFile, exportFile, predictBest,
-// postProcess, numParts, partMap, leafData, leafBestMatch).  cv::Mat is replaced by the two plain row-major images
-// below, cv::Point by ark::Point, Eigen::Matrix<double,2,Dynamic> by MatrixNX<2> (same column-major layout).
+// postProcess, numParts, partMap, leafData, leafBestMatch).  Inference, the batch forms and postProcess on the device are
+// LabelHandle's (ark/LabelHandle.h, which also has the image and point types), shared with ark::RForest.
 // Training runs on the GPU (include/avt_rtree_train.h): trainFromAvatar is the V3 trainer (RTree.cpp:2338-2950) on avatars
 // skinned, rendered and sampled on the device; train(images...) feeds it in-memory depth images and part masks;
 // trainTransfer(images...) re-fits the leaves (:3332-3420).  The V2 trainer of train(depth_dir, part_mask_dir, ...) is not built.
@@ -17,35 +17,31 @@
 #include "../avt_rtree.h"
 #include "../avt_rtree_train.h"
 #include "Avatar.h"
+#include "LabelHandle.h"
 #include "Types.h"
 
 namespace ark {
 
-struct Point {  // cv::Point stand-in
-    int x = 0, y = 0;
-    Point() {}
-    Point(int x_, int y_) : x(x_), y(y_) {}
+/** The C handle's type, the class name of the FATAL lines and the entry points of a tree, for LabelHandle */
+struct RTreeApi {
+    typedef avt_rtree Handle;
+    static constexpr const char* name = "RTree";
+    static constexpr auto predict_best = avt_rtree_predict_best;
+    static constexpr auto predict = avt_rtree_predict;
+    static constexpr auto images_upload = avt_rtree_images_upload;
+    static constexpr auto predict_best_resident_boxes = avt_rtree_predict_best_resident_boxes;
+    static constexpr auto predict_best_from_bgsub = avt_rtree_predict_best_from_bgsub;
+    static constexpr auto labels_download_all = avt_rtree_labels_download_all;
+    static constexpr auto labels_upload = avt_rtree_labels_upload;
+    static constexpr auto post_process_resident = avt_rtree_post_process_resident;
+    static constexpr auto post_process_from_bgsub = avt_rtree_post_process_from_bgsub;
+    static constexpr auto com_pre_get = avt_rtree_com_pre_get;
+    static constexpr auto com_pre_set = avt_rtree_com_pre_set;
 };
 
-template <class T>
-struct Image {  // row-major rows x cols, the layout of a continuous single-channel cv::Mat
-    int rows = 0, cols = 0;
-    std::vector<T> a;
-    Image() {}
-    Image(int r, int c, T fill = T()) : rows(r), cols(c), a((size_t)r * c, fill) {}
-    T& at(int r, int c) { return a[(size_t)r * cols + c]; }
-    T at(int r, int c) const { return a[(size_t)r * cols + c]; }
-    T* ptr(int r) { return a.data() + (size_t)r * cols; }
-    const T* ptr(int r) const { return a.data() + (size_t)r * cols; }
-    T* data() { return a.data(); }
-    const T* data() const { return a.data(); }
-};
-using ImageF = Image<float>;      // CV_32F depth, metres, 0 = background
-using Image8 = Image<uint8_t>;    // CV_8U part labels, 255 = none
+class RTree : public LabelHandle<RTree, RTreeApi> {
+    friend class LabelHandle<RTree, RTreeApi>;      // ensure()
 
-class BGSubtractor;   // ark/BGSubtractor.h, which defines RTree::predictBestFromBGSub
-
-class RTree {
 public:
     typedef std::vector<float> Distribution;
     /** Assumed depth of background (meters), RTree.cpp:325 */
@@ -76,48 +72,6 @@ public:
         return true;
     }
     bool exportFile(const std::string& path) { return ensure() && avt_rtree_export(h_, path.c_str()) == 0; }
-
-    /** Predict best match for each pixel in image (RTree.h:63-81); num_threads is accepted and ignored (GPU). */
-    Image8 predictBest(const ImageF& depth, int /*num_threads*/, int interval = 1, Point top_left = Point(0, 0), Point bot_right = Point(-1, -1),
-                       bool fill_in_gaps = true) {
-        Image8 result(depth.rows, depth.cols, 255);
-        if (!ensure() || avt_rtree_predict_best(h_, depth.data(), depth.rows, depth.cols, interval, top_left.x, top_left.y, bot_right.x, bot_right.y,
-                                                fill_in_gaps ? 1 : 0, result.data()) != 0)
-            die("predictBest");
-        return result;
-    }
-
-    /** predictBest for a batch of same-size images, image i inside boxes[i] = {tl.x, tl.y, br.x, br.y} (the labelling of
-     *  demo.cpp:179-204 for many streams in one launch): br.x == -1 is the whole image, an empty box (tl > br) leaves its image
-     *  all 255.  One upload, one launch sequence, one download. */
-    std::vector<Image8> predictBestBatch(const std::vector<ImageF>& depths, int interval, const std::vector<std::array<int, 4>>& boxes,
-                                         bool fill_in_gaps = true) {
-        if (depths.empty() || depths.size() != boxes.size()) fatal("predictBestBatch", "need one box per depth image, at least one");
-        const int rows = depths[0].rows, cols = depths[0].cols;
-        std::vector<float> d;
-        for (const ImageF& im : depths) {
-            if (im.rows != rows || im.cols != cols) fatal("predictBestBatch", "the images must share one size");
-            d.insert(d.end(), im.a.begin(), im.a.end());
-        }
-        if (!ensure() || avt_rtree_images_upload(h_, (int)depths.size(), rows, cols, d.data()) != 0 ||
-            avt_rtree_predict_best_resident_boxes(h_, interval, boxes[0].data(), fill_in_gaps ? 1 : 0) != 0)
-            die("predictBestBatch");
-        return downloadAll((int)depths.size(), rows, cols, "predictBestBatch");
-    }
-
-    /** The labels of every image of bgsub's last runBatch, each inside the box that run found, read from the masked depth on the
-     *  device (demo.cpp:179-204 without the host in between; avt_rtree_predict_best_from_bgsub).  download = false leaves them
-     *  there (for postProcessFromBGSub) and returns nothing.  Defined in ark/BGSubtractor.h. */
-    std::vector<Image8> predictBestFromBGSub(BGSubtractor& bgsub, int interval = 1, bool fill_in_gaps = true, bool download = true);
-
-    /** Predict distribution for all of image: numParts planes of CV_32F (RTree.h:59-61) */
-    std::vector<ImageF> predict(const ImageF& depth) {
-        std::vector<float> all((size_t)numParts * depth.rows * depth.cols);
-        if (!ensure() || avt_rtree_predict(h_, depth.data(), depth.rows, depth.cols, all.data()) != 0) die("predict");
-        std::vector<ImageF> result(numParts, ImageF(depth.rows, depth.cols));
-        for (int i = 0; i < numParts; ++i) result[i].a.assign(all.begin() + (size_t)i * depth.rows * depth.cols, all.begin() + (size_t)(i + 1) * depth.rows * depth.cols);
-        return result;
-    }
 
     /** The V3 trainer (RTree.cpp:2338-2950) on in-memory images, parameters in the reference's order (include/RTree.h:88-105;
      *  defaults: rtree-train's command line).  num_threads and verbose are accepted and ignored.  Replaces this tree (numParts
@@ -220,50 +174,6 @@ public:
             die("postProcess");
     }
 
-    // ---- postProcess for a batch on the device (avt_rtree.h: connected components per part on the interval grid; RTree::postProcess
-    // bit for bit at interval 1, a documented difference above it).  Image i of a batch uses memory slot i.
-    /** Label images of one size that another classifier made become the images of the last labelling call */
-    void uploadLabels(const std::vector<Image8>& labels) {
-        if (labels.empty()) fatal("uploadLabels", "need at least one image");
-        const int rows = labels[0].rows, cols = labels[0].cols;
-        std::vector<uint8_t> all;
-        for (const Image8& im : labels) {
-            if (im.rows != rows || im.cols != cols) fatal("uploadLabels", "the images must share one size");
-            all.insert(all.end(), im.a.begin(), im.a.end());
-        }
-        if (!ensure() || avt_rtree_labels_upload(h_, (int)labels.size(), rows, cols, all.data()) != 0) die("uploadLabels");
-        lastN_ = (int)labels.size(); lastRows_ = rows; lastCols_ = cols;
-    }
-
-    /** postProcess on the device, in place on the images of the last labelling call (predictBestBatch, predictBestFromBGSub,
-     *  uploadLabels), image i inside boxes[i] = {tl.x, tl.y, br.x, br.y} (none: whole images; tl > br: nothing to do); returns them */
-    std::vector<Image8> postProcessResident(int interval = 1, const std::vector<std::array<int, 4>>& boxes = {}, double dist_to_pre_weight = 0.001) {
-        if (lastN_ <= 0) fatal("postProcessResident", "no labelled images behind the handle");
-        if (!boxes.empty() && (int)boxes.size() != lastN_) fatal("postProcessResident", "need one box per image, or none");
-        if (avt_rtree_post_process_resident(h_, interval, boxes.empty() ? nullptr : boxes[0].data(), dist_to_pre_weight) != 0) die("postProcessResident");
-        return downloadAll(lastN_, lastRows_, lastCols_, "postProcessResident");
-    }
-
-    /** postProcessResident behind predictBestFromBGSub(bgsub, ...): every image inside the box bgsub's last runBatch left on the
-     *  device.  Defined in ark/BGSubtractor.h. */
-    std::vector<Image8> postProcessFromBGSub(BGSubtractor& bgsub, int interval = 1, double dist_to_pre_weight = 0.001);
-
-    /** com_pre of memory slot `slot` as postProcess keeps it (2 x numParts); a slot that is not sized yet comes back empty */
-    MatrixNX<2> comPre(int slot) {
-        MatrixNX<2> com;
-        com.resize(2, numParts);
-        unsigned char valid = 0;
-        if (!ensure() || avt_rtree_com_pre_get(h_, slot, 1, com.data(), &valid) != 0) die("comPre");
-        if (!valid) com.a.clear();
-        return com;
-    }
-    /** Installs com_pre into memory slot `slot`; one that is not 2 x numParts makes the slot "not sized yet" */
-    void setComPre(int slot, const MatrixNX<2>& com_pre) {
-        const unsigned char valid = (int)com_pre.cols() == numParts ? 1 : 0;
-        std::vector<double> zero(2 * (size_t)numParts, 0.0);
-        if (!ensure() || avt_rtree_com_pre_set(h_, slot, 1, valid ? com_pre.data() : zero.data(), &valid) != 0) die("setComPre");
-    }
-
     /** The C handle (ark::RForest copies the tree through it); a tree filled in through the public members is uploaded first.
      *  Null when the tree is empty. */
     avt_rtree* handle() { return ensure() ? h_ : nullptr; }
@@ -292,14 +202,6 @@ private:
         if (avt_rtree_create(&d, device_, &h_) != 0) return false;
         pull();
         return true;
-    }
-    std::vector<Image8> downloadAll(int n, int rows, int cols, const char* what) {
-        std::vector<uint8_t> all((size_t)n * rows * cols);
-        if (avt_rtree_labels_download_all(h_, all.data()) != 0) die(what);
-        lastN_ = n; lastRows_ = rows; lastCols_ = cols;
-        std::vector<Image8> result((size_t)n, Image8(rows, cols));
-        for (int i = 0; i < n; ++i) result[(size_t)i].a.assign(all.begin() + (size_t)i * rows * cols, all.begin() + (size_t)(i + 1) * rows * cols);
-        return result;
     }
     void pull() {
         int n = 0, nl = 0, pml = 0;
@@ -333,17 +235,7 @@ private:
         h_ = out;
         pull();
     }
-    [[noreturn]] void fatal(const char* what, const char* why) {
-        fprintf(stderr, "FATAL: RTree::%s: %s\n", what, why);
-        std::exit(1);
-    }
-    [[noreturn]] void die(const char* what) {   // the reference's failure mode for this class is a fatal message + exit (RTree.cpp:2984-2996)
-        fprintf(stderr, "FATAL: RTree::%s: %s\n", what, avt_last_error());
-        std::exit(1);
-    }
-    avt_rtree* h_ = nullptr;
     int device_ = 0;
-    int lastN_ = 0, lastRows_ = 0, lastCols_ = 0;   // the images of the last labelling call
 };
 
 }  // namespace ark
