@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <limits>
 
 #include <memory>
@@ -159,6 +160,66 @@ int check_launch(const char* what) {
     return 0;
 }
 
+// One read-back: the device is selected, the copies are queued on the context's stream behind everything that is queued there
+// already, and the host waits once.  A copy whose destination is null - an output the caller did not ask for - is left out.
+struct ReadBack { void* dst; const void* src; size_t bytes; };
+int read_back(avt_ctx* c, std::initializer_list<ReadBack> copies) {
+    AVT_HIP(hipSetDevice(c->device));
+    for (const ReadBack& r : copies)
+        if (r.dst) AVT_HIP(hipMemcpyAsync(r.dst, r.src, r.bytes, hipMemcpyDeviceToHost, c->stream));
+    AVT_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// What the last search left for `frame` - the counts and sums, the gated and the trimmed matches - is there after a stand-alone
+// avt_nn (frame slot 0) and after an optimize call with an ICP iteration on the resident frames: its closing launch resets no
+// bookkeeping (LbsLaunch::vis_init = -1).  `who`: the entry point, for the message.
+int last_search_left(const avt_ctx* c, const char* who, int frame) {
+    const bool after_nn = c->nn_sums_frame0 && !c->frames_valid && frame == 0;
+    const bool after_opt = c->frames_valid && c->ran_icp_iters > 0 && frame < c->nframes;
+    if (!after_nn && !after_opt) { avt_set_error(std::string(who) + ": neither a stand-alone avt_nn (frame 0) nor an optimize call with an ICP iteration has run last"); return 1; }
+    return 0;
+}
+
+// Settings the kernels read from device memory - the option scalars, the gate, the trim set, the budgets - are not kernel argument
+// values, so that a change replays the same captured graphs; they are on the context's stream, behind every search already queued.
+// `held` is the host's record of what the device block holds: when the first n values of it are `want` nothing happens, else `held`
+// becomes `want` and `send(held.data())` enqueues it (a failed send leaves no record).  wait: `send` is an asynchronous copy, which
+// reads `held` when the stream gets to it - the host waits in front of rewriting `held`, for a copy that an earlier, failed call may
+// have left queued on it, and behind the copy, which must have read `held` before the next call rewrites it.  Without: `send`
+// launches kernels that carry the values as arguments, read at the launch.
+template <class T, class Send>
+int upload_when_changed(avt_ctx* c, std::vector<T>& held, const T* want, size_t n, bool wait, Send send) {
+    if (held.size() >= n && std::memcmp(want, held.data(), n * sizeof(T)) == 0) return 0;
+    AVT_HIP(hipSetDevice(c->device));
+    if (wait) AVT_HIP(hipStreamSynchronize(c->stream));
+    held.assign(want, want + n);
+    if (send(held.data())) { held.clear(); return 1; }
+    if (wait) AVT_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// A per-part setting arrives as n = 0 (off), 1 (every part alike) or num_parts values.  refusal(i): why value i is refused, empty
+// when it is not; refusal(-1), asked first: the same for what the setter takes beside the values.
+template <class Refusal>
+int check_per_part(const char* who, int n, int np, Refusal refusal) {
+    if (n != 0 && n != 1 && n != np) {
+        avt_set_error(std::string(who) + ": " + std::to_string(n) + " values; 0 (off), 1 (every part) or num_parts = " + std::to_string(np) + " wanted");
+        return 1;
+    }
+    for (int i = -1; i < n; ++i) {
+        const std::string why = refusal(i);
+        if (!why.empty()) { avt_set_error(std::string(who) + ": " + why); return 1; }
+    }
+    return 0;
+}
+// ... and as num_parts values: `off` where n is 0
+std::vector<double> per_part(int n, int np, const double* v, double off) {
+    std::vector<double> out((size_t)np, off);
+    for (int q = 0; q < np && n > 0; ++q) out[(size_t)q] = v[n == 1 ? 0 : q];
+    return out;
+}
+
 // the launch sequence of one optimize() over the resident frames.  budget (avt_optimize_resident_budgets; nullptr for every other call):
 // the per-frame ICP budgets in device memory - the frames whose budget ends early are held where it ends and put back at the end
 void enqueue_optimize(avt_ctx* c, const avt_options* o, int f0, int nf, hipStream_t stream, const int* budget = nullptr) {
@@ -166,7 +227,7 @@ void enqueue_optimize(avt_ctx* c, const avt_options* o, int f0, int nf, hipStrea
     c->fb.max_iters = o->max_iters_per_icp;
     c->cur_stream = stream;
     c->ran_icp_iters = 0;
-    const int vis_init = o->enable_occlusion ? 0 : 1;
+    const int vis_init = o->enable_occlusion ? 0 : 1, gn_iters = o->max_iters_per_icp;
     c->lbs_cleared = true;
     // The two passes of the data bucketing ride in the trailing workgroups of the two launches they do not depend on (the label
     // histogram beside the skinning, the scatter beside the visibility pass of the first ICP iteration): two launches fewer on
@@ -178,57 +239,54 @@ void enqueue_optimize(avt_ctx* c, const avt_options* o, int f0, int nf, hipStrea
     // workgroup's 90 KB of LDS for EVERY workgroup of the skinning, one per CU, and at 32 frames per launch that costs more than the INIT launch
     // saves: 0.980 -> 0.990 ms.  The row form's batches need k_solve INIT's deal of the evaluation ranges.)
     const bool fuse_init = (c->fb.G >= 64 || (c->fb.use_moments && nf <= 16)) && avt_lbs_can_init(c->dm.d);
+    // budget b: held behind the closing launch of ICP iteration b - 1 (budget 0: the state the call found and its skinning, in two
+    // parts); behind the call's closing launch, the held frames are put back
     const bool hold = budget && o->icp_iters > 0;
-    if (hold) launch_budget_hold(c, nf, budget, c->budget_hold, 0, false, 1);      // budget 0: the state the call found ...
+    if (hold) launch_budget_hold(c, nf, budget, c->budget_hold, 0, false, 1);
     if (!fuse_bucket) { ProfScope ps(c, AVT_K_BUCKET); launch_bucket(c, nf, true); }
     // frame batches: k_compact gathers its candidates from the cloud, so k_lbs does not write the part-sorted copy of it
     const bool few = avt_nn_few(c, nf);
     c->nn_from_cloud = !few;
-    { ProfScope ps(c, AVT_K_LBS); launch_lbs(c, nf, nullptr, nullptr, nullptr, nullptr, 1, vis_init, fuse_bucket, fuse_init && o->icp_iters > 0, false, few); }   // ava.update() precondition (:1356)
-    if (hold) launch_budget_hold(c, nf, budget, c->budget_hold, 0, false, 2);      // ... and its skinning
+    const bool mom = c->fb.use_moments != 0, rides = !mom && avt_solve_rides(c, nf);      // rides - few frames, row form: the reduction is part of the solve's launch
+    {   // ava.update() precondition (:1356)
+        LbsLaunch first;
+        first.from_state = 1; first.vis_init = vis_init; first.with_bucket_count = fuse_bucket; first.with_init = fuse_init && o->icp_iters > 0; first.write_pc = few;
+        ProfScope ps(c, AVT_K_LBS);
+        launch_lbs(c, nf, first);
+    }
+    if (hold) launch_budget_hold(c, nf, budget, c->budget_hold, 0, false, 2);
+    // the normal equations of the trial point.  Moment form (avt_moments.hip): assembled from the correspondences' sufficient statistics -
+    // no Jacobian rows, no partial tiles, no reduction.  Row form: k_eval, and k_reduce where the reduction does not ride.
+    auto evaluate = [&](int next_seq) {
+        if (mom) { ProfScope ps(c, AVT_K_EVAL); launch_assemble(c, nf); return; }
+        { ProfScope ps(c, AVT_K_EVAL); launch_eval(c, nf, false, next_seq); }
+        if (!rides) { ProfScope ps(c, AVT_K_REDUCE); launch_reduce(c, nf); }
+    };
     for (int icp = 0; icp < o->icp_iters; ++icp) {
         { ProfScope ps(c, AVT_K_VISIBILITY); launch_visibility(c, nf, o->enable_occlusion, fuse_bucket && icp == 0); }
         { ProfScope ps(c, AVT_K_NN); launch_nn(c, nf); if (c->trim_on) launch_trim(c, nf); }
-        if (c->fb.use_moments) {
-            // Moment form (avt_moments.hip): the correspondences' sufficient statistics once per ICP iteration, then every GN iteration
-            // assembles its normal equations from them - no Jacobian rows, no partial tiles, no reduction.
-            { ProfScope ps(c, AVT_K_AGGREGATE); launch_finalize(c, nf); }
-            { ProfScope ps(c, AVT_K_MOMENTS); c->fb.const_used = (c->launch_maxN + 2047) / 2048; launch_moments(c, nf); }
-            if (!fuse_init) { ProfScope ps(c, AVT_K_PREPARE); launch_solve(c, nf, SOLVE_INIT); }
-            { ProfScope ps(c, AVT_K_EVAL); launch_assemble(c, nf); }
-            for (int it = 1; it <= std::max(1, o->max_iters_per_icp); ++it) {
-                { ProfScope ps(c, AVT_K_SOLVE); launch_solve(c, nf, it == 1 ? SOLVE_FIRST : SOLVE_NORMAL, it); }
-                if (o->max_iters_per_icp == 0) break;
-                { ProfScope ps(c, AVT_K_EVAL); launch_assemble(c, nf); }
-            }
-            // the accept test of the last trial point: the decision part of the solve kernel alone (SOLVE_DECIDE: no factorisation, no step)
-            if (o->max_iters_per_icp > 0) { ProfScope ps(c, AVT_K_DECIDE); launch_solve(c, nf, SOLVE_DECIDE, o->max_iters_per_icp + 1); }
-            { ProfScope ps(c, AVT_K_LBS); const bool more = icp + 1 < o->icp_iters;
-              launch_lbs(c, nf, nullptr, nullptr, nullptr, nullptr, 2, more ? vis_init : -1, false, fuse_init && more, false, few && more, !more); }      // (the last launch of the call also writes the result records)
-            c->ran_icp_iters++;
-            if (hold) launch_budget_hold(c, nf, budget, c->budget_hold, c->ran_icp_iters, c->ran_icp_iters == o->icp_iters);
-            continue;
-        }
-        { ProfScope ps(c, AVT_K_AGGREGATE); launch_finalize(c, nf); launch_records(c, nf); }
+        { ProfScope ps(c, AVT_K_AGGREGATE); launch_finalize(c, nf); if (!mom) launch_records(c, nf); }
+        if (mom) { ProfScope ps(c, AVT_K_MOMENTS); c->fb.const_used = (c->launch_maxN + 2047) / 2048; launch_moments(c, nf); }      // once per ICP iteration
         if (!fuse_init) { ProfScope ps(c, AVT_K_PREPARE); launch_solve(c, nf, SOLVE_INIT); }
-        const bool rides = avt_solve_rides(c, nf);        // few frames: the reduction is part of the solve's launch
-        { ProfScope ps(c, AVT_K_EVAL); launch_eval(c, nf, false, 1); }
-        if (!rides) { ProfScope ps(c, AVT_K_REDUCE); launch_reduce(c, nf); }
-        for (int it = 1; it <= std::max(1, o->max_iters_per_icp); ++it) {
+        evaluate(1);
+        for (int it = 1; it <= std::max(1, gn_iters); ++it) {
             { ProfScope ps(c, AVT_K_SOLVE); launch_solve(c, nf, it == 1 ? SOLVE_FIRST : SOLVE_NORMAL, it); }
-            if (o->max_iters_per_icp == 0) break;
-            if (it < o->max_iters_per_icp) {
-                { ProfScope ps(c, AVT_K_EVAL); launch_eval(c, nf, false, it + 1); }
-                if (!rides) { ProfScope ps(c, AVT_K_REDUCE); launch_reduce(c, nf); }
-            } else {   // no solve follows the last trial point: its cost alone; the accept test is taken by the k_lbs launch below
-                ProfScope ps(c, AVT_K_DECIDE);
-                launch_eval(c, nf, true);
-            }
+            if (gn_iters == 0) break;
+            if (mom || it < gn_iters) evaluate(it + 1);
+            else { ProfScope ps(c, AVT_K_DECIDE); launch_eval(c, nf, true); }      // no solve follows the last trial point: its cost alone; the accept test is taken by the closing k_lbs launch
         }
-        { ProfScope ps(c, AVT_K_LBS); const bool more = icp + 1 < o->icp_iters;      // the last launch of the call skins only: no bookkeeping reset, no part-sorted copy
-          launch_lbs(c, nf, nullptr, nullptr, nullptr, nullptr, 2, more ? vis_init : -1, false, fuse_init && more, o->max_iters_per_icp > 0, few && more, !more); }   // :1494-1497 (2: from the skeleton tables of the current point)
+        // moment form, the accept test of the last trial point: the decision part of the solve kernel alone (SOLVE_DECIDE: no factorisation, no step)
+        if (mom && gn_iters > 0) { ProfScope ps(c, AVT_K_DECIDE); launch_solve(c, nf, SOLVE_DECIDE, gn_iters + 1); }
+        {   // the closing update() of the ICP iteration (:1494-1497), from the skeleton tables of the current point.  The last one of the
+            // call skins only - no bookkeeping reset, no trial point, no part-sorted copy - and writes the result records.
+            const bool more = icp + 1 < o->icp_iters;
+            LbsLaunch close;
+            close.from_state = 2; close.vis_init = more ? vis_init : -1; close.with_init = fuse_init && more; close.write_pc = few && more; close.pack = !more;
+            close.decide = !mom && gn_iters > 0;      // (the moment form has taken the accept test already)
+            ProfScope ps(c, AVT_K_LBS);
+            launch_lbs(c, nf, close);
+        }
         c->ran_icp_iters++;
-        // budget b: held behind the closing launch of ICP iteration b - 1; behind the call's closing launch, the held frames are put back
         if (hold) launch_budget_hold(c, nf, budget, c->budget_hold, c->ran_icp_iters, c->ran_icp_iters == o->icp_iters);
     }
     c->lbs_cleared = false;
@@ -244,12 +302,10 @@ int sync_params(avt_ctx* c, const avt_options* o) {
     pr.beta_pose = o->beta_pose; pr.beta_shape = o->beta_shape; pr.lambda0 = o->lm_lambda0;
     pr.lm_up = o->lm_up; pr.lm_down = o->lm_down; pr.lm_min = o->lm_lambda_min; pr.lm_max = o->lm_lambda_max; pr.lm_policy = o->lm_policy == 1 ? 1.0 : 0.0;
     pr.ftol = o->function_tolerance;
-    if (c->params_valid && std::memcmp(&pr, &c->params_host, sizeof pr) == 0) return 0;
-    c->params_host = pr;
-    AVT_HIP(hipMemcpyAsync((void*)c->fb.params, &c->params_host, sizeof pr, hipMemcpyHostToDevice, c->stream));
-    AVT_HIP(hipStreamSynchronize(c->stream));     // params_host may be rewritten by the next call
-    c->params_valid = true;
-    return 0;
+    return upload_when_changed(c, c->params_host, &pr, 1, true, [&](const AvtRunParams* src) -> int {
+        AVT_HIP(hipMemcpyAsync((void*)c->fb.params, src, sizeof pr, hipMemcpyHostToDevice, c->stream));
+        return 0;
+    });
 }
 
 constexpr size_t GRAPH_CACHE_ENTRIES = 8;
@@ -280,90 +336,105 @@ int check_optimize(const avt_ctx* c, const avt_options* o) {
     return 0;
 }
 
-// budget: see enqueue_optimize (nullptr: a plain call, whose launch sequence and graphs do not know about budgets)
+// ---- the graph cache: the launch sequence depends only on the launch shape, so it is captured once per shape and replayed afterwards.
+// Every graph call of the process goes through g_graph_mutex: contexts are per thread, but HIP 7.0's hipGraphLaunch is not safe
+// against a hipGraphLaunch from another thread (found by the 8-thread loop-back tests: SIGSEGV in hip::Graph::UpdateStreams <-
+// hip::GraphExec::Run, which rearranges a per-device set of helper streams for graphs with parallel branches).  The calls only
+// enqueue, so the lock is held for microseconds.  graph_drop_all takes it; the other two are called with it held (run_optimize).
+
+// every launch sequence captured so far goes: what it was made with - knobs, scratch, the context itself - is about to change
+void graph_drop_all(avt_ctx* c) {
+    std::lock_guard<std::mutex> graph_lock(g_graph_mutex);
+    for (auto& e : c->graphs) (void)hipGraphExecDestroy(e.exec);
+    c->graphs.clear();
+}
+
+// room for one more: the least recently used launch shape goes, once nothing queued replays it any more
+int graph_evict(avt_ctx* c) {
+    if (c->graphs.size() < GRAPH_CACHE_ENTRIES) return 0;
+    size_t lru = 0;
+    for (size_t i = 1; i < c->graphs.size(); ++i) if (c->graphs[i].last_used < c->graphs[lru].last_used) lru = i;
+    AVT_HIP(hipStreamSynchronize(c->stream));
+    (void)hipGraphExecDestroy(c->graphs[lru].exec);
+    c->graphs.erase(c->graphs.begin() + lru);
+    return 0;
+}
+
+// the cached graph of this call's launch shape; captured - the frame groups as parallel branches - when the shape is new
+int graph_find_or_capture(avt_ctx* c, const avt_options* o, int ngroups, int nfg, const int* budget, avt_ctx::GraphEntry** out) {
+    const int nf = c->nframes;
+    char key[200];
+    snprintf(key, sizeof key, "%d|%d|%d|%d|%d|%d|%d|%d|%dx%d%s%s", nf, ngroups, c->fb.G, c->launch_maxN, o->icp_iters, o->max_iters_per_icp, o->enable_occlusion, c->fb.use_moments,
+             c->occ_w, c->occ_w > 0 ? c->occ_h : 0, budget ? "|budgets" : "",      // (the budgets themselves live in device memory: a changing pattern replays the same graph)
+             c->trim_on ? "|trim" : "");                                            // (one launch more per search; its settings live in device memory too)
+    for (auto& e : c->graphs) if (e.key == key) { *out = &e; return 0; }
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    AVT_HIP(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+    bool bad = false;
+    auto cap = [&](hipError_t e) { if (e != hipSuccess && !bad) { bad = true; avt_set_error(std::string("optimize graph capture: ") + hipGetErrorString(e)); } };
+    if (ngroups > 1) cap(hipEventRecord(c->ev_fork, c->stream));
+    for (int gi = 1; gi < ngroups; ++gi) cap(hipStreamWaitEvent(c->side[gi - 1], c->ev_fork, 0));
+    for (int gi = 0; gi < ngroups; ++gi) {
+        const int f0 = gi * nfg, n = std::min(nfg, nf - f0);
+        if (n > 0) enqueue_optimize(c, o, f0, n, gi == 0 ? c->stream : c->side[gi - 1], budget);
+    }
+    for (int gi = 1; gi < ngroups; ++gi) {
+        cap(hipEventRecord(c->ev_join[gi - 1], c->side[gi - 1]));
+        cap(hipStreamWaitEvent(c->stream, c->ev_join[gi - 1], 0));
+    }
+    cap(hipGetLastError());
+    // the capture is ALWAYS ended, so that a failure does not leave the stream stuck in capture mode
+    const hipError_t ee = hipStreamEndCapture(c->stream, &graph);
+    if (bad || ee != hipSuccess) {
+        if (!bad) avt_set_error(std::string("hipStreamEndCapture: ") + hipGetErrorString(ee));
+        if (graph) (void)hipGraphDestroy(graph);
+        return 1;
+    }
+    const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    if (ei != hipSuccess) { avt_set_error(std::string("hipGraphInstantiate: ") + hipGetErrorString(ei)); return 1; }
+    if (graph_evict(c)) return 1;
+    c->graphs.push_back({key, exec, 0});
+    *out = &c->graphs.back();
+    return 0;
+}
+
+// One optimize() over the resident frames: choose the launch shape, run it - launch by launch, or as the replay of its graph - and
+// note what it leaves.  budget: see enqueue_optimize (nullptr: a plain call, whose launch sequence and graphs do not know about budgets)
 int run_optimize(avt_ctx* c, const avt_options* o, const int* budget = nullptr) {
     const int nf = c->nframes;
     if (check_optimize(c, o)) return 1;
     if (sync_params(c, o)) return 1;
     c->ran_max_iters = o->max_iters_per_icp;
     if (o->icp_iters > 0) c->trim_last = c->trim_on;      // (no ICP iteration: no search, the last one's counts stand)
-    // Large batches run as several frame groups: the latency-bound single-workgroup-per-frame kernels of one group
+    // The shape.  Large batches run as several frame groups: the latency-bound single-workgroup-per-frame kernels of one group
     // (k_solve, k_finalize, k_reduce) overlap the throughput kernels (k_eval, k_nn) of the others on separate streams.
-    // The instrumented (profiling) path keeps the SAME groups and launch shapes and runs them one after the other on
-    // the main stream, so that per-launch timings describe the launches the graph replays.
     c->fb.use_moments = choose_moments(c, nf);      // which form of the data term this call runs
     c->last_run_moments = c->fb.use_moments != 0;
     const int ngroups = plan_groups(c, nf);
     const int nfg = (nf + ngroups - 1) / ngroups;       // frames per group (the last group may be smaller)
     c->fb.G = choose_G(nfg, ngroups, c->tun);
     c->concurrent_groups = ngroups;
+    int rc = 0;
     if (!c->tun.use_graph || c->profiling) {
+        // The instrumented (profiling) path keeps the SAME groups and launch shapes and runs them one after the other on
+        // the main stream, so that per-launch timings describe the launches the graph replays.
         for (int gi = 0; gi < ngroups; ++gi) {
             const int f0 = gi * nfg, n = std::min(nfg, nf - f0);
             if (n > 0) enqueue_optimize(c, o, f0, n, c->stream, budget);
         }
-        c->ran_icp_iters = o->icp_iters;
-        note_products(c, o);
-        return check_launch("optimize launch sequence");
+        rc = check_launch("optimize launch sequence");
+    } else {
+        std::lock_guard<std::mutex> graph_lock(g_graph_mutex);
+        avt_ctx::GraphEntry* hit = nullptr;
+        if (graph_find_or_capture(c, o, ngroups, nfg, budget, &hit)) return 1;
+        hit->last_used = ++c->graph_clock;
+        AVT_HIP(hipGraphLaunch(hit->exec, c->stream));
     }
-    // The launch sequence depends only on the launch shape: capture it once, replay it afterwards.
-    // Every graph call of the process goes through one mutex: contexts are per thread, but HIP 7.0's hipGraphLaunch is not safe
-    // against a hipGraphLaunch from another thread (found by the 8-thread loop-back tests: SIGSEGV in hip::Graph::UpdateStreams <-
-    // hip::GraphExec::Run, which rearranges a per-device set of helper streams for graphs with parallel branches).  The calls
-    // only enqueue, so the lock is held for microseconds.
-    std::lock_guard<std::mutex> graph_lock(g_graph_mutex);
-    char key[200];
-    snprintf(key, sizeof key, "%d|%d|%d|%d|%d|%d|%d|%d|%dx%d%s%s", nf, ngroups, c->fb.G, c->launch_maxN, o->icp_iters, o->max_iters_per_icp, o->enable_occlusion, c->fb.use_moments,
-             c->occ_w, c->occ_w > 0 ? c->occ_h : 0, budget ? "|budgets" : "",      // (the budgets themselves live in device memory: a changing pattern replays the same graph)
-             c->trim_on ? "|trim" : "");                                            // (one launch more per search; its settings live in device memory too)
-    avt_ctx::GraphEntry* hit = nullptr;
-    for (auto& e : c->graphs) if (e.key == key) { hit = &e; break; }
-    if (!hit) {
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t exec = nullptr;
-        AVT_HIP(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-        bool bad = false;
-        auto cap = [&](hipError_t e) { if (e != hipSuccess && !bad) { bad = true; avt_set_error(std::string("optimize graph capture: ") + hipGetErrorString(e)); } };
-        if (ngroups > 1) {
-            cap(hipEventRecord(c->ev_fork, c->stream));
-            for (int gi = 1; gi < ngroups; ++gi) cap(hipStreamWaitEvent(c->side[gi - 1], c->ev_fork, 0));
-            for (int gi = 0; gi < ngroups; ++gi) {
-                const int f0 = gi * nfg, n = std::min(nfg, nf - f0);
-                if (n > 0) enqueue_optimize(c, o, f0, n, gi == 0 ? c->stream : c->side[gi - 1], budget);
-            }
-            for (int gi = 1; gi < ngroups; ++gi) {
-                cap(hipEventRecord(c->ev_join[gi - 1], c->side[gi - 1]));
-                cap(hipStreamWaitEvent(c->stream, c->ev_join[gi - 1], 0));
-            }
-        } else {
-            enqueue_optimize(c, o, 0, nf, c->stream, budget);
-        }
-        cap(hipGetLastError());
-        // the capture is ALWAYS ended, so that a failure does not leave the stream stuck in capture mode
-        const hipError_t ee = hipStreamEndCapture(c->stream, &graph);
-        if (bad || ee != hipSuccess) {
-            if (!bad) avt_set_error(std::string("hipStreamEndCapture: ") + hipGetErrorString(ee));
-            if (graph) (void)hipGraphDestroy(graph);
-            return 1;
-        }
-        const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (ei != hipSuccess) { avt_set_error(std::string("hipGraphInstantiate: ") + hipGetErrorString(ei)); return 1; }
-        if (c->graphs.size() >= GRAPH_CACHE_ENTRIES) {      // evict the least recently used launch shape
-            size_t lru = 0;
-            for (size_t i = 1; i < c->graphs.size(); ++i) if (c->graphs[i].last_used < c->graphs[lru].last_used) lru = i;
-            AVT_HIP(hipStreamSynchronize(c->stream));
-            (void)hipGraphExecDestroy(c->graphs[lru].exec);
-            c->graphs.erase(c->graphs.begin() + lru);
-        }
-        c->graphs.push_back({key, exec, 0});
-        hit = &c->graphs.back();
-    }
-    hit->last_used = ++c->graph_clock;
-    AVT_HIP(hipGraphLaunch(hit->exec, c->stream));
     c->ran_icp_iters = o->icp_iters;
     note_products(c, o);
-    return 0;
+    return rc;
 }
 
 // The context's record of which frames are resident: `count_of(f)` points in frame f.  The counts are validated first - nothing changes when it
@@ -401,54 +472,55 @@ int publish_frames(avt_ctx* c, int nframes, bool same_shape) {
     return 0;
 }
 
-// Installs `nframes` frames with `count_of(f)` points each; data / labels are packed back to back (frame f starts at the sum
-// of the previous counts) in host memory or, with device_src, in device memory (the batch split's receive buffer).
-// Everything is validated before any host or device state changes.  The per-frame point count is also written into the
-// device control blocks (working copy and start copy), so that swapping frames under a resident state - the warm-start
-// pattern avt_frames_upload + avt_optimize_resident - runs with the new counts.
-template <class CountOf>
-int install_frames(avt_ctx* c, int nframes, CountOf count_of, const double* data, const int* labels, bool device_src) {
-    const bool same_shape = c->frames_valid && nframes == c->nframes;
-    if (set_resident_frames(c, nframes, count_of)) return 1;
-    c->frames_valid = false;
-    const hipMemcpyKind kind = device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    for (int f = 0; f < nframes; ++f) {
+// ---- staging: what the staged calls (avt_frames_upload, avt_state_upload, avt_state_download below) and the host-pointer calls share
+
+// the points and labels of the resident frames into their slots: data / labels are packed back to back (frame f starts at the sum
+// of the previous counts) in host memory or, kind = device to device, in device memory (the batch split's receive buffer)
+int enqueue_frame_copies(avt_ctx* c, const double* data, const int* labels, hipMemcpyKind kind) {
+    for (int f = 0; f < c->nframes; ++f) {
         const size_t N = (size_t)c->frame_N[f], o = (size_t)c->frame_off[f];
         if (N == 0) continue;
         AVT_HIP(hipMemcpyAsync(c->fb.data_raw + (size_t)f * c->fb.max_points * 3, data + o * 3, N * 3 * sizeof(double), kind, c->stream));
         AVT_HIP(hipMemcpyAsync(c->fb.labels_raw + (size_t)f * c->fb.max_points, labels + o, N * sizeof(int), kind, c->stream));
     }
-    return publish_frames(c, nframes, same_shape);
-}
-
-int upload_frames(avt_ctx* c, int nframes, const double* data, const int* labels, const int* offs) {
-    const size_t first = nframes > 0 ? (size_t)offs[0] : 0;      // (a bad nframes is install_frames' to reject: no entry of offs is read for it)
-    return install_frames(c, nframes, [&](int f) { return offs[f + 1] - offs[f]; }, data + first * 3, labels + first, false);
-}
-
-int upload_state(avt_ctx* c, int nframes, const double* p, const double* q, const double* w) {
-    const AvtDims& d = c->dm.d;
-    if (!c->frames_valid || nframes != c->nframes) { avt_set_error("state: nframes differs from the resident frames"); return 1; }
-    std::vector<double> xs((size_t)nframes * 2 * d.xsize, 0.0);
-    std::vector<AvtFrameCtl> ctl(nframes);
-    for (int f = 0; f < nframes; ++f) {
-        pack_state_row(d, &xs[(size_t)f * 2 * d.xsize], p, q, w, f);
-        std::memset(&ctl[f], 0, sizeof(AvtFrameCtl));
-        ctl[f].N = c->frame_N[f];
-        ctl[f].comp_cur = -1;
-    }
-    AVT_HIP(hipMemcpyAsync(c->fb.x, xs.data(), xs.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    AVT_HIP(hipMemcpyAsync(c->fb.ctl, ctl.data(), ctl.size() * sizeof(AvtFrameCtl), hipMemcpyHostToDevice, c->stream));
-    AVT_HIP(hipMemcpyAsync(c->fb.x_start, c->fb.x, xs.size() * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    AVT_HIP(hipMemcpyAsync(c->fb.ctl_start, c->fb.ctl, ctl.size() * sizeof(AvtFrameCtl), hipMemcpyDeviceToDevice, c->stream));
-    AVT_HIP(hipStreamSynchronize(c->stream));  // host vectors go out of scope
-    c->state_valid = true;
-    c->results_fresh = false;
     return 0;
 }
 
-// "report once, then clear": the message of the host-pointer and the staged calls for frames whose fault word is set
-int report_device_fault(avt_ctx* c, int nbad, int first, unsigned bits) {
+// The start states and control blocks of the resident frames, [x | ctl] as the device holds them, filled into `block` (caller's, of
+// state_block_bytes, 8-byte aligned) and sent to the working copy and the start copy.  The caller waits before `block` goes.
+size_t state_block_bytes(const avt_ctx* c, int nframes) { return (size_t)nframes * (2 * c->dm.d.xsize * sizeof(double) + sizeof(AvtFrameCtl)); }
+int enqueue_start_states(avt_ctx* c, int nframes, void* block, const double* p, const double* q, const double* w) {
+    const AvtDims& d = c->dm.d;
+    const size_t b_x = (size_t)nframes * 2 * d.xsize * sizeof(double), b_ctl = (size_t)nframes * sizeof(AvtFrameCtl);
+    double* xs = (double*)block;
+    AvtFrameCtl* ctl = (AvtFrameCtl*)((char*)block + b_x);
+    std::memset(block, 0, b_x + b_ctl);
+    for (int f = 0; f < nframes; ++f) {
+        pack_state_row(d, xs + (size_t)f * 2 * d.xsize, p, q, w, f);
+        ctl[f].N = c->frame_N[f];
+        ctl[f].comp_cur = -1;
+    }
+    if (nframes == c->fb.max_frames) {      // [x | ctl] and [x_start | ctl_start] are contiguous on the device as they are in the block
+        AVT_HIP(hipMemcpyAsync(c->fb.x, xs, b_x + b_ctl, hipMemcpyHostToDevice, c->stream));
+        AVT_HIP(hipMemcpyAsync(c->fb.x_start, xs, b_x + b_ctl, hipMemcpyHostToDevice, c->stream));
+    } else {
+        AVT_HIP(hipMemcpyAsync(c->fb.x, xs, b_x, hipMemcpyHostToDevice, c->stream));
+        AVT_HIP(hipMemcpyAsync(c->fb.ctl, ctl, b_ctl, hipMemcpyHostToDevice, c->stream));
+        AVT_HIP(hipMemcpyAsync(c->fb.x_start, c->fb.x, b_x, hipMemcpyDeviceToDevice, c->stream));
+        AVT_HIP(hipMemcpyAsync(c->fb.ctl_start, c->fb.ctl, b_ctl, hipMemcpyDeviceToDevice, c->stream));
+    }
+    return 0;
+}
+
+// A faulty frame anywhere: nothing is handed back.  fault_of(f) is frame f's fault word; the first faulty frame is reported, once -
+// the words are cleared, the next optimize() starts clean.
+template <class FaultOf>
+int check_device_faults(avt_ctx* c, int nframes, FaultOf fault_of) {
+    int first = -1, nbad = 0;
+    unsigned bits = 0;
+    for (int f = 0; f < nframes; ++f)
+        if (const unsigned b = fault_of(f)) { if (first < 0) { first = f; bits = b; } ++nbad; }
+    if (first < 0) return 0;
     char msg[256];
     snprintf(msg, sizeof msg, "optimize: %d frame(s) carry a device fault (first: frame %d, bits 0x%x%s); their result is not valid", nbad, first,
              bits, (bits & AVT_FAULT_RIDE_TIMEOUT) ? ": a solver gave up waiting for the in-launch reduction" : "");
@@ -457,32 +529,22 @@ int report_device_fault(avt_ctx* c, int nbad, int first, unsigned bits) {
     return AVT_STATUS_DEVICE_FAULT;
 }
 
-int download_state(avt_ctx* c, double* p, double* q, double* w, avt_stats* st) {
-    const AvtDims& d = c->dm.d;
-    const int nf = c->nframes;
-    std::vector<double> xs((size_t)nf * 2 * d.xsize);
-    std::vector<AvtFrameCtl> ctl(nf);
-    AVT_HIP(hipMemcpyAsync(xs.data(), c->fb.x, xs.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    AVT_HIP(hipMemcpyAsync(ctl.data(), c->fb.ctl, ctl.size() * sizeof(AvtFrameCtl), hipMemcpyDeviceToHost, c->stream));
-    std::vector<unsigned> fault(nf, 0u);
-    AVT_HIP(hipMemcpyAsync(fault.data(), c->fb.fault, fault.size() * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-    AVT_HIP(hipStreamSynchronize(c->stream));
-    int bad = -1, nbad = 0;
-    for (int f = 0; f < nf; ++f) if (fault[f]) { if (bad < 0) bad = f; ++nbad; }
-    if (bad >= 0) return report_device_fault(c, nbad, bad, fault[bad]);
-    for (int f = 0; f < nf; ++f) {
-        unpack_state_row(d, &xs[((size_t)f * 2 + ctl[f].cur_slot) * d.xsize], p, q, w, f);
-        if (st) {
-            st[f].initial_cost = ctl[f].cost_initial;
-            st[f].final_cost = ctl[f].cost_cur;
-            st[f].lambda = ctl[f].lambda;
-            st[f].num_correspondences = ctl[f].T;
-            st[f].matched_model_points = ctl[f].M;
-            st[f].gn_iterations = ctl[f].gn_iterations;
-            st[f].accepted_steps = ctl[f].accepted;
-        }
-    }
-    return 0;
+// Installs `nframes` frames with `count_of(f)` points each, from host memory or, with device_src, from device memory.
+// Everything is validated before any host or device state changes.  The per-frame point count is also written into the
+// device control blocks (working copy and start copy), so that swapping frames under a resident state - the warm-start
+// pattern avt_frames_upload + avt_optimize_resident - runs with the new counts.
+template <class CountOf>
+int install_frames(avt_ctx* c, int nframes, CountOf count_of, const double* data, const int* labels, bool device_src) {
+    const bool same_shape = c->frames_valid && nframes == c->nframes;
+    if (set_resident_frames(c, nframes, count_of)) return 1;
+    c->frames_valid = false;
+    if (enqueue_frame_copies(c, data, labels, device_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice)) return 1;
+    return publish_frames(c, nframes, same_shape);
+}
+
+int upload_frames(avt_ctx* c, int nframes, const double* data, const int* labels, const int* offs) {
+    const size_t first = nframes > 0 ? (size_t)offs[0] : 0;      // (a bad nframes is install_frames' to reject: no entry of offs is read for it)
+    return install_frames(c, nframes, [&](int f) { return offs[f + 1] - offs[f]; }, data + first * 3, labels + first, false);
 }
 
 // avt_optimize / avt_optimize_batch on HOST pointers - the reference's call shape, optimize(const CloudType&, const VectorXi&, ..)
@@ -499,12 +561,11 @@ int optimize_host_to_host(avt_ctx* c, int nframes, const double* data, const int
     if (set_resident_frames(c, nframes, [&](int f) { return offs[f + 1] - offs[f]; })) return 1;
     c->frames_valid = c->state_valid = false;      // until the copies below are enqueued
     const size_t total = (size_t)c->frame_off[nframes];
-    const int xs = d.xsize, stride = result_stride(d);
-    const size_t b_data = total * 24, b_lab = (total * 4 + 15) & ~(size_t)15, b_x = (size_t)nframes * 2 * xs * 8,
-                 b_ctl = (size_t)nframes * sizeof(AvtFrameCtl), b_res = (size_t)nframes * stride * 8;
+    const int stride = result_stride(d);
+    const size_t b_data = total * 24, b_lab = (total * 4 + 15) & ~(size_t)15, b_state = state_block_bytes(c, nframes), b_res = (size_t)nframes * stride * 8;
     const bool want_posed = posed_cloud || posed_jpos || posed_jtrans;
-    const size_t b_posed = want_posed ? (size_t)(3 * d.V + 15 * d.J) * 8 : 0;
-    const size_t need = b_data + b_lab + b_x + b_ctl + b_res + b_posed + 64;
+    const size_t b_cloud = (size_t)3 * d.V * 8, b_jpos = (size_t)3 * d.J * 8, b_jtrans = (size_t)12 * d.J * 8;
+    const size_t need = b_data + b_lab + b_state + b_res + (want_posed ? b_cloud + b_jpos + b_jtrans : 0) + 64;
     //  the pinned block grows with the largest call and shrinks again when a call needs less than a quarter of it: a tracker that once
     // fitted a dense 512-frame batch does not keep gigabytes pinned for its one-frame calls
     if (c->host_pin_cap < need || (c->host_pin_cap > (64u << 20) && need < c->host_pin_cap / 4)) {
@@ -515,68 +576,39 @@ int optimize_host_to_host(avt_ctx* c, int nframes, const double* data, const int
         AVT_HIP(hipHostMalloc((void**)&c->host_pin, cap, hipHostMallocDefault));
         c->host_pin_cap = cap;
     }
-    char* pin = c->host_pin;
-    double* h_data = (double*)pin; int* h_lab = (int*)(pin + b_data); double* h_x = (double*)(pin + b_data + b_lab);
-    AvtFrameCtl* h_ctl = (AvtFrameCtl*)(pin + b_data + b_lab + b_x); double* h_res = (double*)(pin + b_data + b_lab + b_x + b_ctl);
+    // the pinned block: data | labels | x | ctl | result records | posed outputs of frame 0
+    char *h_data = c->host_pin, *h_lab = h_data + b_data, *h_state = h_lab + b_lab, *h_res = h_state + b_state, *h_posed = h_res + b_res;
     std::memcpy(h_data, data + (size_t)offs[0] * 3, b_data);
     std::memcpy(h_lab, labels + offs[0], total * 4);
-    std::memset(h_x, 0, b_x);
-    std::memset((void*)h_ctl, 0, b_ctl);
-    for (int f = 0; f < nframes; ++f) {
-        pack_state_row(d, h_x + (size_t)f * 2 * xs, p, q, w, f);
-        h_ctl[f].N = c->frame_N[f];
-        h_ctl[f].comp_cur = -1;
-    }
-    for (int f = 0; f < nframes; ++f) {
-        const size_t N = (size_t)c->frame_N[f], off = (size_t)c->frame_off[f];
-        if (N == 0) continue;
-        AVT_HIP(hipMemcpyAsync(c->fb.data_raw + (size_t)f * c->fb.max_points * 3, h_data + off * 3, N * 24, hipMemcpyHostToDevice, c->stream));
-        AVT_HIP(hipMemcpyAsync(c->fb.labels_raw + (size_t)f * c->fb.max_points, h_lab + off, N * 4, hipMemcpyHostToDevice, c->stream));
-    }
-    if (nframes == c->fb.max_frames) {      // [x | ctl] and [x_start | ctl_start] are contiguous on the device as they are in the pinned block
-        AVT_HIP(hipMemcpyAsync(c->fb.x, h_x, b_x + b_ctl, hipMemcpyHostToDevice, c->stream));
-        AVT_HIP(hipMemcpyAsync(c->fb.x_start, h_x, b_x + b_ctl, hipMemcpyHostToDevice, c->stream));
-    } else {
-        AVT_HIP(hipMemcpyAsync(c->fb.x, h_x, b_x, hipMemcpyHostToDevice, c->stream));
-        AVT_HIP(hipMemcpyAsync(c->fb.ctl, h_ctl, b_ctl, hipMemcpyHostToDevice, c->stream));
-        AVT_HIP(hipMemcpyAsync(c->fb.x_start, c->fb.x, b_x, hipMemcpyDeviceToDevice, c->stream));
-        AVT_HIP(hipMemcpyAsync(c->fb.ctl_start, c->fb.ctl, b_ctl, hipMemcpyDeviceToDevice, c->stream));
-    }
+    if (enqueue_frame_copies(c, (const double*)h_data, (const int*)h_lab, hipMemcpyHostToDevice)) return 1;
+    if (enqueue_start_states(c, nframes, h_state, p, q, w)) return 1;
     c->frames_valid = c->state_valid = true;
     if (run_optimize(c, o)) { c->results_fresh = false; return 1; }
     if (!c->results_fresh) { launch_pack_results(c, nframes); c->results_fresh = true; }      // (a call without ICP iterations has no closing k_lbs launch)
-    AVT_HIP(hipMemcpyAsync(h_res, c->fb.results, b_res, hipMemcpyDeviceToHost, c->stream));
-    double* h_posed = (double*)(pin + b_data + b_lab + b_x + b_ctl + b_res);
-    if (want_posed) {      // frame 0's posed outputs into the pinned block, behind the fit, in front of the one synchronisation
-        AVT_HIP(hipMemcpyAsync(h_posed, c->fb.cloud, (size_t)3 * d.V * 8, hipMemcpyDeviceToHost, c->stream));
-        AVT_HIP(hipMemcpyAsync(h_posed + 3 * d.V, c->fb.jointpos, (size_t)3 * d.J * 8, hipMemcpyDeviceToHost, c->stream));
-        AVT_HIP(hipMemcpyAsync(h_posed + 3 * d.V + 3 * d.J, c->fb.jointtrans, (size_t)12 * d.J * 8, hipMemcpyDeviceToHost, c->stream));
-    }
-    AVT_HIP(hipStreamSynchronize(c->stream));      // the one synchronisation of the call
-    int bad = -1, nbad = 0;
-    unsigned badbits = 0;
-    for (int f = 0; f < nframes; ++f)      // a faulty frame anywhere: nothing is handed back
-        if (const unsigned bits = unpack_result_row(d, h_res + (size_t)f * stride, nullptr, nullptr, nullptr, nullptr, f)) { if (bad < 0) { bad = f; badbits = bits; } ++nbad; }
-    if (bad >= 0) return report_device_fault(c, nbad, bad, badbits);
-    if (posed_cloud) std::memcpy(posed_cloud, h_posed, (size_t)3 * d.V * 8);
-    if (posed_jpos) std::memcpy(posed_jpos, h_posed + 3 * d.V, (size_t)3 * d.J * 8);
-    if (posed_jtrans) std::memcpy(posed_jtrans, h_posed + 3 * d.V + 3 * d.J, (size_t)12 * d.J * 8);
-    for (int f = 0; f < nframes; ++f) unpack_result_row(d, h_res + (size_t)f * stride, p, q, w, st, f);
+    // behind the fit, in front of the one synchronisation of the call
+    if (read_back(c, {{h_res, c->fb.results, b_res}, {want_posed ? h_posed : nullptr, c->fb.cloud, b_cloud},
+                      {want_posed ? h_posed + b_cloud : nullptr, c->fb.jointpos, b_jpos}, {want_posed ? h_posed + b_cloud + b_jpos : nullptr, c->fb.jointtrans, b_jtrans}}))
+        return 1;
+    const double* res = (const double*)h_res;
+    if (const int rc = check_device_faults(c, nframes, [&](int f) { return unpack_result_row(d, res + (size_t)f * stride, nullptr, nullptr, nullptr, nullptr, f); })) return rc;
+    if (posed_cloud) std::memcpy(posed_cloud, h_posed, b_cloud);
+    if (posed_jpos) std::memcpy(posed_jpos, h_posed + b_cloud, b_jpos);
+    if (posed_jtrans) std::memcpy(posed_jtrans, h_posed + b_cloud + b_jpos, b_jtrans);
+    for (int f = 0; f < nframes; ++f) unpack_result_row(d, res + (size_t)f * stride, p, q, w, st, f);
     return 0;
 }
 
 // The parameters of a stand-alone skinning (Avatar::update of `nframes` avatars) staged in the prep buffer, which nothing else uses
 // outside optimize(): w | p | R.  `who`: the entry point, for the message.
-struct StagedPose { double *w, *p, *R; };
-int stage_pose(avt_ctx* c, const char* who, int nframes, const double* w, const double* p, const double* R, StagedPose* s) {
+// lbs: the k_lbs launch that poses them (the given pose, no bookkeeping touched)
+int stage_pose(avt_ctx* c, const char* who, int nframes, const double* w, const double* p, const double* R, LbsLaunch* lbs) {
     const AvtDims& d = c->dm.d;
     if ((size_t)nframes * (d.K + 3 + 9 * d.J) > (size_t)c->fb.max_frames * 2 * d.prep_size) { avt_set_error(std::string(who) + ": staging overflow"); return 1; }
-    s->w = c->fb.prep;
-    s->p = s->w + (size_t)nframes * d.K;
-    s->R = s->p + (size_t)nframes * 3;
-    AVT_HIP(hipMemcpyAsync(s->w, w, (size_t)nframes * d.K * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    AVT_HIP(hipMemcpyAsync(s->p, p, (size_t)nframes * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    AVT_HIP(hipMemcpyAsync(s->R, R, (size_t)nframes * 9 * d.J * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    double *dw = c->fb.prep, *dp = dw + (size_t)nframes * d.K, *dR = dp + (size_t)nframes * 3;
+    AVT_HIP(hipMemcpyAsync(dw, w, (size_t)nframes * d.K * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    AVT_HIP(hipMemcpyAsync(dp, p, (size_t)nframes * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    AVT_HIP(hipMemcpyAsync(dR, R, (size_t)nframes * 9 * d.J * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    lbs->w = dw; lbs->p = dp; lbs->R = dR;
     return 0;
 }
 
@@ -746,7 +778,6 @@ static int ctx_create_impl(int device, const avt_model* m, int num_parts, const 
     return 0;
 }
 
-
 int avt_ctx_create(int device, const avt_model* m, int num_parts, const int* part_map, int max_points, int max_frames, avt_ctx** out) {
     if (out) *out = nullptr;
     const int rc = avt_guard("avt_ctx_create", [&]() -> int { return ctx_create_impl(device, m, num_parts, part_map, max_points, max_frames, out); });
@@ -767,7 +798,7 @@ void avt_ctx_destroy(avt_ctx* c) {
     // every device buffer (DevBuf members) goes with `delete`, after the events and the streams: the main stream has just been
     // drained and every side stream joins it, so nothing is queued on those buffers either way
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
-    { std::lock_guard<std::mutex> graph_lock(g_graph_mutex); for (auto& g : c->graphs) (void)hipGraphExecDestroy(g.exec); }
+    graph_drop_all(c);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->sub.ev_labels) (void)hipEventDestroy(c->sub.ev_labels);
     for (int i = 0; i < AVT_MAX_GROUPS - 1; ++i) {
@@ -779,8 +810,11 @@ void avt_ctx_destroy(avt_ctx* c) {
 }
 
 int avt_sync(avt_ctx* c) {
-    AVT_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return avt_guard("avt_sync", [&]() -> int {
+        if (!c) { avt_set_error("avt_sync: null context"); return 1; }
+        AVT_HIP(hipStreamSynchronize(c->stream));
+        return 0;
+    });
 }
 
 int avt_lbs_update(avt_ctx* c, int nframes, const double* w, const double* p, const double* R, double* cloud, double* joint_pos,
@@ -791,29 +825,26 @@ int avt_lbs_update(avt_ctx* c, int nframes, const double* w, const double* p, co
         if (nframes <= 0 || nframes > c->fb.max_frames) { avt_set_error("avt_lbs_update: nframes out of range"); return 1; }
         AVT_HIP(hipSetDevice(c->device));
         c->frames_valid = c->state_valid = false;    // frame slots' posed clouds / skeleton scratch are overwritten
-        StagedPose s;
-        if (stage_pose(c, "avt_lbs_update", nframes, w, p, R, &s)) return 1;
-        { ProfScope ps(c, AVT_K_LBS); launch_lbs(c, nframes, nullptr, s.w, s.p, s.R, 0, -1); }
+        LbsLaunch lbs;
+        if (stage_pose(c, "avt_lbs_update", nframes, w, p, R, &lbs)) return 1;
+        { ProfScope ps(c, AVT_K_LBS); launch_lbs(c, nframes, lbs); }
         if (check_launch("k_lbs")) return 1;
-        if (cloud) AVT_HIP(hipMemcpyAsync(cloud, c->fb.cloud, (size_t)nframes * 3 * d.V * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (joint_pos) AVT_HIP(hipMemcpyAsync(joint_pos, c->fb.jointpos, (size_t)nframes * 3 * d.J * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (joint_trans) AVT_HIP(hipMemcpyAsync(joint_trans, c->fb.jointtrans, (size_t)nframes * 12 * d.J * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        AVT_HIP(hipStreamSynchronize(c->stream));
-        return 0;
+        return read_back(c, {{cloud, c->fb.cloud, (size_t)nframes * 3 * d.V * sizeof(double)}, {joint_pos, c->fb.jointpos, (size_t)nframes * 3 * d.J * sizeof(double)},
+                             {joint_trans, c->fb.jointtrans, (size_t)nframes * 12 * d.J * sizeof(double)}});
     });
 }
 
 int avt_visibility(avt_ctx* c, const double* cloud, int enable, unsigned char* visible) {
-    if (!c || !cloud || !visible) { avt_set_error("avt_visibility: null argument"); return 1; }
-    const AvtDims& d = c->dm.d;
-    AVT_HIP(hipSetDevice(c->device));
-    c->frames_valid = c->state_valid = false;
-    AVT_HIP(hipMemcpyAsync(c->fb.cloud, cloud, (size_t)3 * d.V * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    { ProfScope ps(c, AVT_K_VISIBILITY); launch_visibility(c, 1, enable); }
-    if (check_launch("k_visibility")) return 1;
-    AVT_HIP(hipMemcpyAsync(visible, c->fb.visible, (size_t)d.V, hipMemcpyDeviceToHost, c->stream));
-    AVT_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return avt_guard("avt_visibility", [&]() -> int {
+        if (!c || !cloud || !visible) { avt_set_error("avt_visibility: null argument"); return 1; }
+        const AvtDims& d = c->dm.d;
+        AVT_HIP(hipSetDevice(c->device));
+        c->frames_valid = c->state_valid = false;
+        AVT_HIP(hipMemcpyAsync(c->fb.cloud, cloud, (size_t)3 * d.V * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        { ProfScope ps(c, AVT_K_VISIBILITY); launch_visibility(c, 1, enable); }
+        if (check_launch("k_visibility")) return 1;
+        return read_back(c, {{visible, c->fb.visible, (size_t)d.V}});
+    });
 }
 
 int avt_nn(avt_ctx* c, const double* model_cloud, const unsigned char* visible, const double* data, const int* labels, int N, int* out) {
@@ -829,8 +860,7 @@ int avt_nn(avt_ctx* c, const double* model_cloud, const unsigned char* visible, 
         c->nn_sums_frame0 = false;
         // part-sorted SoA copy of the model cloud
         std::vector<int> ppos(V);
-        AVT_HIP(hipMemcpyAsync(ppos.data(), c->dm.part_pos, (size_t)V * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        AVT_HIP(hipStreamSynchronize(c->stream));
+        if (read_back(c, {{ppos.data(), c->dm.part_pos, (size_t)V * sizeof(int)}})) return 1;
         std::vector<double> px(V), py(V), pz(V);
         for (int v = 0; v < V; ++v) { px[ppos[v]] = model_cloud[3 * v]; py[ppos[v]] = model_cloud[3 * v + 1]; pz[ppos[v]] = model_cloud[3 * v + 2]; }
         AVT_HIP(hipMemcpyAsync(c->fb.pcx, px.data(), V * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -853,8 +883,7 @@ int avt_nn(avt_ctx* c, const double* model_cloud, const unsigned char* visible, 
         { ProfScope ps(c, AVT_K_NN); launch_nn(c, 1); if (c->trim_on) launch_trim(c, 1); }
         c->trim_last = c->trim_on;
         if (check_launch("k_nn")) return 1;
-        AVT_HIP(hipMemcpyAsync(out, c->fb.corr, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        AVT_HIP(hipStreamSynchronize(c->stream));
+        if (read_back(c, {{out, c->fb.corr, (size_t)N * sizeof(int)}})) return 1;
         c->nn_sums_frame0 = true;
         return 0;
     });
@@ -876,9 +905,9 @@ int avt_synth_render_frames_mode(avt_ctx* c, int nframes, const double* w, const
         if (nframes <= 0 || nframes > c->fb.max_frames) { avt_set_error("avt_synth_render_frames: nframes out of range"); return 1; }
         AVT_HIP(hipSetDevice(c->device));
         // pose the ground-truth avatars (Avatar::update) for all frames
-        StagedPose s;
-        if (stage_pose(c, "avt_synth_render_frames", nframes, w, p, R, &s)) return 1;
-        launch_lbs(c, nframes, nullptr, s.w, s.p, s.R, 0, -1);
+        LbsLaunch lbs;
+        if (stage_pose(c, "avt_synth_render_frames", nframes, w, p, R, &lbs)) return 1;
+        launch_lbs(c, nframes, lbs);
         // rasterise in chunks of frames (8 bytes of z-buffer key per pixel)
         const size_t npix = (size_t)width * height;
         const int chunk = std::max(1, std::min(nframes, (int)((256ull << 20) / (npix * (painter ? 21 : 9) + 64))));
@@ -907,8 +936,7 @@ int avt_synth_render_frames_mode(avt_ctx* c, int nframes, const double* w, const
         c->fb.f0 = 0;
         if (rc) { avt_set_error("avt_synth_render_frames: render launch failed"); return 1; }
         std::vector<AvtFrameCtl> ctl(nframes);
-        AVT_HIP(hipMemcpyAsync(ctl.data(), c->fb.ctl, ctl.size() * sizeof(AvtFrameCtl), hipMemcpyDeviceToHost, c->stream));
-        AVT_HIP(hipStreamSynchronize(c->stream));
+        if (read_back(c, {{ctl.data(), c->fb.ctl, ctl.size() * sizeof(AvtFrameCtl)}})) return 1;
         c->frames_valid = c->state_valid = false;      // the rendered frames replace what was resident; they have no start state
         for (int f = 0; f < nframes; ++f)
             if (ctl[f].T > c->fb.max_points) { avt_set_error("avt_synth_render_frames: a rendered frame has more points than max_points_per_frame"); return 1; }
@@ -931,23 +959,17 @@ int avt_synth_render_images(avt_ctx* c, int frame, float* depth, unsigned char* 
             return 1;
         }
         if (frame < 0 || frame >= c->render_img_frames) { avt_set_error("avt_synth_render_images: frame out of range"); return 1; }
-        AVT_HIP(hipSetDevice(c->device));
         const size_t npix = (size_t)c->render_img_w * c->render_img_h;
-        if (depth) AVT_HIP(hipMemcpyAsync(depth, c->render_depth + (size_t)frame * npix, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        if (part_mask) AVT_HIP(hipMemcpyAsync(part_mask, c->render_label + (size_t)frame * npix, npix, hipMemcpyDeviceToHost, c->stream));
-        AVT_HIP(hipStreamSynchronize(c->stream));
-        return 0;
+        return read_back(c, {{depth, c->render_depth + (size_t)frame * npix, npix * sizeof(float)}, {part_mask, c->render_label + (size_t)frame * npix, npix}});
     });
 }
 
 int avt_frames_download(avt_ctx* c, int frame, double* data_3xN, int* labels) {
-    if (!c || !c->frames_valid || frame < 0 || frame >= c->nframes) { avt_set_error("avt_frames_download: bad argument"); return 1; }
-    AVT_HIP(hipSetDevice(c->device));
-    const size_t N = c->frame_N[frame];
-    if (data_3xN) AVT_HIP(hipMemcpyAsync(data_3xN, c->fb.data_raw + (size_t)frame * c->fb.max_points * 3, N * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (labels) AVT_HIP(hipMemcpyAsync(labels, c->fb.labels_raw + (size_t)frame * c->fb.max_points, N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    AVT_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return avt_guard("avt_frames_download", [&]() -> int {
+        if (!c || !c->frames_valid || frame < 0 || frame >= c->nframes) { avt_set_error("avt_frames_download: bad argument"); return 1; }
+        const size_t N = c->frame_N[frame];
+        return read_back(c, {{data_3xN, c->fb.data_raw + (size_t)frame * c->fb.max_points * 3, N * 3 * sizeof(double)}, {labels, c->fb.labels_raw + (size_t)frame * c->fb.max_points, N * sizeof(int)}});
+    });
 }
 
 int avt_frames_upload(avt_ctx* c, int nframes, const double* data, const int* labels, const int* frame_offsets) {
@@ -964,7 +986,13 @@ int avt_state_upload(avt_ctx* c, int nframes, const double* p, const double* q, 
     return avt_guard("avt_state_upload", [&]() -> int {
         if (!c || !p || !q || !w) { avt_set_error("avt_state_upload: null argument"); return 1; }
         AVT_HIP(hipSetDevice(c->device));
-        return upload_state(c, nframes, p, q, w);
+        if (!c->frames_valid || nframes != c->nframes) { avt_set_error("state: nframes differs from the resident frames"); return 1; }
+        std::vector<double> block((state_block_bytes(c, nframes) + 7) / 8);
+        if (enqueue_start_states(c, nframes, block.data(), p, q, w)) return 1;
+        AVT_HIP(hipStreamSynchronize(c->stream));  // the block goes out of scope
+        c->state_valid = true;
+        c->results_fresh = false;
+        return 0;
     });
 }
 
@@ -992,17 +1020,17 @@ int avt_optimize_resident_budgets(avt_ctx* c, const avt_options* opt, const int*
                 return 1;
             }
         if (c->budget_hold.reserve((size_t)c->fb.max_frames * avt_budget_hold_doubles(c->dm.d)) || c->budget.reserve((size_t)c->fb.max_frames)) return 1;
-        if (c->budget_host.size() < (size_t)nf || !std::equal(icp_budget, icp_budget + nf, c->budget_host.begin())) {
-            for (int f0 = 0; f0 < nf; f0 += AVT_BUDGET_CHUNK) {
-                AvtBudgetChunk a;
-                a.f0 = f0;
-                a.n = std::min(AVT_BUDGET_CHUNK, nf - f0);
-                std::copy(icp_budget + f0, icp_budget + f0 + a.n, a.b);
-                launch_budget_set(c, c->budget, a);
-            }
-            if (check_launch("k_budget_set")) { c->budget_host.clear(); return 1; }
-            c->budget_host.assign(icp_budget, icp_budget + nf);
-        }
+        if (upload_when_changed(c, c->budget_host, icp_budget, (size_t)nf, false, [&](const int* b) -> int {
+                for (int f0 = 0; f0 < nf; f0 += AVT_BUDGET_CHUNK) {
+                    AvtBudgetChunk a;
+                    a.f0 = f0;
+                    a.n = std::min(AVT_BUDGET_CHUNK, nf - f0);
+                    std::copy(b + f0, b + f0 + a.n, a.b);
+                    launch_budget_set(c, c->budget, a);
+                }
+                return check_launch("k_budget_set");
+            }))
+            return 1;
         const int rc = run_optimize(c, opt, c->budget);
         c->results_fresh = false;      // the result records of the closing launch describe the frames before the held ones were put back
         return rc;
@@ -1035,18 +1063,35 @@ int avt_state_upload_frames(avt_ctx* c, int count, const int* frames, const doub
 }
 
 int avt_state_reset(avt_ctx* c) {
-    if (!c || c->nframes <= 0 || !c->state_valid) { avt_set_error("avt_state_reset: no state resident"); return 1; }
-    AVT_HIP(hipSetDevice(c->device));
-    launch_state_reset(c, c->nframes);
-    c->results_fresh = false;
-    return check_launch("k_state_reset");
+    return avt_guard("avt_state_reset", [&]() -> int {
+        if (!c || c->nframes <= 0 || !c->state_valid) { avt_set_error("avt_state_reset: no state resident"); return 1; }
+        AVT_HIP(hipSetDevice(c->device));
+        launch_state_reset(c, c->nframes);
+        c->results_fresh = false;
+        return check_launch("k_state_reset");
+    });
 }
 
-int avt_state_download(avt_ctx* c, double* p, double* q, double* w, avt_stats* stats) {
+int avt_state_download(avt_ctx* c, double* p, double* q, double* w, avt_stats* st) {
     return avt_guard("avt_state_download", [&]() -> int {
         if (!c) { avt_set_error("avt_state_download: null context"); return 1; }
-        AVT_HIP(hipSetDevice(c->device));
-        return download_state(c, p, q, w, stats);
+        const AvtDims& d = c->dm.d;
+        const int nf = c->nframes;
+        std::vector<double> xs((size_t)nf * 2 * d.xsize);
+        std::vector<AvtFrameCtl> ctl(nf);
+        std::vector<unsigned> fault(nf, 0u);
+        if (read_back(c, {{xs.data(), c->fb.x, xs.size() * sizeof(double)}, {ctl.data(), c->fb.ctl, ctl.size() * sizeof(AvtFrameCtl)},
+                          {fault.data(), c->fb.fault, fault.size() * sizeof(unsigned)}}))
+            return 1;
+        if (const int rc = check_device_faults(c, nf, [&](int f) { return fault[f]; })) return rc;
+        for (int f = 0; f < nf; ++f) {
+            unpack_state_row(d, &xs[((size_t)f * 2 + ctl[f].cur_slot) * d.xsize], p, q, w, f);
+            if (!st) continue;
+            st[f].initial_cost = ctl[f].cost_initial; st[f].final_cost = ctl[f].cost_cur; st[f].lambda = ctl[f].lambda;
+            st[f].num_correspondences = ctl[f].T; st[f].matched_model_points = ctl[f].M;
+            st[f].gn_iterations = ctl[f].gn_iterations; st[f].accepted_steps = ctl[f].accepted;
+        }
+        return 0;
     });
 }
 
@@ -1077,30 +1122,26 @@ int avt_optimize_posed(avt_ctx* c, const double* data, const int* labels, int N,
 }
 
 int avt_get_correspondences(avt_ctx* c, int frame, int* out) {
-    if (!c || !out || frame < 0 || frame >= c->nframes) { avt_set_error("avt_get_correspondences: bad argument"); return 1; }
-    AVT_HIP(hipSetDevice(c->device));
-    AVT_HIP(hipMemcpyAsync(out, c->fb.corr + (size_t)frame * c->fb.max_points, (size_t)c->frame_N[frame] * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    AVT_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return avt_guard("avt_get_correspondences", [&]() -> int {
+        if (!c || !out || frame < 0 || frame >= c->nframes) { avt_set_error("avt_get_correspondences: bad argument"); return 1; }
+        return read_back(c, {{out, c->fb.corr + (size_t)frame * c->fb.max_points, (size_t)c->frame_N[frame] * sizeof(int)}});
+    });
 }
 
 int avt_get_cloud(avt_ctx* c, int frame, double* cloud) {
-    if (!c || !cloud || frame < 0 || frame >= c->fb.max_frames) { avt_set_error("avt_get_cloud: bad argument"); return 1; }
-    AVT_HIP(hipSetDevice(c->device));
-    AVT_HIP(hipMemcpyAsync(cloud, c->fb.cloud + (size_t)frame * 3 * c->dm.d.V, (size_t)3 * c->dm.d.V * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    AVT_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return avt_guard("avt_get_cloud", [&]() -> int {
+        if (!c || !cloud || frame < 0 || frame >= c->fb.max_frames) { avt_set_error("avt_get_cloud: bad argument"); return 1; }
+        return read_back(c, {{cloud, c->fb.cloud + (size_t)frame * 3 * c->dm.d.V, (size_t)3 * c->dm.d.V * sizeof(double)}});
+    });
 }
 
 int avt_get_posed(avt_ctx* c, int frame, double* cloud, double* joint_pos, double* joint_trans) {
-    if (!c || frame < 0 || frame >= c->fb.max_frames) { avt_set_error("avt_get_posed: bad argument"); return 1; }
-    const AvtDims& d = c->dm.d;
-    AVT_HIP(hipSetDevice(c->device));
-    if (cloud) AVT_HIP(hipMemcpyAsync(cloud, c->fb.cloud + (size_t)frame * 3 * d.V, (size_t)3 * d.V * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (joint_pos) AVT_HIP(hipMemcpyAsync(joint_pos, c->fb.jointpos + (size_t)frame * 3 * d.J, (size_t)3 * d.J * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (joint_trans) AVT_HIP(hipMemcpyAsync(joint_trans, c->fb.jointtrans + (size_t)frame * 12 * d.J, (size_t)12 * d.J * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    AVT_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return avt_guard("avt_get_posed", [&]() -> int {
+        if (!c || frame < 0 || frame >= c->fb.max_frames) { avt_set_error("avt_get_posed: bad argument"); return 1; }
+        const AvtDims& d = c->dm.d;
+        return read_back(c, {{cloud, c->fb.cloud + (size_t)frame * 3 * d.V, (size_t)3 * d.V * sizeof(double)}, {joint_pos, c->fb.jointpos + (size_t)frame * 3 * d.J, (size_t)3 * d.J * sizeof(double)},
+                             {joint_trans, c->fb.jointtrans + (size_t)frame * 12 * d.J, (size_t)12 * d.J * sizeof(double)}});
+    });
 }
 
 int avt_get_normal_equations(avt_ctx* c, int frame, double* H, double* g, double* cost) {
@@ -1133,13 +1174,10 @@ int avt_get_normal_equations(avt_ctx* c, int frame, double* H, double* g, double
         c->fb.G = G_keep;
         c->fb.use_moments = use_moments_keep;
         if (check_launch("avt_get_normal_equations")) return 1;
-        AVT_HIP(hipStreamSynchronize(c->stream));
-        AvtFrameCtl ctl;
-        AVT_HIP(hipMemcpyAsync(&ctl, c->fb.ctl + frame, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
-        AVT_HIP(hipStreamSynchronize(c->stream));
+        AvtFrameCtl ctl;      // (first: its cur_slot says which of the frame's two systems is the trial point's)
+        if (read_back(c, {{&ctl, c->fb.ctl + frame, sizeof(ctl)}})) return 1;
         std::vector<double> buf((size_t)d.HS * d.HS);
-        AVT_HIP(hipMemcpyAsync(buf.data(), c->fb.Hraw + ((size_t)frame * 2 + (1 - ctl.cur_slot)) * buf.size(), buf.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        AVT_HIP(hipStreamSynchronize(c->stream));
+        if (read_back(c, {{buf.data(), c->fb.Hraw + ((size_t)frame * 2 + (1 - ctl.cur_slot)) * buf.size(), buf.size() * sizeof(double)}})) return 1;
         for (int r = 0; r < d.P; ++r) {
             if (H) for (int q = 0; q < d.P; ++q) H[(size_t)r * d.P + q] = buf[(size_t)r * d.HS + q];
             if (g) g[r] = buf[(size_t)d.P * d.HS + r];
@@ -1154,15 +1192,12 @@ int avt_debug_mfma_count(avt_ctx* c, int frame, long long* eval_rows, long long*
         if (!c || frame < 0 || frame >= c->nframes) { avt_set_error("avt_debug_mfma_count: bad argument"); return 1; }
         if (!c->frames_valid || c->ran_icp_iters <= 0) { avt_set_error("avt_debug_mfma_count: no optimize call has run on the resident frames"); return 1; }
         const AvtDims& d = c->dm.d;
-        AVT_HIP(hipSetDevice(c->device));
-        AVT_HIP(hipStreamSynchronize(c->stream));
         if (solve) *solve = avt_solve_mfma_count(d);
         if (moments) {
             *moments = -1;
             if (d.mom_ok) {
                 std::vector<int> cnt(d.V);
-                AVT_HIP(hipMemcpyAsync(cnt.data(), c->fb.cnt + (size_t)frame * d.V, cnt.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-                AVT_HIP(hipStreamSynchronize(c->stream));
+                if (read_back(c, {{cnt.data(), c->fb.cnt + (size_t)frame * d.V, cnt.size() * sizeof(int)}})) return 1;
                 *moments = avt_moments_mfma_count(c->model, cnt.data());
             }
         }
@@ -1171,13 +1206,11 @@ int avt_debug_mfma_count(avt_ctx* c, int frame, long long* eval_rows, long long*
             if (c->have_records && d.NT <= 6) {
                 // k_records leaves one word per batch of 16 matched points: bits 0..23 = the live tile pairs (avt_eval.hip); k_eval runs the
                 // 12 k-steps (48 rows / 4) of every live pair - the split pair's are dealt over the four waves, 12 in total all the same
-                AvtFrameCtl ctl;
-                AVT_HIP(hipMemcpyAsync(&ctl, c->fb.ctl + frame, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
-                AVT_HIP(hipStreamSynchronize(c->stream));
+                AvtFrameCtl ctl;      // (first: its M says how many batches there are)
+                if (read_back(c, {{&ctl, c->fb.ctl + frame, sizeof(ctl)}})) return 1;
                 const int nb = (ctl.M + AVT_EVAL_PTS - 1) / AVT_EVAL_PTS;
                 std::vector<int> bm(std::max(nb, 1));
-                AVT_HIP(hipMemcpyAsync(bm.data(), c->fb.bmask + (size_t)frame * d.nb_max, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-                AVT_HIP(hipStreamSynchronize(c->stream));
+                if (read_back(c, {{bm.data(), c->fb.bmask + (size_t)frame * d.nb_max, (size_t)nb * sizeof(int)}})) return 1;
                 long long n = 0;
                 for (int b = 0; b < nb; ++b) n += 12ll * __builtin_popcount((unsigned)bm[b] & 0xffffffu);
                 *eval_rows = n;
@@ -1190,28 +1223,22 @@ int avt_debug_mfma_count(avt_ctx* c, int frame, long long* eval_rows, long long*
 int avt_debug_nn_sums(avt_ctx* c, int frame, int* cnt, long long* fsum, double* centre) {
     return avt_guard("avt_debug_nn_sums", [&]() -> int {
         if (!c || frame < 0 || frame >= c->fb.max_frames) { avt_set_error("avt_debug_nn_sums: bad argument"); return 1; }
-        // the closing launch of optimize() resets no bookkeeping (launch_lbs with vis_init = -1), so the counts and sums of the last ICP
-        // iteration are still there; a stand-alone avt_nn leaves them for frame 0
-        const bool after_nn = c->nn_sums_frame0 && !c->frames_valid && frame == 0;
-        const bool after_opt = c->frames_valid && c->ran_icp_iters > 0 && frame < c->nframes;
-        if (!after_nn && !after_opt) { avt_set_error("avt_debug_nn_sums: neither a stand-alone avt_nn (frame 0) nor an optimize call with an ICP iteration has run last"); return 1; }
+        if (last_search_left(c, "avt_debug_nn_sums", frame)) return 1;
         const size_t V = c->dm.d.V;
-        AVT_HIP(hipSetDevice(c->device));
-        AVT_HIP(hipStreamSynchronize(c->stream));
-        if (cnt) AVT_HIP(hipMemcpyAsync(cnt, c->fb.cnt + (size_t)frame * V, V * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        if (fsum) AVT_HIP(hipMemcpyAsync(fsum, c->fb.fsum + (size_t)frame * 3 * V, 3 * V * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
         AvtFrameCtl ctl;
-        AVT_HIP(hipMemcpyAsync(&ctl, c->fb.ctl + frame, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
-        AVT_HIP(hipStreamSynchronize(c->stream));
+        if (read_back(c, {{cnt, c->fb.cnt + (size_t)frame * V, V * sizeof(int)}, {fsum, c->fb.fsum + (size_t)frame * 3 * V, 3 * V * sizeof(long long)}, {&ctl, c->fb.ctl + frame, sizeof(ctl)}}))
+            return 1;
         if (centre) for (int k = 0; k < 3; ++k) centre[k] = ctl.centre[k];
         return 0;
     });
 }
 
 int avt_ctx_get_tuning(avt_ctx* c, avt_tuning* out) {
-    if (!c || !out) { avt_set_error("avt_ctx_get_tuning: null argument"); return 1; }
-    *out = c->tun;
-    return 0;
+    return avt_guard("avt_ctx_get_tuning", [&]() -> int {
+        if (!c || !out) { avt_set_error("avt_ctx_get_tuning: null argument"); return 1; }
+        *out = c->tun;
+        return 0;
+    });
 }
 
 int avt_ctx_set_tuning(avt_ctx* c, const avt_tuning* t) {
@@ -1220,11 +1247,7 @@ int avt_ctx_set_tuning(avt_ctx* c, const avt_tuning* t) {
         if (validate_tuning(*t)) return 1;
         AVT_HIP(hipSetDevice(c->device));
         AVT_HIP(hipStreamSynchronize(c->stream));
-        {   // the launch sequences captured so far were made with the old knobs
-            std::lock_guard<std::mutex> graph_lock(g_graph_mutex);
-            for (auto& e : c->graphs) (void)hipGraphExecDestroy(e.exec);
-            c->graphs.clear();
-        }
+        graph_drop_all(c);      // the launch sequences captured so far were made with the old knobs
         c->tun = *t;
         c->vis_frame_min = avt_visibility_frame_lds(c->dm.d) <= 150 * 1024 ? c->tun.vis_frame_min : 0;
         c->fb.ride_timeout = c->tun.ride_timeout_us * 100;
@@ -1234,10 +1257,12 @@ int avt_ctx_set_tuning(avt_ctx* c, const avt_tuning* t) {
 }
 
 int avt_set_data_term(avt_ctx* c, int form) {
-    if (!c || (form != AVT_DATA_TERM_ROWS && form != AVT_DATA_TERM_MOMENTS && form != AVT_DATA_TERM_AUTO)) { avt_set_error("avt_set_data_term: bad argument"); return 1; }
-    if (form == AVT_DATA_TERM_MOMENTS && !c->dm.d.mom_ok) { avt_set_error("avt_set_data_term: this model has no moment form (" + c->mom_reason + ")"); return 1; }
-    c->data_term = form;
-    return 0;
+    return avt_guard("avt_set_data_term", [&]() -> int {
+        if (!c || (form != AVT_DATA_TERM_ROWS && form != AVT_DATA_TERM_MOMENTS && form != AVT_DATA_TERM_AUTO)) { avt_set_error("avt_set_data_term: bad argument"); return 1; }
+        if (form == AVT_DATA_TERM_MOMENTS && !c->dm.d.mom_ok) { avt_set_error("avt_set_data_term: this model has no moment form (" + c->mom_reason + ")"); return 1; }
+        c->data_term = form;
+        return 0;
+    });
 }
 
 int avt_get_data_term(avt_ctx* c) { return c ? c->data_term : -1; }
@@ -1262,11 +1287,7 @@ int avt_set_occlusion_render(avt_ctx* c, int width, int height, float fx, float 
             }
         }
         AVT_HIP(hipStreamSynchronize(c->stream));      // nothing queued reads the old scratch any more
-        {   // the launch sequences captured so far hold the old rule and the old scratch
-            std::lock_guard<std::mutex> graph_lock(g_graph_mutex);
-            for (auto& e : c->graphs) (void)hipGraphExecDestroy(e.exec);
-            c->graphs.clear();
-        }
+        graph_drop_all(c);      // the launch sequences captured so far hold the old rule and the old scratch
         c->occ_faces = std::move(faces); c->occ_order = std::move(order); c->occ_rank = std::move(rank);
         c->occ_fkey = std::move(fkey); c->occ_proj = std::move(proj); c->occ_front = std::move(front);
         c->occ_w = width; c->occ_h = width > 0 ? height : 0;
@@ -1280,48 +1301,34 @@ int avt_set_corr_gate(avt_ctx* c, int n, const double* max_dist) {
         if (!c) { avt_set_error("avt_set_corr_gate: null context"); return 1; }
         const int np = c->dm.d.num_parts;
         if (!max_dist) n = 0;
-        if (n != 0 && n != 1 && n != np) {
-            avt_set_error("avt_set_corr_gate: " + std::to_string(n) + " values; 0 (off), 1 (every part) or num_parts = " + std::to_string(np) + " wanted");
+        if (check_per_part("avt_set_corr_gate", n, np, [&](int i) -> std::string {
+                if (i < 0 || max_dist[i] >= 0.0) return "";      // (a NaN fails every comparison)
+                return "value " + std::to_string(i) + " is negative or not a number (each of the 1 or num_parts = " + std::to_string(np) + " gates is a distance >= 0, +inf allowed)";
+            }))
             return 1;
-        }
-        for (int i = 0; i < n; ++i)
-            if (!(max_dist[i] >= 0.0)) {      // (a NaN fails every comparison)
-                avt_set_error("avt_set_corr_gate: value " + std::to_string(i) + " is negative or not a number (each of the 1 or num_parts = " + std::to_string(np) +
-                              " gates is a distance >= 0, +inf allowed)");
-                return 1;
-            }
-        std::vector<double> g((size_t)np, std::numeric_limits<double>::infinity()), g2((size_t)np);
-        for (int q = 0; q < np && n > 0; ++q) g[(size_t)q] = max_dist[n == 1 ? 0 : q];
-        for (int q = 0; q < np; ++q) g2[(size_t)q] = g[(size_t)q] * g[(size_t)q];
-        c->gate_host = g;
-        if (std::memcmp(g2.data(), c->gate2_host.data(), (size_t)np * sizeof(double)) == 0) return 0;      // what the device holds already
-        AVT_HIP(hipSetDevice(c->device));
-        AVT_HIP(hipStreamSynchronize(c->stream));      // (nothing queued reads gate2_host any more)
-        c->gate2_host = g2;
-        // on the context's stream, behind every search already queued; not part of the launch shape: the captured graphs stay valid
-        AVT_HIP(hipMemcpyAsync((void*)c->fb.gate2, c->gate2_host.data(), (size_t)np * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        AVT_HIP(hipStreamSynchronize(c->stream));      // gate2_host may be rewritten by the next call
-        return 0;
+        c->gate_host = per_part(n, np, max_dist, std::numeric_limits<double>::infinity());
+        std::vector<double> g2((size_t)np);
+        for (int q = 0; q < np; ++q) g2[(size_t)q] = c->gate_host[(size_t)q] * c->gate_host[(size_t)q];
+        return upload_when_changed(c, c->gate2_host, g2.data(), g2.size(), true, [&](const double* src) -> int {
+            AVT_HIP(hipMemcpyAsync((void*)c->fb.gate2, src, (size_t)np * sizeof(double), hipMemcpyHostToDevice, c->stream));
+            return 0;
+        });
     });
 }
 
 int avt_get_corr_gate(avt_ctx* c, double* max_dist) {
-    if (!c || !max_dist) { avt_set_error("avt_get_corr_gate: null argument"); return 1; }
-    std::copy(c->gate_host.begin(), c->gate_host.end(), max_dist);
-    return 0;
+    return avt_guard("avt_get_corr_gate", [&]() -> int {
+        if (!c || !max_dist) { avt_set_error("avt_get_corr_gate: null argument"); return 1; }
+        std::copy(c->gate_host.begin(), c->gate_host.end(), max_dist);
+        return 0;
+    });
 }
 
 int avt_get_gated(avt_ctx* c, int frame, int* gated) {
     return avt_guard("avt_get_gated", [&]() -> int {
         if (!c || !gated || frame < 0 || frame >= c->fb.max_frames) { avt_set_error("avt_get_gated: bad argument"); return 1; }
-        // like the counts and sums (avt_debug_nn_sums): what the last search left, a stand-alone avt_nn in frame 0
-        const bool after_nn = c->nn_sums_frame0 && !c->frames_valid && frame == 0;
-        const bool after_opt = c->frames_valid && c->ran_icp_iters > 0 && frame < c->nframes;
-        if (!after_nn && !after_opt) { avt_set_error("avt_get_gated: neither a stand-alone avt_nn (frame 0) nor an optimize call with an ICP iteration has run last"); return 1; }
-        AVT_HIP(hipSetDevice(c->device));
-        AVT_HIP(hipMemcpyAsync(gated, c->fb.gated + frame, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        AVT_HIP(hipStreamSynchronize(c->stream));
-        return 0;
+        if (last_search_left(c, "avt_get_gated", frame)) return 1;
+        return read_back(c, {{gated, c->fb.gated + frame, sizeof(int)}});
     });
 }
 
@@ -1335,23 +1342,17 @@ int avt_set_corr_trim(avt_ctx* c, int n, const double* quantile, const double* f
             if (n != 0 && (quantile || factor || floor_dist)) { avt_set_error("avt_set_corr_trim: quantile, factor and floor_dist go together (all NULL: off)"); return 1; }
             n = 0;
         }
-        if (n != 0 && n != 1 && n != np) {
-            avt_set_error("avt_set_corr_trim: " + std::to_string(n) + " values; 0 (off), 1 (every part) or num_parts = " + std::to_string(np) + " wanted");
+        if (check_per_part("avt_set_corr_trim", n, np, [&](int i) -> std::string {
+                if (i < 0) return n > 0 && min_matches < 1 ? "min_matches = " + std::to_string(min_matches) + "; >= 1 wanted (values are per part: 1 or num_parts = " + std::to_string(np) + ")" : "";
+                const double r = quantile[i], k = factor[i], fl = floor_dist[i];
+                // (a NaN fails every comparison)
+                if (r > 0.0 && r <= 1.0 && k >= 0.0 && (k == inf || k * k < inf) && fl >= 0.0 && fl < inf) return "";
+                return "value " + std::to_string(i) + " of the 1 or num_parts = " + std::to_string(np) +
+                       " is refused (quantile in (0, 1]; factor >= 0 with a finite square, or +inf; floor_dist >= 0 and finite; no NaN)";
+            }))
             return 1;
-        }
-        if (n > 0 && min_matches < 1) { avt_set_error("avt_set_corr_trim: min_matches = " + std::to_string(min_matches) + "; >= 1 wanted (values are per part: 1 or num_parts = " + std::to_string(np) + ")"); return 1; }
-        for (int i = 0; i < n; ++i) {
-            const double r = quantile[i], k = factor[i], fl = floor_dist[i];
-            // (a NaN fails every comparison)
-            const bool ok = r > 0.0 && r <= 1.0 && k >= 0.0 && (k == inf || k * k < inf) && fl >= 0.0 && fl < inf;
-            if (!ok) {
-                avt_set_error("avt_set_corr_trim: value " + std::to_string(i) + " of the 1 or num_parts = " + std::to_string(np) +
-                              " is refused (quantile in (0, 1]; factor >= 0 with a finite square, or +inf; floor_dist >= 0 and finite; no NaN)");
-                return 1;
-            }
-        }
-        std::vector<double> rho((size_t)np, 1.0), kap((size_t)np, inf), flo((size_t)np, 0.0), set((size_t)3 * np + 1);
-        for (int q = 0; q < np && n > 0; ++q) { const int i = n == 1 ? 0 : q; rho[(size_t)q] = quantile[i]; kap[(size_t)q] = factor[i]; flo[(size_t)q] = floor_dist[i]; }
+        const std::vector<double> rho = per_part(n, np, quantile, 1.0), kap = per_part(n, np, factor, inf), flo = per_part(n, np, floor_dist, 0.0);
+        std::vector<double> set((size_t)3 * np + 1);
         bool on = false;
         for (int q = 0; q < np; ++q) {
             set[(size_t)q] = rho[(size_t)q];
@@ -1368,13 +1369,11 @@ int avt_set_corr_trim(avt_ctx* c, int n, const double* quantile, const double* f
                 if (c->trim_set.reserve(set.size()) || c->trim_thr.reserve(fn) || c->trim_count.reserve(fn)) return 1;
                 c->trim_set_host.clear();
             }
-            if (set != c->trim_set_host) {
-                AVT_HIP(hipStreamSynchronize(c->stream));      // (nothing queued reads trim_set_host any more)
-                c->trim_set_host = set;
-                // on the context's stream, behind every search already queued; not part of the launch shape
-                AVT_HIP(hipMemcpyAsync(c->trim_set.p, c->trim_set_host.data(), set.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-                AVT_HIP(hipStreamSynchronize(c->stream));
-            }
+            if (upload_when_changed(c, c->trim_set_host, set.data(), set.size(), true, [&](const double* src) -> int {
+                    AVT_HIP(hipMemcpyAsync(c->trim_set.p, src, set.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+                    return 0;
+                }))
+                return 1;
         }
         c->trim_rho = rho; c->trim_kappa = kap; c->trim_floor = flo; c->trim_min_matches = mm; c->trim_on = on;
         return 0;
@@ -1382,38 +1381,30 @@ int avt_set_corr_trim(avt_ctx* c, int n, const double* quantile, const double* f
 }
 
 int avt_get_corr_trim(avt_ctx* c, double* quantile, double* factor, double* floor_dist, int* min_matches) {
-    if (!c) { avt_set_error("avt_get_corr_trim: null context"); return 1; }
-    const size_t np = (size_t)c->dm.d.num_parts;
-    const bool never = c->trim_rho.empty();      // never set: off
-    for (size_t q = 0; q < np; ++q) {
-        if (quantile) quantile[q] = never ? 1.0 : c->trim_rho[q];
-        if (factor) factor[q] = never ? std::numeric_limits<double>::infinity() : c->trim_kappa[q];
-        if (floor_dist) floor_dist[q] = never ? 0.0 : c->trim_floor[q];
-    }
-    if (min_matches) *min_matches = c->trim_min_matches;
-    return 0;
+    return avt_guard("avt_get_corr_trim", [&]() -> int {
+        if (!c) { avt_set_error("avt_get_corr_trim: null context"); return 1; }
+        const size_t np = (size_t)c->dm.d.num_parts;
+        const bool never = c->trim_rho.empty();      // never set: off
+        for (size_t q = 0; q < np; ++q) {
+            if (quantile) quantile[q] = never ? 1.0 : c->trim_rho[q];
+            if (factor) factor[q] = never ? std::numeric_limits<double>::infinity() : c->trim_kappa[q];
+            if (floor_dist) floor_dist[q] = never ? 0.0 : c->trim_floor[q];
+        }
+        if (min_matches) *min_matches = c->trim_min_matches;
+        return 0;
+    });
 }
 
-// where the counts of avt_get_gated are valid, those of the trim are
-static int trim_search_ran(avt_ctx* c, const char* who, int frame) {
-    if (frame < 0 || frame >= c->fb.max_frames) { avt_set_error(std::string(who) + ": bad argument"); return 1; }
-    const bool after_nn = c->nn_sums_frame0 && !c->frames_valid && frame == 0;
-    const bool after_opt = c->frames_valid && c->ran_icp_iters > 0 && frame < c->nframes;
-    if (!after_nn && !after_opt) { avt_set_error(std::string(who) + ": neither a stand-alone avt_nn (frame 0) nor an optimize call with an ICP iteration has run last"); return 1; }
-    return 0;
-}
-
+// (where the counts of avt_get_gated are valid, those of the trim are)
 int avt_get_trimmed(avt_ctx* c, int frame, int* total, int* per_part) {
     return avt_guard("avt_get_trimmed", [&]() -> int {
         if (!c || !total) { avt_set_error("avt_get_trimmed: null argument"); return 1; }
-        if (trim_search_ran(c, "avt_get_trimmed", frame)) return 1;
+        if (frame < 0 || frame >= c->fb.max_frames) { avt_set_error("avt_get_trimmed: bad argument"); return 1; }
+        if (last_search_left(c, "avt_get_trimmed", frame)) return 1;
         const int np = c->dm.d.num_parts;
         std::vector<int> n((size_t)np, 0);
-        if (c->trim_last) {      // (a search without trimming dropped nothing, whatever an earlier one left in the block)
-            AVT_HIP(hipSetDevice(c->device));
-            AVT_HIP(hipMemcpyAsync(n.data(), c->trim_count.p + (size_t)frame * np, (size_t)np * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-            AVT_HIP(hipStreamSynchronize(c->stream));
-        }
+        // (a search without trimming dropped nothing, whatever an earlier one left in the block)
+        if (c->trim_last && read_back(c, {{n.data(), c->trim_count.p + (size_t)frame * np, (size_t)np * sizeof(int)}})) return 1;
         *total = 0;
         for (int q = 0; q < np; ++q) { *total += n[(size_t)q]; if (per_part) per_part[q] = n[(size_t)q]; }
         return 0;
@@ -1423,75 +1414,78 @@ int avt_get_trimmed(avt_ctx* c, int frame, int* total, int* per_part) {
 int avt_get_trim_thresholds(avt_ctx* c, int frame, double* T) {
     return avt_guard("avt_get_trim_thresholds", [&]() -> int {
         if (!c || !T) { avt_set_error("avt_get_trim_thresholds: null argument"); return 1; }
-        if (trim_search_ran(c, "avt_get_trim_thresholds", frame)) return 1;
+        if (frame < 0 || frame >= c->fb.max_frames) { avt_set_error("avt_get_trim_thresholds: bad argument"); return 1; }
+        if (last_search_left(c, "avt_get_trim_thresholds", frame)) return 1;
         const int np = c->dm.d.num_parts;
         if (!c->trim_last) { std::fill(T, T + np, std::numeric_limits<double>::infinity()); return 0; }
-        AVT_HIP(hipSetDevice(c->device));
-        AVT_HIP(hipMemcpyAsync(T, c->trim_thr.p + (size_t)frame * np, (size_t)np * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        AVT_HIP(hipStreamSynchronize(c->stream));
-        return 0;
+        return read_back(c, {{T, c->trim_thr.p + (size_t)frame * np, (size_t)np * sizeof(double)}});
     });
 }
 
 int avt_get_visibility(avt_ctx* c, int frame, unsigned char* visible) {
-    if (!c || !visible || frame < 0 || frame >= c->nframes) { avt_set_error("avt_get_visibility: bad argument"); return 1; }
-    if (!c->frames_valid || c->ran_icp_iters <= 0) { avt_set_error("avt_get_visibility: no optimize call with an ICP iteration has run on the resident frames"); return 1; }
-    AVT_HIP(hipSetDevice(c->device));
-    AVT_HIP(hipMemcpyAsync(visible, c->fb.visible + (size_t)frame * c->dm.d.V, (size_t)c->dm.d.V, hipMemcpyDeviceToHost, c->stream));
-    AVT_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return avt_guard("avt_get_visibility", [&]() -> int {
+        if (!c || !visible || frame < 0 || frame >= c->nframes) { avt_set_error("avt_get_visibility: bad argument"); return 1; }
+        if (!c->frames_valid || c->ran_icp_iters <= 0) { avt_set_error("avt_get_visibility: no optimize call with an ICP iteration has run on the resident frames"); return 1; }
+        return read_back(c, {{visible, c->fb.visible + (size_t)frame * c->dm.d.V, (size_t)c->dm.d.V}});
+    });
 }
 
 int avt_debug_trace(avt_ctx* c, int frame, double* out64) {
-    if (!c || !out64 || frame < 0 || frame >= c->fb.max_frames) { avt_set_error("avt_debug_trace: bad argument"); return 1; }
-    AVT_HIP(hipSetDevice(c->device));
-    AVT_HIP(hipStreamSynchronize(c->stream));
-    AVT_HIP(hipMemcpyAsync(out64, c->fb.trace + (size_t)frame * 64, 64 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    AVT_HIP(hipStreamSynchronize(c->stream));
-    return 0;
+    return avt_guard("avt_debug_trace", [&]() -> int {
+        if (!c || !out64 || frame < 0 || frame >= c->fb.max_frames) { avt_set_error("avt_debug_trace: bad argument"); return 1; }
+        return read_back(c, {{out64, c->fb.trace + (size_t)frame * 64, 64 * sizeof(double)}});
+    });
 }
 
 int avt_launch_shape(avt_ctx* c, int* groups, int* frames_per_group, int* eval_workgroups_per_frame) {
-    if (!c || c->nframes <= 0) { avt_set_error("avt_launch_shape: no frames resident"); return 1; }
-    const int use_moments_keep = c->fb.use_moments;
-    c->fb.use_moments = choose_moments(c, c->nframes);      // the shape of the form the next optimize() will choose, whatever ran last
-    const int ng = plan_groups(c, c->nframes), nfg = (c->nframes + ng - 1) / ng;
-    c->fb.use_moments = use_moments_keep;
-    if (groups) *groups = ng;
-    if (frames_per_group) *frames_per_group = nfg;
-    if (eval_workgroups_per_frame) *eval_workgroups_per_frame = choose_G(nfg, ng, c->tun);
-    return 0;
+    return avt_guard("avt_launch_shape", [&]() -> int {
+        if (!c || c->nframes <= 0) { avt_set_error("avt_launch_shape: no frames resident"); return 1; }
+        const int use_moments_keep = c->fb.use_moments;
+        c->fb.use_moments = choose_moments(c, c->nframes);      // the shape of the form the next optimize() will choose, whatever ran last
+        const int ng = plan_groups(c, c->nframes), nfg = (c->nframes + ng - 1) / ng;
+        c->fb.use_moments = use_moments_keep;
+        if (groups) *groups = ng;
+        if (frames_per_group) *frames_per_group = nfg;
+        if (eval_workgroups_per_frame) *eval_workgroups_per_frame = choose_G(nfg, ng, c->tun);
+        return 0;
+    });
 }
 
 int avt_profile_begin(avt_ctx* c) {
-    if (!c) { avt_set_error("avt_profile_begin: null context"); return 1; }
-    c->profiling = true;
-    c->prof_events.clear();
-    c->event_pool_used = 0;
-    return 0;
+    return avt_guard("avt_profile_begin", [&]() -> int {
+        if (!c) { avt_set_error("avt_profile_begin: null context"); return 1; }
+        c->profiling = true;
+        c->prof_events.clear();
+        c->event_pool_used = 0;
+        return 0;
+    });
 }
 
 int avt_profile_select(avt_ctx* c, unsigned mask) {
-    if (!c) { avt_set_error("avt_profile_select: null context"); return 1; }
-    c->prof_mask = mask;
-    return 0;
+    return avt_guard("avt_profile_select", [&]() -> int {
+        if (!c) { avt_set_error("avt_profile_select: null context"); return 1; }
+        c->prof_mask = mask;
+        return 0;
+    });
 }
 
 int avt_profile_end(avt_ctx* c, avt_profile* out) {
-    if (!c || !out) { avt_set_error("avt_profile_end: null argument"); return 1; }
-    AVT_HIP(hipSetDevice(c->device));
-    AVT_HIP(hipStreamSynchronize(c->stream));
-    std::memset(out, 0, sizeof(*out));
-    for (auto& rec : c->prof_events) {
-        float ms = 0.f;
-        AVT_HIP(hipEventElapsedTime(&ms, rec.second.first, rec.second.second));
-        out->ms[rec.first] += ms;
-        out->launches[rec.first] += 1;
-    }
-    c->profiling = false;
-    c->prof_events.clear();
-    c->event_pool_used = 0;
-    return 0;
+    return avt_guard("avt_profile_end", [&]() -> int {
+        if (!c || !out) { avt_set_error("avt_profile_end: null argument"); return 1; }
+        AVT_HIP(hipSetDevice(c->device));
+        AVT_HIP(hipStreamSynchronize(c->stream));
+        std::memset(out, 0, sizeof(*out));
+        for (auto& rec : c->prof_events) {
+            float ms = 0.f;
+            AVT_HIP(hipEventElapsedTime(&ms, rec.second.first, rec.second.second));
+            out->ms[rec.first] += ms;
+            out->launches[rec.first] += 1;
+        }
+        c->profiling = false;
+        c->prof_events.clear();
+        c->event_pool_used = 0;
+        return 0;
+    });
 }
 
 }  // extern "C"

@@ -419,7 +419,7 @@ struct avt_ctx {
     struct GraphEntry { std::string key; hipGraphExec_t exec; unsigned long long last_used; };
     std::vector<GraphEntry> graphs;     // small LRU cache keyed on the launch SHAPE only (frames, groups, grids, iteration counts)
     unsigned long long graph_clock = 0;
-    AvtRunParams params_host = {};      // what fb.params currently holds
+    std::vector<AvtRunParams> params_host;       // what fb.params currently holds (empty: nothing yet)
     std::vector<double> gate_host, gate2_host;   // the gates as avt_set_corr_gate was given them (num_parts, +inf = off) and what fb.gate2 holds
     // avt_set_corr_trim: the settings as given (num_parts each; factor +inf = that part is off, the default), whether any part is on,
     // what trim_set holds, and whether the last search of the context ran with trimming on (else it dropped nothing, whatever
@@ -429,7 +429,6 @@ struct avt_ctx {
     int trim_min_matches = 1;
     bool trim_on = false, trim_last = false;
     DevBuf<double> trim_set, trim_thr; DevBuf<int> trim_count;
-    bool params_valid = false;
     bool frames_valid = false, state_valid = false;   // resident frames / start state usable by avt_optimize_resident
     bool nn_sums_frame0 = false;        // a stand-alone avt_nn has left its counts and sums in frame slot 0 (avt_debug_nn_sums)
     int data_term = AVT_DATA_TERM_AUTO; // AVT_DATA_TERM_* policy (avt_set_data_term)
@@ -464,10 +463,18 @@ void avt_set_error(const std::string& s);
 
 // kernel launch wrappers (avt_kernels.hip / avt_nn.hip)
 enum { SOLVE_INIT = 0, SOLVE_FIRST = 1, SOLVE_NORMAL = 2, SOLVE_DECIDE = 3 /* the accept test of the last trial point alone (moment form) */ };
-void launch_lbs(avt_ctx* c, int nframes, const double* x_state_or_null, const double* w, const double* p, const double* R,
-                int from_state, int vis_init /* -1: leave bookkeeping alone; 0/1: reset it, visibility flags to this value */,
-                bool with_bucket_count = false, bool with_init = false, bool decide = false /* from_state 2: accept test of the last trial point first */,
-                bool write_pc = true /* also the part-sorted copy of the cloud (pcx/pcy/pcz, vis_sorted) */, bool pack = false /* workgroup 0 of every frame also writes the frame's result record (fb.results) */);
+// one k_lbs launch (Avatar::update of `nframes` avatars): where the pose comes from and what rides in the launch
+struct LbsLaunch {
+    const double *w = nullptr, *p = nullptr, *R = nullptr;   // from_state 0: the pose as given (device memory)
+    int from_state = 0;              // 1: from the resident state, 2: from the skeleton tables of the current point
+    int vis_init = -1;               // -1: leave the bookkeeping alone; 0/1: reset it, visibility flags to this value
+    bool with_bucket_count = false;  // trailing workgroups histogram the data labels (first half of launch_bucket)
+    bool with_init = false;          // a trailing workgroup per frame sets up the trial point of the next ICP iteration
+    bool decide = false;             // from_state 2: the accept test of the last trial point first
+    bool write_pc = true;            // also the part-sorted copy of the cloud (pcx/pcy/pcz, vis_sorted)
+    bool pack = false;               // workgroup 0 of every frame also writes the frame's result record (fb.results)
+};
+void launch_lbs(avt_ctx* c, int nframes, const LbsLaunch& a);
 int avt_lbs_set_attributes();
 bool avt_lbs_can_init(const AvtDims& d);
 size_t avt_visibility_frame_lds(const AvtDims& d);

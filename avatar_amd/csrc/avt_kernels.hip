@@ -382,8 +382,10 @@ static size_t lbs_multi_lds(const AvtDims& d, int FT) { return sizeof(double) * 
 
 // with_bucket_count: also histogram the data labels (first half of launch_bucket) in trailing workgroups;
 // with_init: also set up the trial point of the next ICP iteration (one trailing workgroup per frame)
-void launch_lbs(avt_ctx* c, int nframes, const double*, const double* w, const double* p, const double* R, int from_state, int vis_init,
-                bool with_bucket_count, bool with_init, bool decide, bool write_pc, bool pack) {
+void launch_lbs(avt_ctx* c, int nframes, const LbsLaunch& a) {
+    const double *w = a.w, *p = a.p, *R = a.R;
+    const int from_state = a.from_state, vis_init = a.vis_init;
+    const bool with_bucket_count = a.with_bucket_count, with_init = a.with_init, decide = a.decide, write_pc = a.write_pc, pack = a.pack;
     const int nlbs = (c->dm.d.V + 255) / 256;
     const int nb = with_bucket_count ? std::max(1, (c->launch_maxN + BUCKET_TILE - 1) / BUCKET_TILE) : 0;
     // frame batches: several frames per workgroup (k_lbs_multi) - the shapes without an accept test or a trial-point workgroup in the launch
@@ -571,7 +573,7 @@ void launch_budget_set(avt_ctx* c, int* dst, const AvtBudgetChunk& a) {
     hipLaunchKernelGGL(k_budget_set, dim3(1), dim3(256), 0, c->stream, dst, a);
 }
 
-// avt_state_upload_frames: one frame's start state into both the working and the start copy (as upload_state writes them:
+// avt_state_upload_frames: one frame's start state into both the working and the start copy (as avt_state_upload writes them:
 // the state in slot 0, slot 1 zero, a cleared control block with the frame's point count)
 __global__ __launch_bounds__(256) void k_state_install(FrameBuffers fb, AvtStateInstall a, int xsize) {
     const int t = threadIdx.x, f = a.frame;

@@ -1045,7 +1045,7 @@ __global__ __launch_bounds__(NTH) void k_solve(DeviceModel dm_arg, FrameBuffers 
             // per frame wait here, so they always get to run - but WHEN is the dispatcher's business (another stream, another
             // process, a profiler serialising dispatch).  The wait is therefore bounded by wall-clock time (2 s by default), and a
             // role that gives up says so: the frame's fault word makes the host calls that return its result fail
-            // (download_state, avt_shard_gather_download) instead of handing out a fit made from a half-reduced system.
+            // (avt_state_download, avt_shard_gather_download) instead of handing out a fit made from a half-reduced system.
             const unsigned want = (unsigned)(fb.seq * (RIDE * d.NPAIR + fb.nspec_cost));      // (< 2^16: AVT_RIDE_COUNT_MASK)
             const long long t0 = wall_clock64();
             TPROBE(10);
