@@ -499,6 +499,9 @@ int avt_internal_clear_faults(avt_ctx* c);
 // frames whose points already lie in the slots become resident with counts[f] points (avt_frames_subsample_commit): the
 // bookkeeping and control-block writes of avt_frames_upload without its copies (avt_capi.cpp)
 int avt_internal_commit_frames(avt_ctx* c, int nframes, const int* counts, bool same_shape);
+// batch split (avt_shard.cpp): frames received into a device buffer (device_src != 0; else host memory) become the resident frames, as
+// after avt_frames_upload (avt_capi.cpp)
+int avt_internal_install_frames(avt_ctx* c, int nframes, const int* counts, const double* data, const int* labels, int device_src);
 // per-frame ICP budgets (avt_optimize_resident_budgets) and per-frame state installs (avt_state_upload_frames)
 #define AVT_BUDGET_CHUNK 248
 struct AvtBudgetChunk { int f0, n; int b[AVT_BUDGET_CHUNK]; };        // a kernel argument (1 KB)

@@ -108,7 +108,8 @@ int avt_shard_gather_results(avt_shard* s, avt_ctx* ctx, int num_frames, double*
  * every call; nothing on the exchange path reads the environment now.)
  * What IS read from the environment, ONCE, when a handle is created: AVT_RCCL_LIB (avt_shard_create: the first library name tried
  * before librccl.so.1 / librccl.so and torch's bundled copy) and AVT_SHARD_LOOPBACK_TIMEOUT_S (avt_shard_create_loopback /
- * avt_shard_create_shm: how long an exchange may see no progress before the group is declared broken; 60 s). */
+ * avt_shard_create_shm: how long an exchange may see no progress before the group is declared broken; default 20 s for the threads
+ * of the loop-back transport, 60 s for the processes of the shared-memory transport). */
 int avt_shard_set_self_exchange(avt_shard* s, int on);
 
 /* ---- barrier on the device (a 1-double all-gather), for hosts without another rendezvous */
